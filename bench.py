@@ -10,10 +10,13 @@ all-gather of the scores closes each step.  Two ways to get the N ranks:
   * `python bench.py --gpus N` on its own: the parent process starts the N ranks itself as child processes BEFORE it makes
     any GPU call (never an exec from a process that touched the GPU), forwards rank 0's JSON line and exits non-zero if
     any rank failed.
-Inputs are synthetic and resident in HBM before the timed region.  Rank 0 prints ONE JSON line.  Beside `value` (exactly K steps
-after W warm-up steps, as the driver asks) the line carries `sustained`: the same workload after >= 2 s of back-to-back forwards,
-timed over >= 3 s (the chip's clock under load settles over seconds), and `fidelity`: what every numerics mode does to
-SROCC / KROCC / PLCC / RMSE against the fp32 oracle's scores on a distortion ladder.
+Inputs are synthetic and resident in HBM before the timed region.  Rank 0 prints ONE JSON line.  A plain run times exactly K steps
+after W warm-up steps and prints `value` / `ms_per_step`, nothing else.  With --full the line also carries the roofline of the
+dominant kernel (HIP events in the timed steps), `sustained`: the same workload after >= 2 s of back-to-back forwards, timed over
+>= 3 s (the chip's clock under load settles over seconds), `fidelity`: what every numerics mode does to SROCC / KROCC / PLCC /
+RMSE against the fp32 oracle's scores on a distortion ladder, and the other optional blocks (--no-<block> skips one of them).
+--dump-outputs DIR writes the scores of the last timed step to DIR/q.npy (float32); inputs and weights are seeded, so two
+builds can be compared output for output.
 """
 import argparse
 import json
@@ -107,6 +110,14 @@ def synth_inputs_on_device(torch, B, N, device, seed):
     dist = (ref + 0.1 * torch.randn(ref.shape, device=device, generator=g)).clamp_(-1, 1)
     pos = torch.rand(B, N, 2, device=device, generator=g).clamp_(max=1 - 1e-6)
     return (ref, dist), (pos, pos.clone()), (None, None)
+
+
+def dump_outputs(out_dir, q):
+    """--dump-outputs: what a caller of the timed path receives from its last step -- the gathered scores q[global_batch], global
+    pair order, float32 (4 bytes per pair)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "q.npy"), q.detach().float().cpu().numpy().astype(np.float32))
 
 
 LADDER_SIGMAS = (0.02, 0.05, 0.1, 0.15, 0.2, 0.3, 0.4, 0.5)
@@ -480,6 +491,11 @@ def main():
     ap.add_argument("--batch", type=int, default=32, help="pairs per GPU (BASELINE config 2: 32)")
     ap.add_argument("--patches", type=int, default=500)
     ap.add_argument("--precision", default=os.environ.get("VTAMIQ_BENCH_PRECISION", HEADLINE), choices=sorted(MFMA_PER_PRODUCT))
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the scores of the last timed step to DIR/q.npy (float32, global pair order)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: roofline, sustained, other modes, north star, e2e, secondary, latency, long "
+                         "sequences, collective, auto overhead, oracle parity, CPU baseline, fidelity, live traffic (--no-<block> skips one)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-second-mode", action="store_true")
     ap.add_argument("--no-north-star", action="store_true")
@@ -540,7 +556,7 @@ def main():
     # One GPU: the RCCL path is still exercised -- a world-size-1 process group on the nccl backend (= RCCL) and the real
     # gather_scores -> all_gather_into_tensor on the compute stream.  A failure here is recorded, never fatal.
     collective = None
-    if world == 1 and on_gpu and not a.stub and not a.no_collective_check:
+    if world == 1 and on_gpu and not a.stub and a.full and not a.no_collective_check:
         try:
             os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
             os.environ.setdefault("MASTER_PORT", str(_free_port()))
@@ -651,6 +667,8 @@ def main():
         from tests.bench_stub import StubModel
         dt, q, _ = run(StubModel(), a.steps, a.warmup)
         assert q.shape == (global_batch,)
+        if rank == 0 and a.dump_outputs:
+            dump_outputs(a.dump_outputs, q)
         if rank == 0:
             print(file=real_stdout, flush=True, *[json.dumps({"metric": "launcher self-test (stub model, no HIP)", "value": global_batch * a.steps / dt,
                               "unit": "image-pairs/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
@@ -666,7 +684,7 @@ def main():
         return
 
     from vtamiq_amd import VTAMIQ, synth, _lib as _vlib
-    fp8_ok = bool(on_gpu and _vlib.fp8_available())
+    fp8_ok = bool(on_gpu and (a.full or a.precision == "fp8") and _vlib.fp8_available())     # a plain run loads only the library it times
     if a.precision == "fp8" and not fp8_ok:
         sys.exit("bench.py --precision fp8: vtamiq_amd/libvtamiq_hip_fp8.so (the fp8 experiment's library) is not built: python -m vtamiq_amd.build --fp8")
 
@@ -676,7 +694,8 @@ def main():
         from vtamiq_amd.experimental_fp8 import VTAMIQFp8
         return VTAMIQFp8
     kw = dict(vit_config=dict(variant="ViT-B16", pretrained=False))   # L=12, T=1, r=8: BASELINE configs 2/3 and north star; seeded weights
-    spec = model_class(a.precision)(**json.loads(json.dumps(kw)), precision=a.precision).spec
+    model = model_class(a.precision)(**json.loads(json.dumps(kw)), precision=a.precision)      # constructed once: its spec seeds the weights
+    spec = model.spec
     sd_np = synth.make_state_dict(spec, 0)
     state = {k: torch.from_numpy(v) for k, v in sd_np.items()}
 
@@ -685,15 +704,19 @@ def main():
         m.load_state_dict(state)
         return m.to(device).eval()
 
-    model = make_model(a.precision)
+    model.load_state_dict(state)
+    model = model.to(device).eval()
     DOM = "fc1"
-    dt, q, prof = run(model, a.steps, a.warmup, profile_class=DOM)
+    # a plain run times the bare steps; --full records HIP events around every fc1 launch in them (`roofline`)
+    dt, q, prof = run(model, a.steps, a.warmup, profile_class=DOM if a.full else None)
     assert q.shape == (global_batch,) and bool(torch.isfinite(q).all())
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, q)
     pairs_per_s = global_batch * a.steps / dt
     headline_rank_times = list(rank_times)
     headline_event_ms = event_ms[0] / a.steps if event_ms else None
     allgather_us = None
-    if world > 1:                                 # the step's one collective, timed alone: a missed scaling target can be read off the record
+    if world > 1 and a.full:                      # the step's one collective, timed alone: a missed scaling target can be read off the record
         qloc = torch.zeros(B, device=device)
         for _ in range(10):
             gather_scores(qloc, global_batch)
@@ -726,7 +749,7 @@ def main():
         except Exception as e:                       # pragma: no cover
             collective = {"collective_executed": False, "error": f"{e!r}"[:300]}
     auto_cost = None
-    if on_gpu and world == 1 and not a.no_auto_overhead and a.precision == HEADLINE:
+    if a.full and on_gpu and world == 1 and not a.no_auto_overhead and a.precision == HEADLINE:
         # what a default-constructed model costs on top of this line's mode: precision="auto" = fp16x3 + the engine's error word read after
         # every forward (one 4-byte D2H + stream sync per call), same K steps after the same warm-up, measured in this run
         try:
@@ -739,7 +762,7 @@ def main():
             auto_cost = {"error": f"{e!r}"[:300]}
         torch.cuda.empty_cache()
     sustained = None
-    if on_gpu and world == 1 and not a.no_sustained:
+    if a.full and on_gpu and world == 1 and not a.no_sustained:
         n_s, dt_s, prof_s = run_sustained(model, a.sustained_seconds[0], a.sustained_seconds[1], profile_class=DOM)
         sustained = {"value": B * n_s / dt_s, "unit": "image-pairs/s", "forwards": n_s, "seconds": dt_s, "warmup_seconds": a.sustained_seconds[0],
                      "ms_per_step": dt_s / n_s * 1e3,
@@ -837,7 +860,7 @@ def main():
                 rf["practical_peak_as_frac_of_nominal"] = pk["operands_of_this_mode"]["tflops"] / PEAK_BF16_TFLOPS
                 out["forward_frac_of_practical"] = out["forward_mfma_frac"] * PEAK_BF16_TFLOPS * MFMA_PER_PRODUCT[a.precision] / pk["operands_of_this_mode"]["tflops"]
     q_other = {}
-    if not a.no_second_mode and (world == 1 or a.other_modes_multi_gpu):      # every rank: run() is collective; N > 1: the headline mode only by default
+    if a.full and not a.no_second_mode and (world == 1 or a.other_modes_multi_gpu):      # every rank: run() is collective; N > 1: the headline mode only by default
         del model
         torch.cuda.empty_cache()
         out["other_modes"] = {}
@@ -851,7 +874,7 @@ def main():
                                          "mfma_per_product_linear": MFMA_PER_PRODUCT[other]}
             del model2
             torch.cuda.empty_cache()
-    if not a.no_north_star and world == 1:
+    if a.full and not a.no_north_star and world == 1:
         # BASELINE north-star operating point: B = 64 pairs on one GPU, every numerics mode (the >= 40 % target is stated on it)
         Bn = 64
         inp64 = synth_inputs_on_device(torch, Bn, N, device, 4321)
@@ -866,7 +889,7 @@ def main():
             del m
             torch.cuda.empty_cache()
         out["north_star_point"] = ns
-    if not a.no_e2e and world == 1 and on_gpu:
+    if a.full and not a.no_e2e and world == 1 and on_gpu:
         me = make_model(a.precision)
         out["e2e"] = e2e_validation(torch, me, B, N, device)
         out["e2e"]["frac_of_value"] = out["e2e"]["value"] / pairs_per_s
@@ -874,7 +897,7 @@ def main():
         out["e2e"]["numerics"] = a.precision
         del me
         torch.cuda.empty_cache()
-    if not a.no_secondary and world == 1 and on_gpu:
+    if a.full and not a.no_secondary and world == 1 and on_gpu:
         # SURVEY 8(d) secondary row: the reference-default topology -- what the released checkpoint runs (train_config.py:169-194,
         # 356-369: 6 kept layers, 8 register tokens, LayerScale, ca_reduction 16) at B = 16, N = 512
         kw2 = dict(vit_config=dict(variant="ViT-B16", pretrained=False, num_keep_layers=6, num_extra_tokens=8, use_layer_scale=True), ca_reduction=16)
@@ -893,7 +916,7 @@ def main():
                             "flops_per_pair": spec2.flops_per_pair(N2), "flops_per_pair_executed": f2, "seq_len": spec2.seq_len(N2)}
         del m2
         torch.cuda.empty_cache()
-    if not a.no_latency and world == 1 and on_gpu:
+    if a.full and not a.no_latency and world == 1 and on_gpu:
         kwl = dict(vit_config=dict(variant="ViT-B16", pretrained=False, num_keep_layers=6, num_extra_tokens=8, use_layer_scale=True), ca_reduction=16)
 
         def make_refdefault(precision):
@@ -907,7 +930,7 @@ def main():
                                                             "rows": latency_block(torch, make_refdefault, a.precision, device, 512, batches=(1, 16))}
         except Exception as e:                           # an optional block never costs the line
             out.setdefault("latency", {})["error"] = f"{e!r}"[:300]
-    if not a.no_long_sequence and world == 1 and on_gpu:
+    if a.full and not a.no_long_sequence and world == 1 and on_gpu:
         try:
             out["long_sequence"] = {"numerics": a.precision, "workload": "ViT-B/16 (L=12, T=1) FR pair forward, 4 pairs per forward at 2500 / 5000 patches "
                                                                          "(reference README.md:85: '50, 500, and 5000 patches')",
@@ -915,7 +938,7 @@ def main():
         except Exception as e:                           # an optional block never costs the line
             out["long_sequence"] = {"error": f"{e!r}"[:300]}
     # N > 1: scaling against the committed N = 1 line of this tree's bench.py (the driver computes its own efficiency from its own runs)
-    if world > 1 and rank == 0:
+    if a.full and world > 1 and rank == 0:
         import glob
         for path in sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_bench_line.json")), reverse=True):
             try:
@@ -932,7 +955,7 @@ def main():
         dist.barrier()
     if dist.is_initialized():
         dist.destroy_process_group()
-    if rank == 0:
+    if a.full and rank == 0:
         # parity of both modes on the first pairs of rank 0's shard, against the oracle on the host (not timed)
         from oracle import vtamiq_oracle as O
         nchk = 2
@@ -975,6 +998,7 @@ def main():
                                                          "run: busy SIMD-cycles / (1024 SIMDs x GRBM_GUI_ACTIVE / 8 XCDs)")
             else:
                 out["roofline"]["traffic_live_error"] = src
+    if rank == 0:
         print(json.dumps(out), file=real_stdout, flush=True)
 
 

@@ -89,3 +89,22 @@ def test_live_traffic_fails_gracefully_without_a_gpu(monkeypatch):
     monkeypatch.setenv("ROCPROF_OUTPUT_PATH", "/tmp/x")
     tb, why = bench.live_fc1_traffic("fp16x3", 32, 501)
     assert tb is None and "profiler" in why
+
+
+def test_dump_outputs_writes_the_last_step_scores(tmp_path):
+    """--dump-outputs DIR: the scores rank 0 received in the last timed step, float32, global pair order; the seeded inputs make two
+    runs with the same arguments write the same array."""
+    import numpy as np
+    dumps = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        p = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "3", "--patches", "5", "--backend", "gloo", "--stub",
+                  "--dump-outputs", str(d)])
+        assert p.returncode == 0, p.stderr[-2000:]
+        line = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][0])
+        assert line["steps"] == 2 and line["ms_per_step"] > 0
+        q = np.load(d / "q.npy")
+        assert q.dtype == np.float32 and q.shape == (6,)
+        assert abs(float(q.astype(np.float64).sum()) - _expected_checksum(2, 3, 5)) < 1e-4
+        dumps.append(q)
+    assert np.array_equal(dumps[0], dumps[1])

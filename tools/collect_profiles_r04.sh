@@ -6,9 +6,9 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r04p; mkdir -p $O
 cd $R
 timeout 2400 python3 -m pytest tests -m gpu -q > $O/pytest_gpu.txt 2>&1; tail -3 $O/pytest_gpu.txt
 python3 -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.txt 2>&1; tail -1 $O/smoke.txt
-python3 bench.py > $O/bench_line.json 2> $O/bench_line.err
+python3 bench.py --full > $O/bench_line.json 2> $O/bench_line.err
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o s -- python3 $R/bench.py --no-cpu-baseline --no-second-mode --no-north-star --no-fidelity --no-sustained --no-live-traffic --no-e2e --no-secondary --no-collective-check > $O/bench_line_headline_profiled.json 2> $O/stats.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o s -- python3 $R/bench.py --full --no-cpu-baseline --no-second-mode --no-north-star --no-fidelity --no-sustained --no-live-traffic --no-e2e --no-secondary --no-collective-check > $O/bench_line_headline_profiled.json 2> $O/stats.err
 G="python3 $R/tools/gemm_bench.py --only fc1 --rounds 1 --fmt fp16x3 fp16"
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/fetch -o f -- $G > $O/fetch.log 2>&1
 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/write -o w -- $G > $O/write.log 2>&1

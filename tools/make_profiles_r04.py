@@ -50,7 +50,7 @@ lh = [l for l in open(os.path.join(G, "bench_line_headline_profiled.json")) if l
 dh = json.loads(lh)
 write("r04_bench_line_headline_profiled.json", lh)
 write("r04_bench_headline_kernel_stats.txt",
-      "# command: rocprofv3 --kernel-trace --stats -- python3 bench.py --no-cpu-baseline --no-second-mode --no-north-star --no-fidelity --no-sustained --no-live-traffic\n"
+      "# command: rocprofv3 --kernel-trace --stats -- python3 bench.py --full --no-cpu-baseline --no-second-mode --no-north-star --no-fidelity --no-sustained --no-live-traffic\n"
       "#          --no-e2e --no-secondary --no-collective-check      (only the headline mode at B = 32 runs: 5 warm-up + 20 timed forwards)\n"
       f"# the same process printed roofline.avg_launch_ms = {dh['roofline']['avg_launch_ms']:.4f} ms for gemm_pp2_kernel<f16, 3, 1> (fc1, HIP events on the\n"
       "# launch stream inside the timed region); the rocprofv3 average below covers warm-up + timed launches of the same kernel.\n"

@@ -1,7 +1,7 @@
 #!/bin/bash
 # the default bench line of this tree (what the driver runs)
 O=gpurun_out/r05e; mkdir -p $O
-timeout 900 python3 bench.py > $O/bench_line.json 2> $O/bench_err.txt
+timeout 900 python3 bench.py --full > $O/bench_line.json 2> $O/bench_err.txt
 python3 - <<'PY'
 import json
 d=json.load(open('gpurun_out/r05e/bench_line.json'))

@@ -13,9 +13,10 @@ timeout 300 python3 tools/small_batch.py --refdefault --batches 1 16 --patches 5
 timeout 400 python3 tools/gemm_stress.py --seconds 200 --seed 31 > $O/gemm_stress.txt 2>&1
 timeout 300 python3 tools/attn_stress.py --seconds 120 --seed 32 > $O/attn_stress.txt 2>&1
 timeout 400 python3 tools/forward_stress.py --seconds 200 --seed 33 > $O/forward_stress.txt 2>&1
-timeout 900 python3 bench.py > $O/bench_line.json 2> $O/bench_err.txt
+timeout 900 python3 bench.py --full > $O/bench_line.json 2> $O/bench_err.txt
+R=$PWD
 cd /tmp && export TMPDIR=/tmp
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/$O/prof_bench -o p -- python3 $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --no-second-mode --no-north-star --no-live-traffic --no-sustained --no-fidelity --no-e2e --no-secondary --no-latency --no-practical-peak --no-auto-overhead --no-collective-check > $GRAFT_REPO_ROOT/$O/bench_line_headline_profiled.json 2>/dev/null
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/prof_bench -o p -- python3 $R/bench.py --full --no-cpu-baseline --no-second-mode --no-north-star --no-live-traffic --no-sustained --no-fidelity --no-e2e --no-secondary --no-latency --no-practical-peak --no-auto-overhead --no-collective-check > $R/$O/bench_line_headline_profiled.json 2>/dev/null
 cd $GRAFT_REPO_ROOT
 python3 tools/summarize_prof.py stats $O/prof_bench > $O/bench_headline_kernel_stats.txt 2>&1; rm -rf $O/prof_bench
 cat $O/pytest_gpu.txt $O/pytest_gpu_fp8_build.txt; tail -1 $O/smoke.txt; tail -1 $O/gemm_stress.txt; tail -1 $O/attn_stress.txt; tail -1 $O/forward_stress.txt; grep -c DIFFERENT $O/st_*.txt

@@ -4,7 +4,7 @@ cd "$(dirname "$0")/../.."
 O=gpurun_out/r06n; mkdir -p $O
 timeout 2400 python3 -m pytest tests -m gpu -q 2>&1 | tail -4 > $O/pytest_gpu.txt; cat $O/pytest_gpu.txt
 timeout 300 python3 -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.txt 2>&1; tail -2 $O/smoke.txt
-timeout 900 python3 bench.py > $O/bench_line.json 2> $O/bench_stderr.txt
+timeout 900 python3 bench.py --full > $O/bench_line.json 2> $O/bench_stderr.txt
 python3 - <<'PY'
 import json
 d = json.load(open("gpurun_out/r06n/bench_line.json"))
