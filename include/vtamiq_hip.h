@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define VTQ_ABI_VERSION 9
+#define VTQ_ABI_VERSION 10
 
 /* numerics mode of the dense contractions (fp32 accumulate, fp32 LayerNorm/softmax/residual in all of them).
  * bf16 and fp16 MFMAs run at the same rate on gfx950; fp16 carries 11 significand bits instead of 8 in the range the reference's
@@ -127,6 +127,19 @@ int  vtq_forward_pairwise(vtq_handle h, const float* const* patches, const float
  * pointers {ref, dist1, dist2}, each (B, N, hidden_size) fp32 contiguous.  Bit-identical to two vtq_forward_tokens calls. */
 int  vtq_forward_pairwise_tokens(vtq_handle h, const float* const* feats, const float* const* pos, const float* const* scales,
                                  int32_t B, int32_t N, float* q_out, void* stream);
+
+/* VisionTransformerBackbone.forward_vit (backbone.py:54-60, transformer.py:628-641, 363-378) on B SINGLE images: the encoder with no head.
+ *   in       (B, N, 3, P, P) fp32 patches, or (tokens_in != 0) (B, N, hidden_size) pre-embedded rows; pos (B, N, 2); scales (B, N) or NULL
+ *            (required when num_scales > 1) -- as one image of vtq_forward / vtq_forward_tokens.
+ *   Rows per sequence: R = T = 1 + num_extra_tokens (all_tokens == 0, tokens_only=True) or R = S = N + T (all_tokens != 0).
+ *   out      (B, R, hidden_size) fp32: encoder_norm of the last layer's rows.  Required.
+ *   states   NULL, or (L, B, R, hidden_size) fp32: the residual stream after each layer, before encoder_norm (no embedding output).
+ *   probs    NULL, or (L, B, num_heads, S, S) fp32: each layer's attention probabilities softmax(Q K^T / sqrt(64)).
+ * The last layer always runs on every row (the result of VTQ_OPT_FULL_LAST_LAYER); the adapter pair 0 applies as in vtq_forward.
+ * Caller-owned device buffers, asynchronous on `stream`; positions outside [0, 1) are recorded in vtq_input_errors bit 0, a
+ * non-finite output value in bit 1.  Refused: the fp8 experiment's handle, a NULL out / in / pos, B or N < 1. */
+int  vtq_forward_vit(vtq_handle h, const float* in, int32_t tokens_in, const float* pos, const float* scales, int32_t B, int32_t N,
+                     int32_t all_tokens, float* out, float* states, float* probs, void* stream);
 
 /* Input check.  The reference raises (IndexError / device assert) when a position lies outside [0, 1)
  * (transformer.py:417-421); vtq_forward clamps such an index into the table instead of gathering out of bounds and records it.
@@ -246,6 +259,13 @@ int  vtq_k_layernorm(const float* x, const float* w, const float* b, void* out, 
  * sequences are S_pad rows apart, keys >= S are masked; out[rows, H] planes, heads merged (transformer.py:153-166). */
 int  vtq_k_attention(const void* qkv, int64_t plane, void* out, int64_t o_plane,
                      int32_t nseq, int32_t S, int32_t S_pad, int32_t H, int32_t num, void* stream);
+
+/* Attention probabilities of every (sequence, head) on the same qkv planes as vtq_k_attention (num = VTQ_NUM_* with 1 or 3 terms):
+ * probs[nseq][H / 64][S][S] fp32 = softmax(Q K^T / sqrt(64)) over the keys < S of each sequence; q_log2 != 0 (3-term formats only): Q
+ * already carries 1/sqrt(64) * log2(e), as the engine's query projection does in those formats.  Reads only rows [s * S_pad, s * S_pad + S)
+ * of sequence s. */
+int  vtq_k_attention_probs(const void* qkv, int64_t plane, float* probs, int32_t nseq, int32_t S, int32_t S_pad, int32_t H, int32_t num,
+                           int32_t q_log2, void* stream);
 
 /* One skinny linear stage on the MFMA pipe (CLS tail of the last layer, DiffNet head): out[R, N] = act[R, K] * W[N, K]^T + bias,
  * operands as 16-bit planes in format `num` (VTQ_NUM_*): xa [planes][>= ceil64(R)][ldx], W [planes][ceil16(N)][K], K % 32 == 0.

@@ -271,6 +271,26 @@ __global__ __launch_bounds__(64) void final_diff_kernel(const float* __restrict_
     }
 }
 
+// encoder_norm on `rows` token rows of every sequence (forward_vit, transformer.py:376): fp32 rows out[seq][rows][H], packed with
+// no batch padding.  One wave per row (grid: rows x nseq); a non-finite output value raises bit 1 of the error word, as
+// final_diff_kernel does for the CLS difference.
+template <int V4>
+__global__ __launch_bounds__(64) void seq_rows_ln_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ b,
+                                                         float* __restrict__ out, SeqMap sm, int rows, int* __restrict__ err) {
+    constexpr int H = 256 * V4;
+    const int lane = threadIdx.x, j = blockIdx.x, seq = blockIdx.y;
+    float4 y[V4];
+    ln_row<V4>(x + (seq_row(sm, seq) + j) * H, w, b, lane, y);
+    float4* o = (float4*)(out + ((int64_t)seq * rows + j) * H);
+    bool ok = true;
+#pragma unroll
+    for (int i = 0; i < V4; ++i) {
+        o[i * 64 + lane] = y[i];
+        ok = ok && isfinite(y[i].x) && isfinite(y[i].y) && isfinite(y[i].z) && isfinite(y[i].w);
+    }
+    if (err && !ok) atomicOr(err, 2);
+}
+
 inline int grid_for(int64_t work, int block) {
     int64_t g = (work + block - 1) / block;
     return (int)(g < 1 ? 1 : (g > 256 * 16 ? 256 * 16 : g));
@@ -401,6 +421,15 @@ hipError_t launch_final_diff(const float* x, const float* ln_w, const float* ln_
                              SeqMap sm, int H, PlaneOut po, hipStream_t s, int* err) {
     if (H == 768) hipLaunchKernelGGL(final_diff_kernel<3>, dim3(B, ndist), dim3(64), 0, s, x, ln_w, ln_b, gamma, d, B, sm, po, err);
     else if (H == 1024) hipLaunchKernelGGL(final_diff_kernel<4>, dim3(B, ndist), dim3(64), 0, s, x, ln_w, ln_b, gamma, d, B, sm, po, err);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+hipError_t launch_seq_rows_ln(const float* x, const float* ln_w, const float* ln_b, float* out, int nseq, SeqMap sm, int rows, int H,
+                              hipStream_t s, int* err) {
+    if (nseq < 1 || rows < 1) return hipErrorInvalidValue;
+    if (H == 768) hipLaunchKernelGGL(seq_rows_ln_kernel<3>, dim3(rows, nseq), dim3(64), 0, s, x, ln_w, ln_b, out, sm, rows, err);
+    else if (H == 1024) hipLaunchKernelGGL(seq_rows_ln_kernel<4>, dim3(rows, nseq), dim3(64), 0, s, x, ln_w, ln_b, out, sm, rows, err);
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }

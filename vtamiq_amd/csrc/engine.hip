@@ -141,6 +141,10 @@ struct vtq_engine {
     int* err_flag = nullptr;             // device word (vtq_input_errors): bit 0 = a position outside [0, 1) was clamped, bit 1 = non-finite CLS difference
     std::vector<void*> ws_allocs;
     float* trace = nullptr;
+    // vtq_forward_vit (one call's worth; NULL / 0 otherwise): per-layer residual rows (vit_rows per sequence) and attention probabilities
+    float* vit_states = nullptr;
+    float* vit_probs = nullptr;
+    int vit_rows = 0;
     int iqa_token = 0;                          // vtamiq.py:57, 107-108: the token row the head consumes (0 = CLS, 1 .. = register tokens)
     // profiling
     uint32_t prof_mask = 0;
@@ -321,7 +325,7 @@ struct Geometry {
     SeqMap sm;
 };
 
-// nimg images per item: 2 = (ref, dist) FR pair, 3 = (ref, dist1, dist2) pairwise triplet
+// nimg images per item: 1 = single images (vtq_forward_vit), 2 = (ref, dist) FR pair, 3 = (ref, dist1, dist2) pairwise triplet
 Geometry geometry(const vtq_engine* e, int B, int N, int nimg = 2) {
     Geometry g;
     g.S = N + e->T;
@@ -563,6 +567,10 @@ int run_encoder(vtq_engine* e, const Geometry& g, hipStream_t s, bool prune) {
             if (f8m) {
                 if (fp8_stage(e, s, e->s_att[i], [&](float sc, Fp8Obs ob) { HIP_TRY(launch_attention(big, e->big_plane, lnb, e->ln_plane, g.nseq, g.S, g.S_pad, H, e->att, s, sc, ob, e->att.terms == 3)); return 0; })) return 1;
             } else HIP_TRY(launch_attention(big, e->big_plane, lnb, e->ln_plane, g.nseq, g.S, g.S_pad, H, e->att, s, 0.0f, Fp8Obs{nullptr, nullptr}, e->att.terms == 3));
+            // forward_vit's attention maps: from the same QKV planes, before the out-proj (with adapters it reuses `big`)
+            if (e->vit_probs)
+                HIP_TRY(launch_attention_probs(big, e->big_plane, e->vit_probs + (int64_t)i * g.nseq * (H / 64) * g.S * g.S, g.nseq, g.S, g.S_pad, H,
+                                               e->att, s, e->att.terms == 3));
         }
         if (e->dbg_stop == i * 7 + 2) return 0;
         {
@@ -622,6 +630,7 @@ int run_encoder(vtq_engine* e, const Geometry& g, hipStream_t s, bool prune) {
         }
         if (e->dbg_stop == i * 7 + 6) return 0;
         if (e->trace) HIP_TRY(launch_copy_tokens(x, e->trace + (i + 1) * trace_stride, g.nseq, g.sm, T, H, s));
+        if (e->vit_states) HIP_TRY(launch_copy_tokens(x, e->vit_states + (int64_t)i * g.nseq * e->vit_rows * H, g.nseq, g.sm, e->vit_rows, H, s));
     }
     return 0;
 }
@@ -935,14 +944,15 @@ int vtq_profile_collect(vtq_handle e, double* ms_sum, int64_t* launches) {
     return 0;
 }
 
-// nimg = 2: q_out[B] for (ref, dist); nimg = 3: q_out[2B] = scores of (ref, dist1) then (ref, dist2) with ref encoded once
+// nimg = 2: q_out[B] for (ref, dist); nimg = 3: q_out[2B] = scores of (ref, dist1) then (ref, dist2) with ref encoded once;
+// nimg = 1 (vtq_forward_vit): no head -- vit_out receives encoder_norm of `vit_rows` rows per image (e->vit_states / vit_probs set by the caller)
 static int forward_impl(vtq_handle e, int nimg, const float* const* patches, const float* const* pos, const float* const* scales,
-                        int32_t B, int32_t N, float* q_out, void* stream, bool tokens_in = false) {
+                        int32_t B, int32_t N, float* q_out, void* stream, bool tokens_in = false, float* vit_out = nullptr) {
     if (!e) return fail("vtq_forward: null handle");
     if (tokens_in && e->fp8) return fail("vtq_forward_tokens: the fp8 experiment has no pre-embedded input path");
     for (int k = 0; k < nimg; ++k)
         if (!patches[k] || !pos[k]) return fail("vtq_forward: null tensor");
-    if (!q_out) return fail("vtq_forward: null output");
+    if (!q_out && nimg > 1) return fail("vtq_forward: null output");
     if (B < 1 || N < 1) return fail("vtq_forward: B=%d N=%d", B, N);
     const vtq_config& c = e->cfg;
     const bool use_scales = c.num_scales > 1;
@@ -1017,8 +1027,14 @@ static int forward_impl(vtq_handle e, int nimg, const float* const* patches, con
     // the trace tap needs every token row of the last layer; sequences longer than the CLS kernel's LDS score buffer run the
     // full last layer instead (same result)
     // (fp8 mode runs the full last layer: its CLS row then goes through the same e4m3 GEMMs as every other row)
-    const bool prune = e->cls_prune && !e->trace && !e->fp8 && c.num_adapters == 0 && g.S <= cls_attention_max_seq();
+    // (forward_vit needs every row of the last layer: always the full last layer)
+    const bool prune = e->cls_prune && !e->trace && !e->fp8 && c.num_adapters == 0 && g.S <= cls_attention_max_seq() && nimg > 1;
     if (run_encoder(e, g, s, prune)) return 1;
+    if (nimg == 1) {                 // ---- forward_vit: encoder_norm (transformer.py:376) of the requested rows, no head
+        Prof p(e, s, VTQ_K_LN);
+        HIP_TRY(launch_seq_rows_ln(e->x, e->encw, e->encb, vit_out, g.nseq, g.sm, e->vit_rows, H, s, e->err_flag));
+        return 0;
+    }
 
     // ---- head (vtamiq.py:104-117) ------------------------------------------------------------------------------
     {
@@ -1111,6 +1127,24 @@ int vtq_forward_pairwise_tokens(vtq_handle e, const float* const* feats, const f
     return forward_impl(e, 3, feats, pos, sc, B, N, q_out, stream, true);
 }
 
+int vtq_forward_vit(vtq_handle e, const float* in, int32_t tokens_in, const float* pos, const float* scales, int32_t B, int32_t N,
+                    int32_t all_tokens, float* out, float* states, float* probs, void* stream) {
+    if (!e) return fail("vtq_forward_vit: null handle");
+    if (e->fp8) return fail("vtq_forward_vit: not available for the fp8 experiment's engine");
+    if (!in || !pos) return fail("vtq_forward_vit: null input");
+    if (!out) return fail("vtq_forward_vit: null output");
+    if (B < 1 || N < 1) return fail("vtq_forward_vit: B=%d N=%d", (int)B, (int)N);
+    // two-entry arrays: the embedding launches read the second image's pointer slot (unused with nimg = 1)
+    const float* p[2] = {in, nullptr};
+    const float* ps[2] = {pos, nullptr};
+    const float* sc[2] = {scales, nullptr};
+    struct Reset { vtq_engine* e; ~Reset() { e->vit_states = nullptr; e->vit_probs = nullptr; e->vit_rows = 0; } } reset{e};
+    e->vit_states = states;
+    e->vit_probs = probs;
+    e->vit_rows = all_tokens ? N + e->T : e->T;
+    return forward_impl(e, 1, p, ps, sc, B, N, nullptr, stream, tokens_in != 0, out);
+}
+
 int vtq_input_errors(vtq_handle e, int32_t* flags, void* stream) {
     if (!e || !flags) return fail("vtq_input_errors: null argument");
     hipStream_t s = (hipStream_t)stream;
@@ -1195,6 +1229,16 @@ int vtq_k_attention(const void* qkv, int64_t plane, void* out, int64_t o_plane, 
     const Num nm = num_from_code(num);
     if (!num_valid(nm) || nm.terms == 2) return fail("vtq_k_attention: operand format code %d", num);
     HIP_TRY(launch_attention(qkv, plane, out, o_plane, nseq, S, S_pad, H, nm, (hipStream_t)stream));
+    return 0;
+}
+
+int vtq_k_attention_probs(const void* qkv, int64_t plane, float* probs, int32_t nseq, int32_t S, int32_t S_pad, int32_t H, int32_t num,
+                          int32_t q_log2, void* stream) {
+    const Num nm = num_from_code(num);
+    if (!num_valid(nm) || nm.terms == 2 || nm.f16 > 1) return fail("vtq_k_attention_probs: operand format code %d", num);
+    if (!qkv || !probs || nseq < 1 || S < 1 || S_pad < S || H < 64 || H % 64) return fail("vtq_k_attention_probs: bad argument");
+    if (q_log2 && nm.terms != 3) return fail("vtq_k_attention_probs: q_log2 applies to the 3-term formats only");
+    HIP_TRY(launch_attention_probs(qkv, plane, probs, nseq, S, S_pad, H, nm, (hipStream_t)stream, q_log2 != 0));
     return 0;
 }
 

@@ -184,11 +184,21 @@ hipError_t launch_layernorm(const float* x, const float* w, const float* b, void
 hipError_t launch_attention(const void* qkv, int64_t plane, void* out, int64_t o_plane, int nseq, int S, int S_pad, int H,
                             Num num, hipStream_t s, float out8_scale = 0.0f, Fp8Obs obs = Fp8Obs{nullptr, nullptr}, bool q_log2 = false);
 
+// softmax(Q K^T / sqrt(64)) of every (sequence, head) as fp32 probs[nseq][H / 64][S][S] (attention_probs.hip), from the same QKV planes
+// launch_attention reads; num.terms 1 or 3, q_log2 as there.  Reads rows [seq * S_pad, seq * S_pad + S) of each sequence only.
+hipError_t launch_attention_probs(const void* qkv, int64_t plane, float* probs, int nseq, int S, int S_pad, int H, Num num, hipStream_t s,
+                                  bool q_log2 = false);
+
 // zero the rows of the residual stream that belong to no token: per-sequence pads, per-part tails, and everything up to rows_total
 hipError_t launch_zero_pad_rows(float* x, int nseq, int S, SeqMap sm, int H, int rows_total, hipStream_t s);
 
-// copy token rows (first T rows of each sequence) of x into trace[nseq][T][H]
+// copy token rows (first T rows of each sequence; T = S: every row) of x into trace[nseq][T][H]
 hipError_t launch_copy_tokens(const float* x, float* dst, int nseq, SeqMap sm, int T, int H, hipStream_t s);
+
+// out[seq][j] = encoder_norm(x[row(seq) + j]) for j < rows, fp32 rows packed [nseq][rows][H] (forward_vit's output); bit 1 of *err
+// (when err != NULL) is raised for a non-finite output value
+hipError_t launch_seq_rows_ln(const float* x, const float* ln_w, const float* ln_b, float* out, int nseq, SeqMap sm, int rows, int H,
+                              hipStream_t s, int* err = nullptr);
 
 // d[j*B + b] = gamma * (LN(x[row(b)]) - LN(x[row((j+1)*B + b)])), j < ndist  (final encoder_norm on the CLS rows only; vtamiq.py:104-111)
 hipError_t launch_final_diff(const float* x, const float* ln_w, const float* ln_b, const float* gamma, float* d, int B, int ndist,

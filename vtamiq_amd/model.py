@@ -110,20 +110,22 @@ class _EncoderLayer(_Params):               # EncoderLayer (transformer.py:246-2
 
 
 class _Encoder(_Params):                    # Encoder (transformer.py:328-361)
-    def __init__(self, spec: ModelSpec):
+    def __init__(self, spec: ModelSpec, return_layers=False, return_attention=False):
         super().__init__()
+        self.return_layers = return_layers          # read by VTAMIQ.forward_vit at every call (transformer.py:340-341, 369-372)
+        self.return_attention = return_attention
         self.encoder_norm = nn.LayerNorm(spec.hidden_size, eps=1e-6)
         self.layers = nn.ModuleList(_EncoderLayer(spec) for _ in range(spec.num_layers))
 
 
 class _Transformer(_Params):                # VisionTransformer (transformer.py:565-626)
-    def __init__(self, spec: ModelSpec):
+    def __init__(self, spec: ModelSpec, return_layers=False, return_attention=False):
         super().__init__()
         self.hidden_size = spec.hidden_size
         self.use_layer_scale = spec.use_layer_scale
         self.use_adapters = spec.num_adapters > 0
         self.embeddings = _Embeddings(spec)
-        self.encoder = _Encoder(spec)
+        self.encoder = _Encoder(spec, return_layers, return_attention)
         for m in self.modules():            # _init_weights (transformer.py:670-678)
             if isinstance(m, nn.Linear):
                 nn.init.trunc_normal_(m.weight, std=0.02)
@@ -167,7 +169,7 @@ class VTAMIQ(nn.Module):
                               num_rcabs=num_rcabs, ca_reduction=ca_reduction)
         spec = self.spec
         H = spec.hidden_size
-        self.transformer = _Transformer(spec)
+        self.transformer = _Transformer(spec, vit_config.get("return_layers", False), vit_config.get("return_attention", False))
         self.token_num = 0                                                   # vtamiq.py:57
         self.diff_scale = _Gamma(H) if diff_scale else nn.Sequential()       # vtamiq.py:61
         if calibrate:                                                        # vtamiq.py:63-69
@@ -607,6 +609,70 @@ class VTAMIQ(nn.Module):
             self._launch_checked(device, lambda lib: self._check((lib.vtq_forward_pairwise_tokens if tokens_in else lib.vtq_forward_pairwise)(
                 self._engine, arr(pt), arr(ps), arr(sc) if use_scales else None, B, N, q.data_ptr(), stream)))
         return q[:B], q[B:]
+
+    def forward_vit(self, patches, patches_pos, patches_scale, tokens_only=True, adapter_num=None):
+        """VisionTransformerBackbone.forward_vit (backbone.py:54-60, transformer.py:628-641, 363-378) on the HIP engine: B single images
+        (5-D patches or pre-embedded (B, N, H) rows, as one image of forward()) -> (x, attn_weights, hidden_states):
+          x              encoder_norm output, (B, T, H) when tokens_only else (B, S, H) with every token row; T = 1 + num_extra_tokens, S = N + T
+          hidden_states  transformer.encoder.return_layers: L tensors, the residual stream after each layer (before encoder_norm; the
+                         embedding output is not one of them), sliced to [:, :T] when tokens_only; else []
+          attn_weights   transformer.encoder.return_attention: L (B, num_heads, S, S) softmax probabilities; else []
+        All fp32 on the input device.  The flags are read at every call, so setting them after construction takes effect."""
+        if self.training:
+            raise NotImplementedError(
+                "the MI355X engine implements the eval/no-grad forward only (Dropout/DropPath of vtamiq.py:72-75 and "
+                "channel_attention.py:26-29 are train-time stochastic; backward is out of scope): call model.eval()")
+        if self._FP8_EXPERIMENT:
+            raise NotImplementedError("forward_vit is not available for the fp8 experiment's model (it scores pairs only)")
+        if adapter_num is not None and adapter_num >= 1 and self.spec.num_adapters > 0:
+            # backbone.py:55-57: None / negative selects pair 0 when the model has adapters; a model without adapters ignores the number
+            # (transformer.py:277-278), as the engine does
+            raise NotImplementedError(f"adapter_num={adapter_num}: the engine applies adapter pair 0 only (adapter_num None, negative or 0)")
+        device = patches.device
+        if device.type != "cuda":
+            raise RuntimeError("VTAMIQ (vtamiq_amd) runs on an MI355X only: move the model and inputs to 'cuda'. "
+                               "There is no CPU fallback on the product path.")
+        if torch.is_grad_enabled() and not self._warned_grad and any(p.requires_grad for p in self.parameters()):
+            warnings.warn("vtamiq_amd.VTAMIQ.forward returns scores without an autograd graph (inference engine)")
+            self._warned_grad = True
+        spec = self.spec
+        tokens_in = patches.dim() != 5           # Embeddings.forward (transformer.py:527-535), as in forward()
+        if tokens_in:
+            if patches.dim() != 3 or patches.shape[2] != spec.hidden_size:
+                raise ValueError(f"pre-embedded input must be a (B,N,{spec.hidden_size}) tensor, got {tuple(patches.shape)}")
+            B, N = patches.shape[:2]
+        else:
+            if not spec.use_patch_embedding:
+                raise AttributeError("'Embeddings' object has no attribute 'patch_embeddings' (use_patch_embedding=False: pass pre-embedded (B,N,H) rows)")
+            B, N, Cc, P, P2 = patches.shape
+            if (Cc, P, P2) != (3, spec.patch_size, spec.patch_size):
+                raise ValueError(f"patch shape {(Cc, P, P2)} != (3,{spec.patch_size},{spec.patch_size})")
+        if not spec.use_pos_embedding:           # as in forward(): `pos` is not looked at
+            patches_pos = torch.zeros(B, N, 2, device=device, dtype=torch.float32)
+        if tuple(patches_pos.shape) != (B, N, 2):
+            raise ValueError("pos must be a (B,N,2) tensor")
+        use_scales = spec.use_scale_embedding
+        if use_scales:
+            if patches_scale is None:
+                raise ValueError("Model uses scale embedding but scales is passed as None.")   # transformer.py:547-548
+            if patches_scale.numel() != B * N:
+                raise ValueError("scales must be a (B,N) tensor")
+        enc = self.transformer.encoder
+        want_states, want_probs = bool(enc.return_layers), bool(enc.return_attention)
+        L, T, H, nh = spec.num_layers, spec.num_tokens, spec.hidden_size, spec.num_heads
+        S = N + T
+        R = T if tokens_only else S
+        with torch.no_grad(), torch.cuda.device(device):
+            pt, pp = self._prep(patches, device), self._prep(patches_pos, device)
+            ps = self._prep(patches_scale, device) if use_scales else None
+            x = torch.empty(B, R, H, device=device, dtype=torch.float32)
+            states = torch.empty(L, B, R, H, device=device, dtype=torch.float32) if want_states else None
+            probs = torch.empty(L, B, nh, S, S, device=device, dtype=torch.float32) if want_probs else None
+            stream = torch.cuda.current_stream(device).cuda_stream
+            self._launch_checked(device, lambda lib: self._check(lib.vtq_forward_vit(
+                self._engine, pt.data_ptr(), int(tokens_in), pp.data_ptr(), ps.data_ptr() if use_scales else None, B, N, int(not tokens_only),
+                x.data_ptr(), states.data_ptr() if want_states else None, probs.data_ptr() if want_probs else None, stream)))
+        return x, (list(probs.unbind(0)) if want_probs else []), (list(states.unbind(0)) if want_states else [])
 
     # ---- measurement helpers (bench.py) ---------------------------------------------------------------------
     def profile_enable(self, classes):
