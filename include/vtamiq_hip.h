@@ -176,11 +176,8 @@ int  vtq_debug_cu_partition(int32_t gemm_cus_per_xcd, int32_t attention_cus);
 int  vtq_debug_cu_map(uint32_t* out, int32_t nblocks, int32_t spin_us, void* stream);
 int  vtq_debug_stop_after(vtq_handle h, int32_t stage);
 int  vtq_debug_buffers(vtq_handle h, void** x, void** lnbuf, void** big, int64_t* rows);
-/* Clock diagnostic of the GEMM kernel (MI355X_MICROARCH.md 'DVFS give-back' item 6).  Only a library built with -DVTQ_GEMM_DIAG
- * (tools/build_abl.sh) executes stamps; the shipped build returns 0 and does nothing.  buf = 256 x 64 uint64 of device memory that
- * nothing else reads: per workgroup {sum over its K loops of s_memtime, of s_memrealtime; the same two over the whole kernel;
- * tiles; XCC id; then per wave the cycles spent in the epilogue conversion, copy-out and waits}; shadow = dummy VALU instructions (x8) issued in every LDS-read phase of the main loop (what vector work beside
- * the partner wave's MFMAs costs).  Returns 1 in a diagnostic build. */
+/* Retired: the GEMM clock-stamp diagnostic build no longer exists.  Ignores its arguments, does nothing and returns 0; the entry point
+ * stays until the next ABI change. */
 int  vtq_debug_gemm_diag(void* buf, int32_t shadow);
 /* Which of the two fused-attention kernels vtq_k_attention and the engine launch (process-wide; tests and measurement):
  * 0 = the 4-wave kernel, 1 = the 8-wave software-pipelined kernel, 2 = split (the pipelined kernel on the full 256-row query blocks, the

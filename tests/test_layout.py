@@ -374,9 +374,8 @@ MEASUREMENT_KNOBS = ["VTQ_GEMM_FLAGS", "VTQ_GEMM_CUS", "VTQ_GEMM_CG", "VTQ_GEMM_
 
 
 def test_product_library_reads_no_measurement_environment():
-    """the shipped library must not be steerable (or corruptible) through the environment.  Every measurement
-    knob is compiled in only with -DVTQ_MEASURE (tools/build_abl.sh); the product objects and the linked library contain neither the
-    variable names nor an undefined reference to getenv."""
+    """the shipped library must not be steerable (or corruptible) through the environment.  The product objects
+    and the linked library contain neither the old measurement knobs' variable names nor an undefined reference to getenv."""
     import subprocess
     from vtamiq_amd import _lib, build
     build.build(verbose=False)
@@ -388,13 +387,24 @@ def test_product_library_reads_no_measurement_environment():
             assert knob.encode() not in data, (os.path.basename(path), knob)
     nm = subprocess.run(["nm", "-D", "--undefined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
     assert not re.search(r"\bgetenv\b", nm), "libvtamiq_hip.so imports getenv"
-    # and in the sources every getenv of csrc/ goes through the VTQ_MEASURE_ENV gate
+    # and no source of csrc/ calls getenv at all
     csrc = os.path.join(ROOT, "vtamiq_amd", "csrc")
     for f in os.listdir(csrc):
         if f.endswith((".hip", ".h")):
             for line in open(os.path.join(csrc, f)):
-                if "getenv(" in line:
-                    assert "#define VTQ_MEASURE_ENV(name) getenv(name)" in line, (f, line.strip())
+                assert not re.search(r"\bgetenv\b", line), (f, line.strip())
+
+
+def test_sources_have_no_build_switch_but_fp8():
+    """The kernels carry no measurement build switch: the only VTQ_ macro a preprocessor conditional of csrc/ may name is
+    VTQ_WITH_FP8 (the fp8 build of vtamiq_amd.build)."""
+    csrc = os.path.join(ROOT, "vtamiq_amd", "csrc")
+    for f in os.listdir(csrc):
+        if f.endswith((".hip", ".h")):
+            for line in open(os.path.join(csrc, f)):
+                if re.match(r"\s*#\s*(if|ifdef|ifndef|elif)\b", line):
+                    names = set(re.findall(r"\bVTQ_\w+", line.split("//")[0]))
+                    assert names <= {"VTQ_WITH_FP8"}, (f, line.strip())
 
 
 def test_weight_signature_sees_replacement_and_new_storage():

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """The two attention kernels (4-wave, software-pipelined) side by side (GPU box): outputs compared bit for bit, error against an fp64
-reference, time per launch (interleaved short bursts; tools/attn_probe.py times sustained launches)."""
+reference, time per launch (interleaved short bursts)."""
 import argparse, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

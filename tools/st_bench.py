@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Tile-shape exploration of the GEMM: every tile variant of csrc/gemm_st.hip against the persistent 256x256
 kernel on the encoder's four GEMM shapes at the row counts of B = 1 .. 32 pairs (N = 500 patches): bitwise comparison of the
-outputs and median time.  Variants 3+ exist in -DVTQ_GEMM_ST_EXPLORE builds only."""
+outputs and median time.  Variants: 0 the 256x256 kernel, 1 - 3 the small-tile shapes (kernels.h GEMM_TILE_256 / GEMM_ST_*)."""
 import argparse, json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -11,7 +11,7 @@ from tests.gpu_util import elt_dtype, num_code, to_planes, stream
 ap = argparse.ArgumentParser()
 ap.add_argument("--batches", type=int, nargs="+", default=[1, 2, 4, 8, 16, 32])
 ap.add_argument("--seq", type=int, default=501)
-ap.add_argument("--variants", type=int, nargs="+", default=[0, 1, 2])
+ap.add_argument("--variants", type=int, nargs="+", default=[0, 1, 2], choices=[0, 1, 2, 3])
 ap.add_argument("--fmt", default="fp16x3")
 ap.add_argument("--rounds", type=int, default=7)
 ap.add_argument("--only", nargs="+", default=None)

@@ -132,7 +132,7 @@ def load(path: str | None = None) -> C.CDLL:
         lib = C.CDLL(path)
     except OSError as e:
         raise RuntimeError(f"failed to load {path}: {e}") from e
-    # VTQ_LIB_PATH selects WHICH build is loaded (tools/build_abl.sh variants of this tree); it does not relax any check.  An A/B
+    # VTQ_LIB_PATH selects WHICH build is loaded (e.g. a build of another tree, for an A/B); it does not relax any check.  An A/B
     # build of an OLDER tree (different ABI: argument layouts may differ) loads only with VTQ_ALLOW_ABI_MISMATCH=1, with a warning.
     relaxed = os.environ.get("VTQ_ALLOW_ABI_MISMATCH") == "1"
     for name, (res, args) in SIGNATURES.items():

@@ -17,7 +17,6 @@
 //   * T = bf16 | f16 operand planes.  P (in (0, 1]) is split with a TRUNCATED hi part, so that lo = v - hi is exact in fp32:
 //     f16: v_cvt_pkrtz for a pair (subnormal results are kept: tools/micro/split_probe.hip); bf16: mask + subtract.
 #include <atomic>
-#include <cstdlib>
 #include <mutex>
 
 #include "dev_common.h"
@@ -25,15 +24,6 @@
 
 namespace vtq {
 namespace {
-
-// Diagnostic builds (-DVTQ_ATTN_DIAG, tools/build_abl.sh) accumulate per-wave s_memtime spans of the phases of a tile into the
-// buffer of gemm_set_diag (16 words per wave; tools/attn_probe.py); the shipped library executes no stamp.
-#ifdef VTQ_ATTN_DIAG
-#define VTQ_AT_STAMP(var) { __builtin_amdgcn_sched_barrier(0); asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(var) :: "memory"); __builtin_amdgcn_sched_barrier(0); }
-#define VTQ_AT_SPAN(acc) { unsigned long long dg_t1; VTQ_AT_STAMP(dg_t1); acc += dg_t1 - dg_t; dg_t = dg_t1; }
-#else
-#define VTQ_AT_SPAN(acc)
-#endif
 
 typedef __attribute__((ext_vector_type(4))) short s16x4;
 typedef __attribute__((ext_vector_type(8))) short s16x8;
@@ -107,7 +97,7 @@ __device__ __forceinline__ void prescale_q(typename Vec<T>::x8 (&qf)[2][4], floa
 template <typename T, int NSPLIT>
 __global__ __launch_bounds__(256) void attention_kernel(const T* __restrict__ qkv, int64_t plane, T* __restrict__ out,
                                                         int64_t o_plane, int S, int S_pad, int H, float out8_scale, Fp8Obs obs,
-                                                        unsigned long long* diag, int q_log2, int q0, int Sq) {
+                                                        int q_log2, int q0, int Sq) {
     // q0, Sq: this launch covers the query rows [q0, Sq) of every sequence (0, S_pad: all of them; launch_attention's split form gives
     // the rows behind the last full 256-row block to this kernel)
     typedef typename Vec<T>::x8 tx8;
@@ -122,10 +112,6 @@ __global__ __launch_bounds__(256) void attention_kernel(const T* __restrict__ qk
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int c = lane & 31, hh = lane >> 5;
-#ifdef VTQ_ATTN_DIAG
-    unsigned long long dg_k0, dg_r0, dg_t, dg_qk = 0, dg_sm = 0, dg_pv = 0, dg_bar = 0, dg_stage = 0;
-    asm volatile("s_memtime %0\n\ts_memrealtime %1\n\ts_waitcnt lgkmcnt(0)" : "=s"(dg_k0), "=s"(dg_r0) :: "memory");
-#endif
     // 1-D grid, XCD-aware: the q-blocks of one (sequence, head) re-read the same K/V, so they must share an L2.
     // Blocks are dealt round-robin over the 8 XCDs; remap so each XCD owns a contiguous range of work ids (bijective).
     const int nqb = (Sq - q0 + 127) / 128, nh = H / 64;
@@ -212,22 +198,12 @@ __global__ __launch_bounds__(256) void attention_kernel(const T* __restrict__ qk
     };
     stage(0, 0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#ifndef VTQ_ATTN_NO_VMASK                          // measurement builds only: the cost of the masked-key V rows' zeroing (A/B)
     if (nt == 1) zero_masked_v(0);
-#endif
     __syncthreads();
     int cur = 0;
-#ifdef VTQ_ATTN_DIAG
-    unsigned long long dg_loop0, dg_loop1;
-    VTQ_AT_STAMP(dg_loop0);
-#endif
     for (int t = 0; t < nt; ++t) {
         const int nxt = cur ^ 1;
-#ifdef VTQ_ATTN_DIAG
-        VTQ_AT_STAMP(dg_t);
-#endif
         if (t + 1 < nt) stage(t + 1, nxt);
-        VTQ_AT_SPAN(dg_stage);
         const char* sk = smem + cur * STAGE;
         const char* sv = sk + NPL * TB;
 
@@ -250,7 +226,6 @@ __global__ __launch_bounds__(256) void attention_kernel(const T* __restrict__ qk
             }
         }
 
-        VTQ_AT_SPAN(dg_qk);
         // ---- online softmax (base-2 domain; scale folded into one FMA per score) -----------------------------------
         if ((t + 1) * KT > S) {                 // wave-uniform: only the last tile(s) hold padded keys
             int hq = 4 * hh;
@@ -308,7 +283,6 @@ __global__ __launch_bounds__(256) void attention_kernel(const T* __restrict__ qk
         }
         m_run = m_new;
         l_run += rs;
-        VTQ_AT_SPAN(dg_sm);
 
         // ---- O^T[d][q] += V^T[d][key] P^T[key][q] -------------------------------------------------------------
 #pragma unroll
@@ -344,20 +318,13 @@ __global__ __launch_bounds__(256) void attention_kernel(const T* __restrict__ qk
                 }
             }
 
-        VTQ_AT_SPAN(dg_pv);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // tile t+1 has landed
-#ifndef VTQ_ATTN_NO_VMASK
         if (t + 2 == nt) zero_masked_v(nxt);                // ... and it is the last one: its masked keys' V rows become zeros
-#endif
         __syncthreads();
-        VTQ_AT_SPAN(dg_bar);
         cur = nxt;
     }
 
-#ifdef VTQ_ATTN_DIAG
-    VTQ_AT_STAMP(dg_loop1);
-#endif
     // ---- normalise and write merged heads: out[row][head*64 + d] -------------------------------------------------
     const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
     const float inv = 1.0f / l_tot;
@@ -420,17 +387,6 @@ __global__ __launch_bounds__(256) void attention_kernel(const T* __restrict__ qk
             }
     }
     if (out8_scale > 0.f) fp8_report(obs, amax8, out8_scale);
-#ifdef VTQ_ATTN_DIAG
-    if (diag) {
-        unsigned long long dg_k1, dg_r1;
-        asm volatile("s_memtime %0\n\ts_memrealtime %1\n\ts_waitcnt lgkmcnt(0)" : "=s"(dg_k1), "=s"(dg_r1) :: "memory");
-        if (lane == 0) {          // one 16-word slot per wave, plain stores (same-address atomics of 12 k waves would take a millisecond)
-            unsigned long long* dq = diag + ((size_t)blockIdx.x * 4 + wave) * 16;
-            dq[0] = dg_k1 - dg_k0; dq[1] = dg_r1 - dg_r0; dq[2] = dg_qk; dq[3] = dg_sm; dq[4] = dg_pv; dq[5] = dg_bar; dq[6] = 1; dq[7] = nt; dq[8] = dg_stage;
-            dq[9] = dg_loop0 - dg_k0; dq[10] = dg_k1 - dg_loop1;
-        }
-    }
-#endif
 }
 
 
@@ -456,13 +412,11 @@ __device__ __forceinline__ void static_for(F&& f) {
 #define PP_DS_B128(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:%c2" : "=v"(dst) : "v"(addr), "i"(off))
 #define PP_DS_TR(dst, addr, off) asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%c2" : "=v"(dst) : "v"(addr), "i"(off))
 
+constexpr int kDist = 2;              // LDS fragment groups read ahead of the MFMAs that consume them (2 or 3; 3 measured: see the profile)
 template <typename T, int NSPLIT>
-#ifndef VTQ_SW_DIST
-#define VTQ_SW_DIST 2                 // LDS fragment groups read ahead of the MFMAs that consume them (2 or 3; 3 measured: see the profile)
-#endif
 struct PPFrags {                      // DIST + 1 rolling fragment buffers: group G (QK^T 0..7, PV 8..15 of a tile) uses slot G % (DIST + 1)
-    u32x4 ka[VTQ_SW_DIST + 1], kl[VTQ_SW_DIST + 1];               // QK^T groups: K fragment hi / lo (ds_read_b128)
-    u32x2 va0[VTQ_SW_DIST + 1], va1[VTQ_SW_DIST + 1], vl0[VTQ_SW_DIST + 1], vl1[VTQ_SW_DIST + 1];   // PV groups: V^T fragment halves (ds_read_b64_tr_b16)
+    u32x4 ka[kDist + 1], kl[kDist + 1];               // QK^T groups: K fragment hi / lo (ds_read_b128)
+    u32x2 va0[kDist + 1], va1[kDist + 1], vl0[kDist + 1], vl1[kDist + 1];   // PV groups: V^T fragment halves (ds_read_b64_tr_b16)
 };
 
 // =====================================================================================================================
@@ -482,43 +436,7 @@ struct PPFrags {                      // DIST + 1 rolling fragment buffers: grou
 // middle of the NEXT iteration (phase 1 does not touch O), so that its stores are 16 B per lane on whole 128-byte row segments, older
 // than that iteration's LDS-DMA and covered by its phase 2.  Waves whose rows lie behind the sequence (ragged last block) only load.
 // Same arithmetic in the same order per query row as attention_kernel: outputs are bit-identical (tools/attn_ab.py, tests).
-// Measurements, the skeleton ablations behind the switches below and the ping-pong variant that lost: profiles/r03_attention_anatomy.txt.
-#ifndef VTQ_SW_NOFILL
-#define VTQ_SW_NOFILL 0
-#endif
-#ifndef VTQ_SW_QPF
-#define VTQ_SW_QPF 1                  // the next block's Q rows are pulled into L2 two iterations before they are loaded (0: measurement builds)
-#endif
-#ifndef VTQ_SW_EARLY_WRITE
-#define VTQ_SW_EARLY_WRITE 1          // a finished block's output is written at the top of the next iteration (0: in its middle, the round-3 place)
-#endif
-#ifndef VTQ_SW_PRIO
-#define VTQ_SW_PRIO 0                 // measurement builds: issue priority alternating between the two waves of a SIMD (1: per phase, 2: per fragment group, 3: static for waves 4-7)
-#endif
-#ifndef VTQ_SW_NOSTORE
-#define VTQ_SW_NOSTORE 0
-#endif
-#ifndef VTQ_SW_PAIRED
-#define VTQ_SW_PAIRED 1
-#endif
-#ifndef VTQ_SW_NOQ
-#define VTQ_SW_NOQ 0
-#endif
-#ifndef VTQ_SW_NODMA
-#define VTQ_SW_NODMA 0
-#endif
-#ifndef VTQ_SW_NOMFMA
-#define VTQ_SW_NOMFMA 0
-#endif
-template <typename T>
-__device__ __forceinline__ f32x16 SW_MFMA(typename Vec<T>::x8 a, typename Vec<T>::x8 b, f32x16 c) {
-#if VTQ_SW_NOMFMA
-    asm volatile("" :: "v"(a), "v"(b));
-    return c;
-#else
-    return mfma32<T>(a, b, c);
-#endif
-}
+// Measurements, the skeleton ablations and the ping-pong variant that lost: profiles/r03_attention_anatomy.txt.
 #define SW_MFMA_VALU(n)                                         \
     __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);          \
     __builtin_amdgcn_sched_group_barrier(0x002, n, 0)
@@ -552,19 +470,15 @@ __device__ __forceinline__ void split_p4(const float (&p)[4], uint32_t (&hw)[2],
 }
 
 // LDS reads of fragment group G of a tile (QK^T groups 0..7: K hi [+ lo] by ds_read_b128; PV groups 8..15: V^T hi [+ lo] by two
-// ds_read_b64_tr_b16 each), and the reads still in flight when group G is consumed: those of the next VTQ_SW_DIST groups below `end`
-#ifndef VTQ_SW_HALFREADS
-#define VTQ_SW_HALFREADS 0            // measurement builds: every second fragment group is not read (its registers keep the previous group's): what
-#endif                                //   a kernel with HALF the K / V fragment reads per MFMA -- 64 query rows per wave -- could save at most (results wrong)
+// ds_read_b64_tr_b16 each), and the reads still in flight when group G is consumed: those of the next kDist groups below `end`
 template <int NSPLIT>
 constexpr int sw_reads(int G) {
-    if (VTQ_SW_HALFREADS && (G & 1)) return 0;
     return G < 8 ? (NSPLIT == 1 ? 1 : 2) : (G < 16 ? (NSPLIT == 1 ? 2 : 4) : 0);
 }
 template <int NSPLIT>
 constexpr int sw_ahead(int G, int end) {
     int n = 0;
-    for (int j = 1; j <= VTQ_SW_DIST; ++j)
+    for (int j = 1; j <= kDist; ++j)
         if (G + j < end) n += sw_reads<NSPLIT>(G + j);
     return n;
 }
@@ -572,7 +486,7 @@ constexpr int sw_ahead(int G, int end) {
 template <typename T, int NSPLIT>
 __global__ __launch_bounds__(512) void attention_sw_kernel(const T* __restrict__ qkv, int64_t plane, T* __restrict__ out, int64_t o_plane,
                                                            int S, int S_pad, int H, int nblk, int per, float out8_scale, Fp8Obs obs,
-                                                           unsigned long long* diag, int q_log2, int Sq) {
+                                                           int q_log2, int Sq) {
     // Sq: this launch covers the query rows [0, Sq) of every sequence -- S_pad (all of them), or the full 256-row blocks only when
     // launch_attention hands the short rest to the 4-wave kernel; S_pad stays the pitch of a sequence
     typedef typename Vec<T>::x8 tx8;
@@ -607,7 +521,7 @@ __global__ __launch_bounds__(512) void attention_sw_kernel(const T* __restrict__
         b0 = i0 * nqb + sl;
         bstep = nx;
         b1 = i1 * nqb;
-    } else if (VTQ_SW_PAIRED && nqb == 2 && (gridDim.x & 15) == 0 && (int)gridDim.x * per == nblk) {
+    } else if (nqb == 2 && (gridDim.x & 15) == 0 && (int)gridDim.x * per == nblk) {
         const int x = blockIdx.x & 7, sl = blockIdx.x >> 3;
         const int g = x * ((int)gridDim.x >> 4) + (sl >> 1);
         b0 = 2 * g * per + (sl & 1);
@@ -619,20 +533,8 @@ __global__ __launch_bounds__(512) void attention_sw_kernel(const T* __restrict__
         bstep = 1;
     }
     if (b0 >= b1) return;
-#if defined(VTQ_SW_SEAM_STAGGER) && VTQ_SW_SEAM_STAGGER > 0
-    // Measurement builds (tools/runs/r05g_attn_seams.sh): every second workgroup of an XCD starts VTQ_SW_SEAM_STAGGER microseconds late, so that the
-    // block seams of the chip (Q loads, output stores) do not coincide; s_sleep 32 = ~2048 cycles = ~1 us.  Same results.
-    if ((blockIdx.x >> 3) & 1)
-        for (int i = 0; i < VTQ_SW_SEAM_STAGGER; ++i) __builtin_amdgcn_s_sleep(32);
-#endif
     const int NT = ((b1 - b0 + bstep - 1) / bstep) * nt;
     const float sc = 0.125f * 1.4426950408889634f;
-#ifdef VTQ_ATTN_DIAG
-    unsigned long long dg_k0, dg_r0, dg_t, dg_p1 = 0, dg_p2 = 0, dg_bar = 0, dg_pro = 0, dg_rest = 0;
-    unsigned long long dg_it0 = 0, dg_kind[3] = {0, 0, 0}, dg_nkind[3] = {0, 0, 0}, dg_wb = 0, dg_tail0 = 0;   // whole iterations by kind: plain / writes a block / loads Q
-    asm volatile("s_memtime %0\n\ts_memrealtime %1\n\ts_waitcnt lgkmcnt(0)" : "=s"(dg_k0), "=s"(dg_r0) :: "memory");
-    dg_t = dg_k0;
-#endif
 
     auto block_base = [&](int b, int& qb) __attribute__((always_inline)) -> int64_t {
         qb = b % nqb;
@@ -687,7 +589,6 @@ __global__ __launch_bounds__(512) void attention_sw_kernel(const T* __restrict__
         const T* base = qkv + ibase + (int64_t)it * KT * ld;
 #pragma unroll
         for (int pl = 0; pl < NPL; ++pl) {
-            if (VTQ_SW_NODMA) break;
             glds16(base + pl * plane + k_off, sb + pl * TB);
             glds16(base + pl * plane + v_off, sb + (NPL + pl) * TB);
         }
@@ -746,7 +647,7 @@ __global__ __launch_bounds__(512) void attention_sw_kernel(const T* __restrict__
         const int q_row = qb * 256 + wave * 32 + c;
         const int64_t obase = block_out(b);
         if (out8_scale > 0.f) {                                    // fp8 mode: bytes, direct stores (one 64-byte piece per row)
-            if (q_row < Sq && !VTQ_SW_NOSTORE) {
+            if (q_row < Sq) {
 #pragma unroll
                 for (int d = 0; d < 2; ++d)
 #pragma unroll
@@ -795,7 +696,7 @@ __global__ __launch_bounds__(512) void attention_sw_kernel(const T* __restrict__
                     const int row = r_row + 8 * k;
                     const uint4 w = *(const uint4*)(o_stage + row * 128 + ((r_chunk ^ (row & 7)) << 4));
                     const int qr = qb * 256 + wave * 32 + row;
-                    if (qr < Sq && !VTQ_SW_NOSTORE) *(uint4*)(out + pl * o_plane + obase + (int64_t)qr * H + 8 * r_chunk) = w;
+                    if (qr < Sq) *(uint4*)(out + pl * o_plane + obase + (int64_t)qr * H + 8 * r_chunk) = w;
                 }
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // the reads are done before the next plane overwrites the image
             }
@@ -869,7 +770,7 @@ __global__ __launch_bounds__(512) void attention_sw_kernel(const T* __restrict__
     };
 
     PPFrags<T, NSPLIT> fr;
-    constexpr int NS = VTQ_SW_DIST + 1, DIST = VTQ_SW_DIST;
+    constexpr int NS = kDist + 1, DIST = kDist;
     auto issue_k = [&](auto gc, const uint32_t (&kaddr)[4]) __attribute__((always_inline)) {       // QK^T group g = kb * 4 + tt
         constexpr int g = decltype(gc)::value, sl = g % NS, kb = g >> 2, tt = g & 3, off = kb * 4096;
         PP_DS_B128(fr.ka[sl], kaddr[tt], off);
@@ -887,7 +788,6 @@ __global__ __launch_bounds__(512) void attention_sw_kernel(const T* __restrict__
 
     auto issue_g = [&](auto Gc, const uint32_t (&kaddr)[4], const uint32_t (&vaddr)[2]) __attribute__((always_inline)) {   // group G of a tile
         constexpr int G = decltype(Gc)::value;
-        if constexpr (VTQ_SW_HALFREADS && (G & 1)) return;
         if constexpr (G < 8) issue_k(std::integral_constant<int, G>{}, kaddr);
         else if constexpr (G < 16) issue_v(std::integral_constant<int, G - 8>{}, vaddr);
     };
@@ -910,10 +810,8 @@ __global__ __launch_bounds__(512) void attention_sw_kernel(const T* __restrict__
     // ---- pipeline prologue: S(0) = QK^T of tile 0 and its softmax, no overlap ---------------------------------------------
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     int ib2 = 2 % nt;                                        // in-block index of tile tau + 2 (tau = 0 here), kept by increments
-#ifndef VTQ_ATTN_NO_VMASK
     for (int g = 0; g < 3 && g < NT; ++g)
         if (g % nt == nt - 1) zero_masked_v(g);             // tiles 0 .. 2 were staged above and have landed
-#endif
     pp_barrier();
     {
         uint32_t kaddr[4];
@@ -929,11 +827,11 @@ __global__ __launch_bounds__(512) void attention_sw_kernel(const T* __restrict__
             else asm volatile("s_waitcnt lgkmcnt(%c1)" : "+v"(fr.ka[sl]) : "i"(ahead));
             const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
             const tx8 kf = __builtin_bit_cast(tx8, fr.ka[sl]);
-            sB[kb] = SW_MFMA<T>(kf, qf[0][tt], tt == 0 ? zero16 : sB[kb]);
+            sB[kb] = mfma32<T>(kf, qf[0][tt], tt == 0 ? zero16 : sB[kb]);
             if constexpr (NSPLIT == 3) {
                 const tx8 kl = __builtin_bit_cast(tx8, fr.kl[sl]);
-                sB[kb] = SW_MFMA<T>(kf, qf[1][tt], sB[kb]);
-                sB[kb] = SW_MFMA<T>(kl, qf[0][tt], sB[kb]);
+                sB[kb] = mfma32<T>(kf, qf[1][tt], sB[kb]);
+                sB[kb] = mfma32<T>(kl, qf[0][tt], sB[kb]);
             }
             __builtin_amdgcn_sched_barrier(0);
         });
@@ -951,7 +849,6 @@ __global__ __launch_bounds__(512) void attention_sw_kernel(const T* __restrict__
             if constexpr (NSPLIT == 3) { if (!q_log2) prescale_q<T>(qf, sc); }
         }
     }
-    VTQ_AT_SPAN(dg_pro);
 
     // Half a step of the P split: 4 probabilities of sA -> 2 hi words + 2 lo words, written IN PLACE over the floats they came from, so
     // that after both halves the 8 registers of a step hold [hi0 hi1 hi2 hi3 | lo0 lo1 lo2 lo3] = the two MFMA fragments of the step
@@ -991,16 +888,6 @@ __global__ __launch_bounds__(512) void attention_sw_kernel(const T* __restrict__
         const f4 w = {v[o], v[o + 1], v[o + 2], v[o + 3]};
         return __builtin_bit_cast(tx8, w);
     };
-    // Issue priority of this wave against its SIMD partner (waves w and w + 4 share a SIMD; the older one, w, wins arbitration by age): the stamps show
-    // waves 4 - 7 taking 2 462 + 3 312 cycles for the two phases of a tile against 1 674 + 2 837 for waves 0 - 3, which then wait 1 300 cycles longer at the
-    // tile's barrier (profiles/r05_attention_prio.txt).  hi(x): this wave is favoured in slot x (phase or fragment group).
-    auto prio = [&](int slot) __attribute__((always_inline)) {
-#if VTQ_SW_PRIO == 1 || VTQ_SW_PRIO == 2
-        if (((wave >> 2) ^ slot) & 1) __builtin_amdgcn_s_setprio(2); else __builtin_amdgcn_s_setprio(0);
-#elif VTQ_SW_PRIO == 3
-        if (wave >> 2) __builtin_amdgcn_s_setprio(2);
-#endif
-    };
     auto iteration = [&](auto more_c, int tau) __attribute__((always_inline)) {
         constexpr bool more = decltype(more_c)::value;         // is there a tile tau + 1 (its QK^T and softmax run in this iteration)
         const int tb_next = (ct + 1 == nt) ? 0 : ct + 1;       // its index in its block
@@ -1019,22 +906,11 @@ __global__ __launch_bounds__(512) void attention_sw_kernel(const T* __restrict__
         // Q of the block after the one tile tau + 1 belongs to, when tile tau + 1 is that block's last: loaded into spare registers at
         // the top of the iteration whose phase 1 still needs the current Q, installed behind the end-of-iteration wait.
         // ---------------- phase 1: QK^T(tau + 1) -> sB  ||  split of P(tau) = sA, rescale of O ------------------------------
-#if VTQ_SW_PRIO == 1 || VTQ_SW_PRIO == 3
-        prio(1);                                   // phase 1: waves 4 - 7 favoured (1); phase 2: waves 0 - 3 (below)
-#endif
         // Output of the block that ended with the previous iteration's PV.  Written HERE, at the top: phase 1 does not touch O, the stores are
         // older than this iteration's LDS-DMA and have both phases as cover before the counted wait at the end (all CUs reach their seams
         // together: 16 MB of stores in one burst, which one phase did not cover).
         const bool had_pending = wr_pending;       // the successor block starts from zero: nothing to rescale
-#ifdef VTQ_ATTN_DIAG
-        dg_it0 = dg_t;
-#endif
-#if VTQ_SW_EARLY_WRITE
         if (wr_pending) { write_block(l_fin, wr_b, wr_qb); wr_pending = false; }
-#endif
-#ifdef VTQ_ATTN_DIAG
-        if (had_pending) { VTQ_AT_SPAN(dg_wb); }
-#endif
         if (rescale && !had_pending) {
 #pragma unroll
             for (int d = 0; d < 2; ++d)
@@ -1047,9 +923,6 @@ __global__ __launch_bounds__(512) void attention_sw_kernel(const T* __restrict__
             static_for<0, DIST>([&](auto gc) __attribute__((always_inline)) { issue_g(gc, kaddr, vaddr); });
             static_for<0, 8>([&](auto gc) __attribute__((always_inline)) {
                 constexpr int g = decltype(gc)::value, sl = g % NS, kb = g >> 2, tt = g & 3;
-#if VTQ_SW_PRIO == 2
-                prio(g);
-#endif
                 issue_g(std::integral_constant<int, g + DIST>{}, kaddr, vaddr);
                 constexpr int ahead = ahead_of(g, 16);
                 if constexpr (NSPLIT == 3) asm volatile("s_waitcnt lgkmcnt(%c2)" : "+v"(fr.ka[sl]), "+v"(fr.kl[sl]) : "i"(ahead));
@@ -1057,13 +930,13 @@ __global__ __launch_bounds__(512) void attention_sw_kernel(const T* __restrict__
                 __builtin_amdgcn_sched_barrier(0);
                 const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
                 const tx8 kf = __builtin_bit_cast(tx8, fr.ka[sl]);
-                sB[kb] = SW_MFMA<T>(kf, qf[0][tt], tt == 0 ? zero16 : sB[kb]);
+                sB[kb] = mfma32<T>(kf, qf[0][tt], tt == 0 ? zero16 : sB[kb]);
                 if constexpr (NSPLIT == 3) {
                     const tx8 kl = __builtin_bit_cast(tx8, fr.kl[sl]);
-                    sB[kb] = SW_MFMA<T>(kf, qf[1][tt], sB[kb]);
-                    sB[kb] = SW_MFMA<T>(kl, qf[0][tt], sB[kb]);
+                    sB[kb] = mfma32<T>(kf, qf[1][tt], sB[kb]);
+                    sB[kb] = mfma32<T>(kl, qf[0][tt], sB[kb]);
                 }
-                if constexpr (!VTQ_SW_NOFILL) split_half(gc);
+                split_half(gc);
                 if constexpr (NSPLIT == 3) { SW_MFMA_VALU(4); SW_MFMA_VALU(4); SW_MFMA_VALU(4); }
                 else { SW_MFMA_VALU(2); }
                 __builtin_amdgcn_sched_barrier(0);
@@ -1073,24 +946,14 @@ __global__ __launch_bounds__(512) void attention_sw_kernel(const T* __restrict__
             static_for<0, 8>([&](auto gc) __attribute__((always_inline)) { split_half(gc); });
             static_for<8, 8 + DIST>([&](auto gc) __attribute__((always_inline)) { issue_g(gc, kaddr, vaddr); });
         }
-        VTQ_AT_SPAN(dg_p1);
-#if !VTQ_SW_EARLY_WRITE
-        if (wr_pending) { write_block(l_fin, wr_b, wr_qb); wr_pending = false; }
-#endif
         // at a seam the finished block's row sums are set aside and the statistics restart before the next tile's softmax
         const bool seam = (ct + 1 == nt);
         if (seam) { l_fin = l_run; m_run = -1e30f; l_run = 0.f; }
         if constexpr (more) mask_tail(tb_next);
         // ---------------- phase 2: PV(tau) into O  ||  softmax of sB (tile tau + 1) -------------------------------------------
-#if VTQ_SW_PRIO == 1
-        prio(0);
-#endif
         bool sent = false, q_loaded = false;
         auto pv_group = [&](auto gc) __attribute__((always_inline)) {
             constexpr int g = decltype(gc)::value, sl = (g + 8) % NS, step = g >> 1, d = g & 1;
-#if VTQ_SW_PRIO == 2
-            prio(g);
-#endif
             issue_g(std::integral_constant<int, g + 8 + DIST>{}, kaddr, vaddr);          // nothing beyond group 15
             constexpr int ahead = ahead_of(g + 8, 16);
             if constexpr (NSPLIT == 3)
@@ -1100,14 +963,14 @@ __global__ __launch_bounds__(512) void attention_sw_kernel(const T* __restrict__
             __builtin_amdgcn_sched_barrier(0);
             const tx8 vf = __builtin_bit_cast(tx8, u32x4{fr.va0[sl][0], fr.va0[sl][1], fr.va1[sl][0], fr.va1[sl][1]});
             const tx8 ph = p_frag(step, 0);
-            o_acc[d] = SW_MFMA<T>(vf, ph, o_acc[d]);
+            o_acc[d] = mfma32<T>(vf, ph, o_acc[d]);
             if constexpr (NSPLIT == 3) {
                 const tx8 vl = __builtin_bit_cast(tx8, u32x4{fr.vl0[sl][0], fr.vl0[sl][1], fr.vl1[sl][0], fr.vl1[sl][1]});
                 const tx8 pl = p_frag(step, 1);
-                o_acc[d] = SW_MFMA<T>(vf, pl, o_acc[d]);
-                o_acc[d] = SW_MFMA<T>(vl, ph, o_acc[d]);
+                o_acc[d] = mfma32<T>(vf, pl, o_acc[d]);
+                o_acc[d] = mfma32<T>(vl, ph, o_acc[d]);
             }
-            if constexpr (more && !VTQ_SW_NOFILL) {
+            if constexpr (more) {
                 if constexpr (g == 0) max_part(0);
                 else if constexpr (g == 1) max_part(1);
                 else if constexpr (g == 2) exp_part(0, 6);
@@ -1128,7 +991,7 @@ __global__ __launch_bounds__(512) void attention_sw_kernel(const T* __restrict__
         // (phase 1 above); loaded in place, hidden from hipcc's vmcnt bookkeeping, complete behind the counted wait at the end
         if constexpr (more) {
             const int bq = (tb_next == 0 ? cb + bstep : cb) + bstep;
-            if (tb_next == nt - 1 && bq < b1 && !VTQ_SW_NOQ) { load_q_async(bq, qf); q_loaded = true; }
+            if (tb_next == nt - 1 && bq < b1) { load_q_async(bq, qf); q_loaded = true; }
         }
         sent = issue_tile();                    // tile tau + 3: younger than the Q loads and stores, so vmcnt(NI) below covers them
         if (active1 || active2) phase2();
@@ -1137,7 +1000,6 @@ __global__ __launch_bounds__(512) void attention_sw_kernel(const T* __restrict__
         // serves in ~3.5 us -- longer than the phase that covers them; pulled into L2 ahead of time they return at L2 latency.  Issued
         // AFTER this iteration's LDS-DMA, behind phase 2 (younger: this iteration's counted wait leaves it in flight, the next one's covers it).
         bool q_pf_sent = false;
-#if VTQ_SW_QPF
         if constexpr (more) {
             const int bq = (tb_next == 0 ? cb + bstep : cb) + bstep;
             if (tb_next == nt - 3 && bq < b1) {
@@ -1150,9 +1012,7 @@ __global__ __launch_bounds__(512) void attention_sw_kernel(const T* __restrict__
                 q_pf_sent = true;
             }
         }
-#endif
         if constexpr (more) finish_softmax(); else rescale = false;
-        VTQ_AT_SPAN(dg_p2);
         if (seam) {
             wr_pending = true; wr_b = cb; wr_qb = cqb;
             ct = 0;
@@ -1162,43 +1022,21 @@ __global__ __launch_bounds__(512) void attention_sw_kernel(const T* __restrict__
         }
 #pragma unroll
         for (int d = 0; d < 2; ++d) sA[d] = sB[d];
-        VTQ_AT_SPAN(dg_rest);
         if (sent && q_pf_sent) asm volatile("s_waitcnt vmcnt(%c0)" :: "i"(NI + 1) : "memory");
         else if (sent) asm volatile("s_waitcnt vmcnt(%c0)" :: "i"(NI) : "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         asm volatile("" : "+v"(q_pf));                         // the prefetch's destination stays reserved (it may still be in flight)
         // everything older than tile tau + 3 has landed: tile tau + 2 (its V is read two iterations from now) gets its masked rows zeroed
-#ifndef VTQ_ATTN_NO_VMASK
         if (tau + 2 < NT && ib2 == nt - 1) zero_masked_v(tau + 2);
         ib2 = (ib2 + 1 == nt) ? 0 : ib2 + 1;                   // in-block index of tile tau + 3, for the next iteration
-#endif
         pin_q(qf);
         if constexpr (NSPLIT == 3) { if (q_loaded && !q_log2) prescale_q<T>(qf, sc); }
         pp_barrier();
-        VTQ_AT_SPAN(dg_bar);
-#ifdef VTQ_ATTN_DIAG
-        { const int kd = had_pending ? 1 : (q_loaded ? 2 : 0); dg_kind[kd] += dg_t - dg_it0; dg_nkind[kd] += 1; }
-#endif
     };
     for (int tau = 0; tau < NT - 1; ++tau) iteration(std::true_type{}, tau);
     iteration(std::false_type{}, NT - 1);
-#ifdef VTQ_ATTN_DIAG
-    dg_tail0 = dg_t;
-#endif
     write_block(l_fin, wr_b, wr_qb);             // the last block of the list
     if (out8_scale > 0.f) fp8_report(obs, amax8, out8_scale);
-#ifdef VTQ_ATTN_DIAG
-    if (diag) {
-        unsigned long long dg_k1, dg_r1;
-        asm volatile("s_memtime %0\n\ts_memrealtime %1\n\ts_waitcnt lgkmcnt(0)" : "=s"(dg_k1), "=s"(dg_r1) :: "memory");
-        if (lane == 0) {
-            unsigned long long* dq = diag + ((size_t)blockIdx.x * 8 + wave) * 16;
-            dq[0] = dg_k1 - dg_k0; dq[1] = dg_r1 - dg_r0; dq[2] = dg_p1; dq[3] = dg_p2; dq[4] = dg_rest; dq[5] = dg_bar; dq[6] = 1; dq[7] = NT; dq[8] = 0;
-            dq[9] = dg_pro;
-            dq[10] = dg_kind[0]; dq[11] = dg_kind[1]; dq[12] = dg_kind[2]; dq[13] = dg_nkind[0] | (dg_nkind[1] << 20) | (dg_nkind[2] << 40); dq[14] = dg_wb; dq[15] = dg_k1 - dg_tail0;
-        }
-    }
-#endif
 }
 
 }  // namespace
@@ -1206,12 +1044,7 @@ __global__ __launch_bounds__(512) void attention_sw_kernel(const T* __restrict__
 template <typename T, int NSPLIT>
 hipError_t launch_attention_t(const void* qkv, int64_t plane, void* out, int64_t o_plane, int nseq, int S, int S_pad, int H, hipStream_t s,
                               float out8_scale, Fp8Obs obs, bool q_log2, int q0 = 0) {
-#ifdef VTQ_ATTN_DIAG
-    static const int lds_pad = VTQ_MEASURE_ENV("VTQ_ATTN_LDS_PAD") ? atoi(VTQ_MEASURE_ENV("VTQ_ATTN_LDS_PAD")) : 0;   // occupancy experiments
-    const int LDS = 2 * 2 * 64 * 128 * (NSPLIT == 1 ? 1 : 2) + lds_pad;
-#else
     constexpr int LDS = 2 * 2 * 64 * 128 * (NSPLIT == 1 ? 1 : 2);
-#endif
     static std::mutex mu;
     static bool configured[64] = {false};          // hipFuncSetAttribute is per device
     int dev = 0;
@@ -1228,7 +1061,7 @@ hipError_t launch_attention_t(const void* qkv, int64_t plane, void* out, int64_t
     }
     const dim3 grid(((S_pad - q0 + 127) / 128) * (H / 64) * nseq), blk(256);
     hipLaunchKernelGGL((attention_kernel<T, NSPLIT>), grid, blk, LDS, s, (const T*)qkv, plane, (T*)out, o_plane, S, S_pad, H, out8_scale, obs,
-                       gemm_diag_buffer(), q_log2 ? 1 : 0, q0, S_pad);
+                       q_log2 ? 1 : 0, q0, S_pad);
     return hipGetLastError();
 }
 
@@ -1270,11 +1103,11 @@ hipError_t launch_attention_sw_t(const void* qkv, int64_t plane, void* out, int6
         per = 0;
     }
     hipLaunchKernelGGL((attention_sw_kernel<T, NSPLIT>), grid, blk, LDS, s, (const T*)qkv, plane, (T*)out, o_plane, S, S_pad, H, nblk, per, out8_scale, obs,
-                       gemm_diag_buffer(), q_log2 ? 1 : 0, Sq);
+                       q_log2 ? 1 : 0, Sq);
     return hipGetLastError();
 }
 
-static int g_attn_variant = -1;                 // -1: the rule below (or VTQ_ATTN_VARIANT), 0: 4-wave kernel, 1: pipelined kernel
+static int g_attn_variant = -1;                 // -1: the rule below, 0: 4-wave kernel, 1: pipelined kernel
 void attention_set_variant(int v) { g_attn_variant = v; }
 
 static std::atomic<int> g_attn_cus{0};          // measurement hook (a launch on a CU-masked stream): 0 = the device's CU count
@@ -1314,8 +1147,7 @@ int attention_rule(int nseq, int S_pad, int H, int terms, int cus) {
 }
 
 static int pick_variant(int nseq, int S_pad, int H, int terms, int cus) {
-    static const int env = VTQ_MEASURE_ENV("VTQ_ATTN_VARIANT") ? atoi(VTQ_MEASURE_ENV("VTQ_ATTN_VARIANT")) : -1;   // -DVTQ_MEASURE builds only
-    const int forced = g_attn_variant >= 0 ? g_attn_variant : env;
+    const int forced = g_attn_variant;
     if (forced == 2) return (S_pad >= 256 && S_pad % 256) ? 2 : 1;      // forced split needs a full block and a rest
     if (forced >= 0) return forced == 1 ? 1 : 0;
     return attention_rule(nseq, S_pad, H, terms, cus);

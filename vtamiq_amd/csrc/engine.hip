@@ -911,9 +911,8 @@ int vtq_k_attention_rule(int32_t nseq, int32_t S_pad, int32_t H, int32_t num, in
     return attention_rule(nseq, S_pad, H, nm.terms, cus);
 }
 
-int vtq_debug_gemm_diag(void* buf, int32_t shadow) {
-    gemm_set_diag((unsigned long long*)buf, shadow);
-    return gemm_is_diag_build() ? 1 : 0;
+int vtq_debug_gemm_diag(void*, int32_t) {
+    return 0;
 }
 
 int vtq_debug_mfma_stream(int32_t f16, int32_t data, double warm_s, double timed_s, double* tflops, double* ghz, void* stream) {

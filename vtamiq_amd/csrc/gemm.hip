@@ -38,7 +38,6 @@
 //     ends with 128-row half tiles so the last round is filled in half-tile granules.
 #include <algorithm>
 #include <atomic>
-#include <cstdlib>
 #include <map>
 #include <mutex>
 #include <tuple>
@@ -63,13 +62,6 @@ template <int N> __device__ __forceinline__ void wait_vm() {
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
-#ifndef VTQ_RESID_DEFER
-#define VTQ_RESID_DEFER 0             // 1: residual epilogue with the copy-out's LDS reads issued before the next chunk's conversion (A/B: profiles/r05_epilogue_balanced.txt)
-#endif
-#ifndef VTQ_EPI_BALANCED
-#define VTQ_EPI_BALANCED 1            // 0: the plane-alternating passes of rounds 2 - 4 (A/B: profiles/r05_epilogue_balanced.txt)
-#endif
-
 constexpr int kHalfRows = 128;
 
 // ---- shared epilogue of the ping-pong kernels -------------------------------------------------------------------------
@@ -84,20 +76,10 @@ template <typename T, int OPL, int EPI, int MH> constexpr int epilogue_ops_of() 
 }
 
 // T = OUTPUT element type of the 16-bit / 8-bit forms; SCALED: fp8 operands (acc * wscale[n] * ascale_inv before the bias)
-#ifdef VTQ_GEMM_DIAG
-struct EpiDiag { unsigned long long conv, copy, wait; };
-#define VTQ_EPI_T0() unsigned long long dg_e0; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(dg_e0) :: "memory");
-#define VTQ_EPI_T1(field) { unsigned long long dg_e1; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(dg_e1) :: "memory"); ed.field += dg_e1 - dg_e0; dg_e0 = dg_e1; }
-#else
-struct EpiDiag {};
-#define VTQ_EPI_T0()
-#define VTQ_EPI_T1(field)
-#endif
-
 // BIASED: the accumulators were initialised with the bias (gemm_pp2_kernel init_acc), so the forms below add nothing
 template <typename T, int OPL, int EPI, int MH, bool SCALED, bool BIASED>      // MH = 2: 256-row tile, MH = 1: 128-row half tile (rows m0 .. m0+127)
 __device__ __forceinline__ void pp_epilogue(const GemmArgs& p, f32x4 (&acc)[2][2][4][2], char* smem, int tid, int wr, int wc,
-                                            int fr, int fq, int64_t m0, int n0, EpiDiag& ed) {
+                                            int fr, int fq, int64_t m0, int n0) {
     typedef typename Vec<T>::x4 tx4;
     // opaque copies of the lane indices: every per-lane address below is then formed HERE, after the main loop, instead of being
     // hoisted above it and kept (or spilled) across it
@@ -188,11 +170,11 @@ __device__ __forceinline__ void pp_epilogue(const GemmArgs& p, f32x4 (&acc)[2][2
         }
         copy_out(NPASS - 1);
         fp8_report(p.obs, amax8, p.out_scale);
-#if VTQ_EPI_BALANCED
     } else if constexpr ((EPI == EPI_BIAS || EPI == EPI_BIAS_GELU) && OPL == 2) {
         // Two output planes, BALANCED passes (round 5): chunk (mh, mi) = the 32 rows {mh*128 + wr*64 + mi*16 + fr} with BOTH planes per pass --
-        // image = [plane][row wr*16 + fr][256 x 16 bit + pad] -- so that every barrier interval holds the same work (the form below alternates a pass
-        // with all of a chunk's arithmetic and a pass that only writes the kept lo plane, and needs 16 registers for that plane).  Within an
+        // image = [plane][row wr*16 + fr][256 x 16 bit + pad] -- so that every barrier interval holds the same work (the plane-alternating passes of
+        // rounds 2 - 4 alternated a pass with all of a chunk's arithmetic and a pass that only wrote the kept lo plane, and needed 16 registers for
+        // that plane: A/B in profiles/r05_epilogue_balanced.txt).  Within an
         // interval every wave ISSUES the LDS reads of the previous chunk's copy-out, converts the next chunk under them, then waits and stores:
         // the read latency sits under the conversion and both waves of a SIMD convert at the same time (two waves issue vector instructions
         // every 3.3 cycles, a lone one every 6.6: profiles/r05_gelu_packed.txt section 1).  Same values, same stores per thread.
@@ -244,25 +226,17 @@ __device__ __forceinline__ void pp_epilogue(const GemmArgs& p, f32x4 (&acc)[2][2
                 store_nt16(og, uint4{cv[k][0], cv[k][1], cv[k][2], cv[k][3]});
             }
         };
-        VTQ_EPI_T0()
         convert(0);
-        VTQ_EPI_T1(conv)
         interval_end();
-        VTQ_EPI_T1(wait)
 #pragma unroll
         for (int pass = 1; pass < NPASS; ++pass) {
             copy_issue(pass - 1);
             convert(pass);
-            VTQ_EPI_T1(conv)
             copy_store(pass - 1);
-            VTQ_EPI_T1(copy)
             interval_end();
-            VTQ_EPI_T1(wait)
         }
         copy_issue(NPASS - 1);
         copy_store(NPASS - 1);
-        VTQ_EPI_T1(copy)
-#endif
     } else if constexpr (EPI == EPI_BIAS || EPI == EPI_BIAS_GELU) {
         // chunk (mh, q): the 64 rows {mh*128 + wr*64 + (2q + e)*16 + fr}, image row = wr*32 + e*16 + fr; one pass per plane
         constexpr int RS = 528;                         // 256 x 16 bit + 16 B pad: rows stay 16-B aligned for ds_read_b128
@@ -290,9 +264,7 @@ __device__ __forceinline__ void pp_epilogue(const GemmArgs& p, f32x4 (&acc)[2][2
                                 const float4 bb = b4[nh][ni];
                                 v[0] += bb.x; v[1] += bb.y; v[2] += bb.z; v[3] += bb.w;
                             }
-#if !(defined(VTQ_EPI_ABL) && VTQ_EPI_ABL == 1)                           // measurement build 1: no GELU arithmetic
                             if constexpr (EPI == EPI_BIAS_GELU) gelu_erf4(v);
-#endif
                             if constexpr (NP == 1) {
                                 h = tx4{(T)v[0], (T)v[1], (T)v[2], (T)v[3]};
                             } else if constexpr (std::is_same<T, f16>::value) {
@@ -308,12 +280,7 @@ __device__ __forceinline__ void pp_epilogue(const GemmArgs& p, f32x4 (&acc)[2][2
                         } else {
                             h = lo[(NP == 1) ? 0 : li];
                         }
-#if defined(VTQ_EPI_ABL) && VTQ_EPI_ABL == 4                               // measurement build 4: no LDS staging either
-                        asm volatile("" ::"v"(h));
-                        (void)img; (void)lrow; (void)col;
-#else
                         *(tx4*)(img + lrow * RS + col * 2) = h;
-#endif
                     }
         };
         auto copy_out = [&](int pass) {
@@ -321,46 +288,26 @@ __device__ __forceinline__ void pp_epilogue(const GemmArgs& p, f32x4 (&acc)[2][2
             const char* img = smem + STG + (pass & 1) * IMG;
             const int c16 = tid & 31, r0 = tid >> 5;
             T* og = (T*)p.out + pl * p.o_plane + m0 * p.ldo + n0 + c16 * 8;
-#if defined(VTQ_EPI_ABL) && (VTQ_EPI_ABL == 2 || VTQ_EPI_ABL == 4)          // measurement builds: no copy-out at all
-            (void)img; (void)og; (void)mh; (void)q; (void)r0; (void)c16;
-#else
             u32x4 v[4];
             lds_read_rows4<16 * RS>(img + r0 * RS + c16 * 16, v);
 #pragma unroll
             for (int ps = 0; ps < 4; ++ps) {            // image row ps*16 + r0 = (wr = ps>>1, e = ps&1, fr = r0)
                 const int grow = mh * 128 + (ps >> 1) * 64 + (2 * q + (ps & 1)) * 16 + r0;
-#if defined(VTQ_EPI_ABL) && VTQ_EPI_ABL == 3                               // measurement build: LDS read kept, global store dropped
-                asm volatile("" ::"v"(v[ps])); (void)grow;
-#else
                 store_nt16(og + (int64_t)grow * p.ldo, uint4{v[ps][0], v[ps][1], v[ps][2], v[ps][3]});
-#endif
             }
-#endif
         };
         // Within an interval the two wave groups (the two waves of every SIMD) run the two steps in OPPOSITE order -- they touch
         // different images, so either order is valid -- so that one wave's VALU conversion runs while its SIMD partner sits in
         // the store-issue queue, instead of both queueing and then both converting.
-        VTQ_EPI_T0()
         convert(0);
-        VTQ_EPI_T1(conv)
         interval_end();
-        VTQ_EPI_T1(wait)
 #pragma unroll
         for (int pass = 1; pass < NPASS; ++pass) {
-#if defined(VTQ_EPI_ORDER) && VTQ_EPI_ORDER == 1          // measurement builds: both wave groups copy first / convert first
-            const bool copy_first = true;
-#elif defined(VTQ_EPI_ORDER) && VTQ_EPI_ORDER == 2
-            const bool copy_first = false;
-#else
-            const bool copy_first = (wr == 0);
-#endif
-            if (copy_first) { copy_out(pass - 1); VTQ_EPI_T1(copy) convert(pass); VTQ_EPI_T1(conv) }
-            else { convert(pass); VTQ_EPI_T1(conv) copy_out(pass - 1); VTQ_EPI_T1(copy) }
+            if (wr == 0) { copy_out(pass - 1); convert(pass); }
+            else { convert(pass); copy_out(pass - 1); }
             interval_end();
-            VTQ_EPI_T1(wait)
         }
         copy_out(NPASS - 1);
-        VTQ_EPI_T1(copy)
     } else if constexpr (EPI == EPI_RESID) {
         // chunk (mh, mi): the 32 rows {mh*128 + wr*64 + mi*16 + fr}, image row = wr*16 + fr, fp32; the residual rows of chunk
         // k are requested one interval before they are needed
@@ -395,46 +342,14 @@ __device__ __forceinline__ void pp_epilogue(const GemmArgs& p, f32x4 (&acc)[2][2
             for (int ps = 0; ps < 4; ++ps) xv[ch & 1][ps] = *(const float4*)(xg + (int64_t)grow_of(ch, ps) * p.N);
         };
         f32x4 dv[4];
-#if VTQ_RESID_DEFER
-        // the previous chunk's image rows are requested BEFORE the next chunk's conversion and waited for behind it (as in the balanced two-plane form)
-        auto copy_issue = [&](int ch) {
-            const char* img = smem + STG + (ch & 1) * IMG;
-            asm volatile("ds_read_b128 %0, %4\n\tds_read_b128 %1, %4 offset:%c5\n\tds_read_b128 %2, %4 offset:%c6\n\tds_read_b128 %3, %4 offset:%c7"
-                         : "=&v"(dv[0]), "=&v"(dv[1]), "=&v"(dv[2]), "=&v"(dv[3])
-                         : "v"(lds_addr(img + r0 * RS + c16 * 16)), "i"(8 * RS), "i"(16 * RS), "i"(24 * RS) : "memory");
-        };
-#endif
         auto copy_out = [&](int ch) {
-#if VTQ_RESID_DEFER
-            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(dv[0]), "+v"(dv[1]), "+v"(dv[2]), "+v"(dv[3]) :: "memory");
-#else
             const char* img = smem + STG + (ch & 1) * IMG;
             lds_read_rows4<8 * RS>(img + r0 * RS + c16 * 16, dv);
-#endif
 #pragma unroll
             for (int ps = 0; ps < 4; ++ps) {            // image row ps*8 + r0 = (wr = ps>>1, fr = (ps&1)*8 + r0)
                 float4 x = xv[ch & 1][ps];
                 x.x += dv[ps][0]; x.y += dv[ps][1]; x.z += dv[ps][2]; x.w += dv[ps][3];
                 *(float4*)(xg + (int64_t)grow_of(ch, ps) * p.N) = x;
-#ifdef VTQ_RESID_PLANES
-                // Pricing build (tools/ln_fold_price.py): what the producer side of a LayerNorm fold would add to this epilogue -- the new
-                // residual row also as the consumer's hi / lo operand planes, and the (mean, M2) of its 256 columns for a Chan combination.
-                if (p.out) {
-                    typedef typename Vec<T>::x4 tx4;
-                    const int64_t gr = m0 + grow_of(ch, ps);
-                    T* pg = (T*)p.out + gr * p.ldo + n0 + c16 * 4;
-                    const float xs[4] = {x.x, x.y, x.z, x.w};
-                    tx4 h, l;
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) { T a, b; split2<T>(xs[k], a, b); h[k] = a; l[k] = b; }
-                    *(tx4*)pg = h;
-                    *(tx4*)(pg + p.o_plane) = l;
-                    const float mt = wave_sum((x.x + x.y) + (x.z + x.w)) * (1.0f / 256.0f);
-                    const float d0 = x.x - mt, d1 = x.y - mt, d2 = x.z - mt, d3 = x.w - mt;
-                    const float m2 = wave_sum((d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3));
-                    if (c16 == 0 && p.row_stats) *(float2*)(p.row_stats + (gr * (p.N >> 8) + (n0 >> 8)) * 2) = float2{mt, m2};
-                }
-#endif
             }
         };
         load_x(0);
@@ -443,19 +358,10 @@ __device__ __forceinline__ void pp_epilogue(const GemmArgs& p, f32x4 (&acc)[2][2
 #pragma unroll
         for (int ch = 1; ch < NCH; ++ch) {
             load_x(ch);
-#if VTQ_RESID_DEFER
-            copy_issue(ch - 1);
-            convert(ch);
-            copy_out(ch - 1);
-#else
             copy_out(ch - 1);
             convert(ch);
-#endif
             interval_end();
         }
-#if VTQ_RESID_DEFER
-        copy_issue(NCH - 1);
-#endif
         copy_out(NCH - 1);
     } else {  // EPI_EMBED: scattered rows + table gathers, once per forward: direct from registers
 #pragma unroll
@@ -696,30 +602,6 @@ __global__ __launch_bounds__(512, 2) void gemm_pp2_kernel(GemmArgs p) {
     // vmcnt -- i.e. the previous tile's epilogue stores -- at the top of every tile
     const __attribute__((address_space(4))) int* sch = (const __attribute__((address_space(4))) int*)p.sched;
     const int it_beg = sch[blockIdx.x], it_end = sch[blockIdx.x + 1];
-    EpiDiag epi_diag{};
-#ifdef VTQ_GEMM_DIAG
-    // Diagnostic build only (MI355X_MICROARCH.md 'DVFS give-back' item 6): shader-clock and 100 MHz real-time stamps around every
-    // K loop and around the whole kernel, summed in scalar registers and written to a buffer nothing else reads.
-    unsigned long long dg_lt = 0, dg_lr = 0, dg_t0, dg_r0, dg_kt0, dg_kr0;
-    auto stamp = [&](unsigned long long& t, unsigned long long& r) {
-        asm volatile("s_memtime %0\n\ts_memrealtime %1\n\ts_waitcnt lgkmcnt(0)" : "=s"(t), "=s"(r) :: "memory");
-    };
-    stamp(dg_kt0, dg_kr0);
-    float dg_v[4] = {1.0f, 1.5f, 2.0f, 2.5f};
-    auto shadow_valu = [&]() {           // p.shadow x 8 independent FMAs in the load phase (beside the partner wave's MFMA cluster)
-        for (int i = 0; i < p.shadow; ++i)
-            asm volatile("v_fma_f32 %0, %0, %1, %2\n\tv_fma_f32 %1, %1, %2, %3\n\tv_fma_f32 %2, %2, %3, %0\n\tv_fma_f32 %3, %3, %0, %1\n\t"
-                         "v_fma_f32 %0, %0, %1, %2\n\tv_fma_f32 %1, %1, %2, %3\n\tv_fma_f32 %2, %2, %3, %0\n\tv_fma_f32 %3, %3, %0, %1"
-                         : "+v"(dg_v[0]), "+v"(dg_v[1]), "+v"(dg_v[2]), "+v"(dg_v[3]));
-    };
-#define VTQ_DIAG_SHADOW() shadow_valu();
-#define VTQ_DIAG_LOOP_BEGIN() stamp(dg_t0, dg_r0);
-#define VTQ_DIAG_LOOP_END() { unsigned long long t1, r1; stamp(t1, r1); dg_lt += t1 - dg_t0; dg_lr += r1 - dg_r0; }
-#else
-#define VTQ_DIAG_SHADOW()
-#define VTQ_DIAG_LOOP_BEGIN()
-#define VTQ_DIAG_LOOP_END()
-#endif
     bool chained = false;       // this tile's K tile 0 (both groups) was staged by the previous tile; K tile 1's g2 is still to issue
     for (int it = it_beg; it < it_end; ++it) {
         const int d = sch[it];
@@ -727,20 +609,19 @@ __global__ __launch_bounds__(512, 2) void gemm_pp2_kernel(GemmArgs p) {
         const int tm = tile / ntn, tn = tile - tm * ntn;
         const int64_t m0 = (int64_t)tm * 256 + (kind == 2 ? kHalfRows : 0);
         const int n0 = tn * 256;
-        const bool wrapl = (gemm_flags(p) & GEMM_FLAG_WRAP_LOADS) != 0;     // measurement: every tile reads the first two A / W panels (L2 hits)
-        const T* __restrict__ Ag = (const T*)p.A + (wrapl ? (m0 & 511) : m0) * p.lda;
-        const T* __restrict__ Wg = (const T*)p.W + (int64_t)(wrapl ? (n0 & 511) : n0) * p.K;
+        const T* __restrict__ Ag = (const T*)p.A + m0 * p.lda;
+        const T* __restrict__ Wg = (const T*)p.W + (int64_t)n0 * p.K;
         // the next entry of this workgroup's list, if the DMA ring may run on into it
         const T* Agn = Ag;
         const T* Wgn = Wg;
         bool has_next = false;
         if constexpr (kChain) {
-            if (kind == 0 && it + 1 < it_end && !(gemm_flags(p) & GEMM_FLAG_NO_CHAIN)) {
+            if (kind == 0 && it + 1 < it_end) {
                 const int dn = sch[it + 1];
                 if ((dn & 3) == 0) {
                     const int tmn = (dn >> 2) / ntn, tnn = (dn >> 2) - tmn * ntn;
-                    Agn = (const T*)p.A + (int64_t)(wrapl ? (tmn & 1) : tmn) * 256 * p.lda;
-                    Wgn = (const T*)p.W + (int64_t)(wrapl ? (tnn & 1) : tnn) * 256 * p.K;
+                    Agn = (const T*)p.A + (int64_t)tmn * 256 * p.lda;
+                    Wgn = (const T*)p.W + (int64_t)tnn * 256 * p.K;
                     has_next = true;
                 }
             }
@@ -762,7 +643,6 @@ __global__ __launch_bounds__(512, 2) void gemm_pp2_kernel(GemmArgs p) {
             if (wr == 1) __builtin_amdgcn_s_barrier();        // second wave group runs one barrier behind
             if constexpr (kBiasInAcc) init_acc(n0);           // here, not at the top of the tile: the accumulators are dead until now
 
-            VTQ_DIAG_LOOP_BEGIN()
             for (int kt = 0; kt < nkt; ++kt) {
                 const char* buf = smem + (kt & 1) * BUF_B;
                 // ---- phase A --------------------------------------------------------------------------------------------
@@ -779,7 +659,6 @@ __global__ __launch_bounds__(512, 2) void gemm_pp2_kernel(GemmArgs p) {
                 } else {
                     wait_vm<0>();
                 }
-                VTQ_DIAG_SHADOW()
                 VTQ_SYNC_OPEN_WAITED()
                 mma(acc[0][0], fb0);
                 mma(acc[0][1], fb1);
@@ -793,26 +672,13 @@ __global__ __launch_bounds__(512, 2) void gemm_pp2_kernel(GemmArgs p) {
                     if (has_next) { stage(Agn, Wgn, 0, 0); stage(Agn, Wgn, 0, 1); stage(Agn, Wgn, 0, 2); wait_vm<GO + GE>(); }
                     else wait_vm<GO>();
                 }                                             // last K tile: nothing of this tile is left to land
-                VTQ_DIAG_SHADOW()
                 VTQ_SYNC_OPEN_WAITED()
                 mma(acc[1][1], fb1);
                 mma(acc[1][0], fb0);
                 VTQ_SYNC_CLOSE()
             }
-            VTQ_DIAG_LOOP_END()
             if (wr == 0) __builtin_amdgcn_s_barrier();        // match the extra barrier of the second group
-            if (!(gemm_flags(p) & GEMM_FLAG_NO_EPILOGUE))
-                pp_epilogue<TO, OPL, EPI, 2, F8, kBiasInAcc>(p, acc, smem, tid, wr, wc, fr, fq, (gemm_flags(p) & GEMM_FLAG_WRAP_ROWS) ? 0 : m0, n0, epi_diag);
-            else {
-#pragma unroll
-                for (int a = 0; a < 2; ++a)
-#pragma unroll
-                    for (int b = 0; b < 2; ++b)
-#pragma unroll
-                        for (int i = 0; i < 4; ++i)
-#pragma unroll
-                            for (int j = 0; j < 2; ++j) asm volatile("" ::"v"(acc[a][b][i][j]));
-            }
+            pp_epilogue<TO, OPL, EPI, 2, F8, kBiasInAcc>(p, acc, smem, tid, wr, wc, fr, fq, m0, n0);
             chained = has_next;
             if (it + 1 < it_end) {                            // the staging images are re-staged / re-used next: retire their reads
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -842,7 +708,6 @@ __global__ __launch_bounds__(512, 2) void gemm_pp2_kernel(GemmArgs p) {
             if (wr == 1) __builtin_amdgcn_s_barrier();
             if constexpr (kBiasInAcc) init_acc(n0);
             int slot = 0;                                      // kt % 3
-            VTQ_DIAG_LOOP_BEGIN()
             for (int kt = 0; kt < nkt; ++kt) {
                 const char* buf = smem + slot * BUF_H;
                 read_b(buf + 1 * REG_B, fb0);
@@ -851,16 +716,14 @@ __global__ __launch_bounds__(512, 2) void gemm_pp2_kernel(GemmArgs p) {
                 const int nslot = slot == 0 ? 2 : slot - 1;    // (kt + 2) % 3
                 if (kt + 2 < nkt) { stage_h(kt + 2, nslot); wait_vm<GH>(); }
                 else wait_vm<0>();
-                VTQ_DIAG_SHADOW()
                 VTQ_SYNC_OPEN_WAITED()
                 mma(acc[0][0], fb0);
                 mma(acc[0][1], fb1);
                 VTQ_SYNC_CLOSE()
                 slot = slot == 2 ? 0 : slot + 1;
             }
-            VTQ_DIAG_LOOP_END()
             if (wr == 0) __builtin_amdgcn_s_barrier();
-            pp_epilogue<TO, OPL, EPI, 1, F8, kBiasInAcc>(p, acc, smem, tid, wr, wc, fr, fq, (gemm_flags(p) & GEMM_FLAG_WRAP_ROWS) ? 0 : m0, n0, epi_diag);
+            pp_epilogue<TO, OPL, EPI, 1, F8, kBiasInAcc>(p, acc, smem, tid, wr, wc, fr, fq, m0, n0);
             chained = false;
             if (it + 1 < it_end) {
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -868,24 +731,6 @@ __global__ __launch_bounds__(512, 2) void gemm_pp2_kernel(GemmArgs p) {
             }
         }
     }
-#ifdef VTQ_GEMM_DIAG
-    {
-        unsigned long long t1, r1;
-        stamp(t1, r1);
-        unsigned xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        asm volatile("" ::"v"(dg_v[0]), "v"(dg_v[1]), "v"(dg_v[2]), "v"(dg_v[3]));
-        if (p.diag && (threadIdx.x & 63) == 0) {
-            unsigned long long* d = p.diag + (size_t)blockIdx.x * 64;
-            if (threadIdx.x == 0) { d[0] = dg_lt; d[1] = dg_lr; d[2] = t1 - dg_kt0; d[3] = r1 - dg_kr0; d[4] = (unsigned long long)(it_end - it_beg); d[5] = xcc & 0xf; }
-            unsigned long long* w = d + 8 + (threadIdx.x >> 6) * 4;          // per wave: cycles in convert / copy-out / interval-end waits
-            w[0] = epi_diag.conv; w[1] = epi_diag.copy; w[2] = epi_diag.wait;
-        }
-    }
-#endif
-#undef VTQ_DIAG_SHADOW
-#undef VTQ_DIAG_LOOP_BEGIN
-#undef VTQ_DIAG_LOOP_END
 #undef VTQ_SYNC_OPEN_WAITED
 #undef VTQ_SYNC_CLOSE
 }
@@ -906,14 +751,13 @@ __global__ __launch_bounds__(512, 2) void gemm_pp2_kernel(GemmArgs p) {
 constexpr int kXcds = 8, kCusPerXcd = 32, kNumCus = kXcds * kCusPerXcd;
 constexpr double kHalfCost = 0.57;
 
-// Workgroups per XCD of the persistent launch: all 32 CUs, unless a measurement narrows the grid -- vtq_debug_gemm_cus (a launch on a
-// CU-masked stream, tools/cu_partition.py: the grid must match the CUs the stream owns, the schedule is rebuilt for it) or, in
-// -DVTQ_MEASURE builds, VTQ_GEMM_CUS.  Results never depend on it (the tile -> workgroup assignment does not enter the arithmetic).
+// Workgroups per XCD of the persistent launch: all 32 CUs, unless a measurement narrows the grid with vtq_debug_gemm_cus (a launch on a
+// CU-masked stream, tools/cu_partition.py: the grid must match the CUs the stream owns, the schedule is rebuilt for it).  Results never
+// depend on it (the tile -> workgroup assignment does not enter the arithmetic).
 std::atomic<int> g_cus_per_xcd{0};
 int cus_per_xcd() {
-    static const int env = [] { const char* v = VTQ_MEASURE_ENV("VTQ_GEMM_CUS"); const int k = v ? atoi(v) : kCusPerXcd; return (k >= 1 && k <= kCusPerXcd) ? k : kCusPerXcd; }();
     const int g = g_cus_per_xcd.load(std::memory_order_relaxed);
-    return (g >= 1 && g <= kCusPerXcd) ? g : env;
+    return (g >= 1 && g <= kCusPerXcd) ? g : kCusPerXcd;
 }
 
 double greedy_makespan(int n_full, int n_half) {
@@ -933,14 +777,12 @@ double greedy_makespan(int n_full, int n_half) {
 
 // entries of one XCD owning `order[0..cnt)`: whole tiles, then `tail` tiles as top/bottom halves
 void xcd_sequence(const int* order, int cnt, std::vector<int>& out) {
-    static const bool all_halves = [] { const char* v = VTQ_MEASURE_ENV("VTQ_GEMM_SCHED"); return v && v[0] == '2'; }();   // measurement knob
     int best_tail = 0;
     double best = 1e30;
     for (int tail = 0; tail <= cnt && tail <= 2 * kCusPerXcd; ++tail) {
         const double m = greedy_makespan(cnt - tail, 2 * tail) + 1e-3 * tail;
         if (m < best) { best = m; best_tail = tail; }
     }
-    if (all_halves) best_tail = cnt;
     for (int i = 0; i < cnt - best_tail; ++i) out.push_back(order[i] << 2);
     for (int i = cnt - best_tail; i < cnt; ++i) { out.push_back((order[i] << 2) | 1); out.push_back((order[i] << 2) | 2); }
 }
@@ -972,45 +814,16 @@ std::vector<int> build_schedule(int ntm, int ntn, int cg) {
     // workgroup of the chip reaches its epilogue -- a burst of stores and, in the residual form, loads -- at the same moments; with the
     // half tile in front, the odd XCDs' epilogues fall about half a tile after the even ones'.  Whole XCDs, not every second CU of one:
     // the column tiles of a row panel that share their A panel through the XCD's L2 stay in step (per-CU staggering cost fc2 3.5 %).
-    // Same work, same results (profiles/r03_gemm_stagger.txt: out-proj -6 %, QKV -3 %, fc2 and fc1 unchanged; -DVTQ_MEASURE builds: VTQ_GEMM_STAGGER=0 turns it off).
-    static const bool stagger = [] { const char* v = VTQ_MEASURE_ENV("VTQ_GEMM_STAGGER"); return !(v && v[0] == '0'); }();
-    if (stagger)
-        for (int b = 0; b < kNumCus; ++b) {
-            std::vector<int>& l = lists[b];
-            if (((b % kXcds) & 1) && l.size() >= 2 && (l.back() & 3) && !(l[l.size() - 2] & 3)) { const int h = l.back(); l.pop_back(); l.insert(l.begin(), h); }
-        }
+    // Same work, same results (profiles/r03_gemm_stagger.txt: out-proj -6 %, QKV -3 %, fc2 and fc1 unchanged).
+    for (int b = 0; b < kNumCus; ++b) {
+        std::vector<int>& l = lists[b];
+        if (((b % kXcds) & 1) && l.size() >= 2 && (l.back() & 3) && !(l[l.size() - 2] & 3)) { const int h = l.back(); l.pop_back(); l.insert(l.begin(), h); }
+    }
     std::vector<int> out(kNumCus + 1);
     int off = kNumCus + 1;
     for (int b = 0; b < kNumCus; ++b) { out[b] = off; off += (int)lists[b].size(); }
     out[kNumCus] = off;
     for (int b = 0; b < kNumCus; ++b) out.insert(out.end(), lists[b].begin(), lists[b].end());
-    return out;
-}
-
-// Measurement form (GEMM_FLAG_DYNAMIC): the same per-XCD sequences, but one entry per workgroup in hardware dispatch order
-// (block b -> XCD b % 8): offsets[b] = first entry of block b, one entry each.
-std::vector<int> build_schedule_dynamic(int ntm, int ntn, int cg) {
-    const int nt = ntm * ntn, q = nt / kXcds, r = nt % kXcds;
-    if (cg < 1) cg = 1;
-    std::vector<std::vector<int>> seq(kXcds);
-    size_t total = 0;
-    for (int x = 0; x < kXcds; ++x) {
-        const int t0 = x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q, cnt = q + (x < r ? 1 : 0);
-        std::vector<std::tuple<int, int, int, int>> keyed;
-        for (int t = t0; t < t0 + cnt; ++t) keyed.emplace_back((t % ntn) / cg, t / ntn, t % ntn, t);
-        std::sort(keyed.begin(), keyed.end());
-        std::vector<int> order(cnt);
-        for (int i = 0; i < cnt; ++i) order[i] = std::get<3>(keyed[i]);
-        xcd_sequence(order.data(), cnt, seq[x]);
-        total += seq[x].size();
-    }
-    std::vector<int> ent;
-    for (size_t j = 0; ent.size() < total; ++j)
-        for (int x = 0; x < kXcds; ++x)
-            if (j < seq[x].size()) ent.push_back(seq[x][j]);
-    std::vector<int> out(total + 1);
-    for (size_t b = 0; b <= total; ++b) out[b] = (int)(total + 1 + b);
-    out.insert(out.end(), ent.begin(), ent.end());
     return out;
 }
 
@@ -1025,22 +838,22 @@ int column_group(int ntn, int K, int wpl) {
 // Device-resident schedules, per DEVICE (a second engine on another GPU of the same process gets its own copies) and per
 // (tile grid, column group); entries are a few KiB and live until exit.
 struct DevSched { int* dev; int nwg; };
-hipError_t schedule_for(int ntm, int ntn, int cg, bool dynamic, DevSched& ds, hipStream_t s) {
+hipError_t schedule_for(int ntm, int ntn, int cg, DevSched& ds, hipStream_t s) {
     static std::mutex mu;
-    static std::map<std::tuple<int, int, int, int, int, int>, DevSched> cache;
+    static std::map<std::tuple<int, int, int, int, int>, DevSched> cache;
     static std::vector<std::vector<int>*> staged;              // host images of uploads in flight on some stream: kept for the process lifetime
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;
     std::lock_guard<std::mutex> lk(mu);
-    const auto key = std::make_tuple(dev, ntm, ntn, cg, (int)dynamic, cus_per_xcd());
+    const auto key = std::make_tuple(dev, ntm, ntn, cg, cus_per_xcd());
     auto it = cache.find(key);
     if (it != cache.end()) { ds = it->second; return hipSuccess; }
     // First use of a shape on this device.  The engine does this from vtq_reserve / the top of vtq_forward (gemm_prepare), never
     // between the launches of a forward; the per-kernel test entry points may land here from a launch.  The upload is an async
     // copy on the launch stream (ordered before the kernel that reads it) from a host image that stays alive.
-    std::vector<int>* h = new std::vector<int>(dynamic ? build_schedule_dynamic(ntm, ntn, cg) : build_schedule(ntm, ntn, cg));
-    DevSched d{nullptr, dynamic ? (*h)[0] - 1 : kXcds * cus_per_xcd()};
+    std::vector<int>* h = new std::vector<int>(build_schedule(ntm, ntn, cg));
+    DevSched d{nullptr, kXcds * cus_per_xcd()};
     e = hipMalloc(&d.dev, h->size() * sizeof(int));
     if (e != hipSuccess) { delete h; return e; }
     e = hipMemcpyAsync(d.dev, h->data(), h->size() * sizeof(int), hipMemcpyHostToDevice, s);
@@ -1049,19 +862,6 @@ hipError_t schedule_for(int ntm, int ntn, int cg, bool dynamic, DevSched& ds, hi
     cache[key] = d;
     ds = d;
     return hipSuccess;
-}
-
-int env_cg() {
-    static const int v = [] { const char* c = VTQ_MEASURE_ENV("VTQ_GEMM_CG"); return c ? atoi(c) : 0; }();    // measurement knob: column-group width of the tile order
-    return v;
-}
-
-unsigned long long* g_diag_buf = nullptr;      // diagnostic builds: stamp buffer and shadow-VALU count (gemm_set_diag)
-int g_diag_shadow = 0;
-
-int env_flags() {
-    static const int f = [] { const char* v = VTQ_MEASURE_ENV("VTQ_GEMM_FLAGS"); return v ? atoi(v) : 0; }();   // measurement knobs (kernels.h)
-    return f;
 }
 
 template <typename T, int TERMS, int EPI> hipError_t launch_t(GemmArgs a, hipStream_t s) {
@@ -1082,22 +882,9 @@ template <typename T, int TERMS, int EPI> hipError_t launch_t(GemmArgs a, hipStr
     }
     constexpr int WPL = (TERMS == 3) ? 2 : 1;
     DevSched ds;
-    a.flags = env_flags();
-    const int cg = env_cg() > 0 ? env_cg() : column_group(a.N / 256, a.K, WPL);
-    e = schedule_for(a.M / 256, a.N / 256, cg, (a.flags & GEMM_FLAG_DYNAMIC) != 0, ds, s);
+    e = schedule_for(a.M / 256, a.N / 256, column_group(a.N / 256, a.K, WPL), ds, s);
     if (e != hipSuccess) return e;
     a.sched = ds.dev;
-    a.diag = g_diag_buf;
-    a.shadow = g_diag_shadow;
-#ifdef VTQ_RESID_PLANES
-    {   // pricing build: a statistics buffer nothing reads (one per process, sized for the largest M x N / 256 asked for so far)
-        static float* stats = nullptr;
-        static size_t cap = 0;
-        const size_t need = (size_t)a.M * (a.N / 256) * 2 * sizeof(float);
-        if (need > cap) { if (stats) (void)hipFree(stats); if (hipMalloc((void**)&stats, need) != hipSuccess) return hipErrorOutOfMemory; cap = need; }
-        a.row_stats = stats;
-    }
-#endif
     hipLaunchKernelGGL((gemm_pp2_kernel<T, TERMS, EPI>), dim3(ds.nwg), dim3(512), LDS, s, a);
     return hipGetLastError();
 }
@@ -1114,21 +901,10 @@ template <typename T, int TERMS> hipError_t launch_e(const GemmArgs& a, int epil
 
 }  // namespace
 
-void gemm_set_diag(unsigned long long* buf, int shadow) { g_diag_buf = buf; g_diag_shadow = shadow; }
-unsigned long long* gemm_diag_buffer() { return g_diag_buf; }
-bool gemm_is_diag_build() {
-#ifdef VTQ_GEMM_DIAG
-    return true;
-#else
-    return false;
-#endif
-}
-
 hipError_t gemm_prepare(int M, int N, int K, int wpl, hipStream_t s) {
     if (M <= 0 || M % 256 || N <= 0 || N % 256) return hipErrorInvalidValue;
     DevSched ds;
-    const int cg = env_cg() > 0 ? env_cg() : column_group(N / 256, K, wpl);
-    return schedule_for(M / 256, N / 256, cg, (env_flags() & GEMM_FLAG_DYNAMIC) != 0, ds, s);
+    return schedule_for(M / 256, N / 256, column_group(N / 256, K, wpl), ds, s);
 }
 
 std::vector<int> gemm_tile_schedule(int ntm, int ntn, int K, int wpl) {

@@ -38,7 +38,6 @@
 #include "dev_common.h"
 #include "kernels.h"
 
-#include <cstdlib>
 #include <mutex>
 
 namespace vtq {
@@ -50,11 +49,9 @@ template <int N> __device__ __forceinline__ void st_wait_vm() {
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
-// MODE (exploration builds only): 0 = the kernel; 1 = no fragment reads / MFMAs (the load path alone); 2 = no LDS-DMA (compute + barriers
-// alone); 3 = 2 without the barriers; 4 = 2 without the fragment reads; 5 = MFMAs alone
 // NPW: producer waves.  0: the WR x WC MFMA waves issue the LDS-DMA themselves.  > 0: NPW extra waves do nothing but issue the DMA, wait for it and
 // synchronise -- the MFMA waves then spend no issue slots on DMA addressing and never stall on vmcnt (one wave per SIMD has nothing else to overlap with).
-template <typename T, int TERMS, int EPI, int BM, int BN, int WR, int WC, int NST, int MODE = 0, int NPW = 0>
+template <typename T, int TERMS, int EPI, int BM, int BN, int WR, int WC, int NST, int NPW = 0>
 __global__ __launch_bounds__(64 * (WR * WC + NPW)) void gemm_st_kernel(GemmArgs p) {
     typedef typename Vec<T>::x8 tx8;
     typedef typename Vec<T>::x4 tx4;
@@ -103,7 +100,6 @@ __global__ __launch_bounds__(64 * (WR * WC + NPW)) void gemm_st_kernel(GemmArgs 
     const int64_t a_pl = p.a_plane * 2, w_pl = p.w_plane * 2;
     const int64_t a_rb = (int64_t)PR * p.lda * 2, w_rb = (int64_t)PR * p.K * 2;
     auto issue = [&](int kt, int s) {
-        if constexpr (MODE >= 2) return;
         char* dst = smem + s * STAGE + dwave * 1024;
         const int kb = kt * ROWB;                         // byte column of the stage
 #pragma unroll
@@ -230,26 +226,16 @@ __global__ __launch_bounds__(64 * (WR * WC + NPW)) void gemm_st_kernel(GemmArgs 
         const int rem = nkt - kt - 1;                 // stages issued behind this one (at most NST - 2 at this point)
         wait_stages(rem < NST - 2 ? rem : NST - 2);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        if constexpr (MODE != 3 && MODE != 5) __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_s_barrier();
         // re-stage the slot read in iteration kt - 1
         if constexpr (NPW == 0)
             if (kt + NST - 1 < nkt) issue(kt + NST - 1, slot == 0 ? NST - 1 : slot - 1);
         const char* buf = smem + slot * STAGE;
-        if constexpr (MODE >= 4) {         // exploration: no fragment reads (the same registers every k-step)
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
             Frag f;
-            if (kt == 0) read_frag(f, buf, 0);
-#pragma unroll
-            for (int i = 0; i < MI; ++i) asm volatile("" : "+v"(f.a[i][0]));
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) mma(f);
-        } else
-        if constexpr (MODE != 1) {
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) {
-                Frag f;
-                read_frag(f, buf, ks);
-                mma(f);
-            }
+            read_frag(f, buf, ks);
+            mma(f);
         }
         slot = (slot == NST - 1) ? 0 : slot + 1;
     }
@@ -326,8 +312,6 @@ __global__ __launch_bounds__(64 * (WR * WC + NPW)) void gemm_st_kernel(GemmArgs 
 // W counts double: inside a forward it comes from HBM, A from the Infinity Cache.  Only grids that leave no XCD without tiles.
 constexpr int kColdW = 2;
 int st_xcd_grid(int M, int N, int ntm, int ntn) {
-    static const int forced = [] { const char* v = VTQ_MEASURE_ENV("VTQ_ST_GRID"); return v ? atoi(v) : 0; }();   // measurement builds: rows * 16 + columns
-    if (forced) return forced;
     int best = (8 << 4) | 1;
     long best_cost = -1;
     for (int gr = 8; gr >= 1; gr >>= 1) {
@@ -339,12 +323,12 @@ int st_xcd_grid(int M, int N, int ntm, int ntn) {
     return best;
 }
 
-template <typename T, int TERMS, int EPI, int BM, int BN, int WR, int WC, int NST, int MODE = 0, int NPW = 0>
+template <typename T, int TERMS, int EPI, int BM, int BN, int WR, int WC, int NST, int NPW = 0>
 hipError_t launch_v(const GemmArgs& a, hipStream_t s) {
     constexpr int APL = (TERMS == 1) ? 1 : 2, WPL = (TERMS == 3) ? 2 : 1;
     constexpr int LDS = NST * (APL * BM + WPL * BN) * 128;
     static_assert(LDS <= 163840, "LDS ring");
-    auto kern = gemm_st_kernel<T, TERMS, EPI, BM, BN, WR, WC, NST, MODE, NPW>;
+    auto kern = gemm_st_kernel<T, TERMS, EPI, BM, BN, WR, WC, NST, NPW>;
     if constexpr (LDS > 65536) {
         static std::mutex mu;
         static bool configured[64] = {false};
@@ -372,32 +356,9 @@ template <typename T, int TERMS, int EPI> hipError_t launch_shape(const GemmArgs
     switch (variant) {
         // MFMA waves 2x2 (64x64) or 2x4 (128x128) + DMA-only producer waves (profiles/r05_gemm_tile_shapes.txt: -24 .. -27 % on the B = 1 out-proj / fc2,
         // -16 .. -18 % on the 128x128 fc2 of B = 3 .. 5 against the same tiles with the MFMA waves issuing the DMA themselves)
-        case GEMM_ST_64: return launch_v<T, TERMS, EPI, 64, 64, 2, 2, 3, 0, 2>(a, s);    // ring of 3: 96 KiB (3-term formats), one workgroup per CU; 4 + 2 waves
-        case GEMM_ST_64X2: return launch_v<T, TERMS, EPI, 64, 64, 2, 2, 2, 0, 4>(a, s);  // ring of 2: 64 KiB, two workgroups per CU; 4 + 4 waves
-        case GEMM_ST_128: return launch_v<T, TERMS, EPI, 128, 128, 2, 4, 2, 0, 8>(a, s); // ring of 2: 128 KiB; 8 + 8 waves
-#ifdef VTQ_GEMM_ST_EXPLORE                                   // tile-shape exploration builds (tools/st_bench.py): not in the product library
-        case 9: return launch_v<T, TERMS, EPI, 64, 64, 2, 2, 3>(a, s);                   // the three shapes WITHOUT producer waves
-        case 10: return launch_v<T, TERMS, EPI, 64, 64, 2, 2, 2>(a, s);
-        case 18: return launch_v<T, TERMS, EPI, 128, 128, 2, 4, 2>(a, s);
-        case 4: return launch_v<T, TERMS, EPI, 128, 64, 2, 2, 3>(a, s);
-        case 5: return launch_v<T, TERMS, EPI, 64, 128, 2, 2, 3>(a, s);
-        case 6: return launch_v<T, TERMS, EPI, 128, 128, 2, 2, 2>(a, s);
-        case 7: return launch_v<T, TERMS, EPI, 64, 64, 2, 2, 4>(a, s);
-        case 8: return launch_v<T, TERMS, EPI, 64, 64, 2, 2, 5>(a, s);
-        case 20: return launch_v<T, TERMS, EPI, 64, 64, 2, 2, 3, 0, 4>(a, s);
-        case 21: return launch_v<T, TERMS, EPI, 64, 64, 2, 2, 2, 0, 4>(a, s);
-        case 22: return launch_v<T, TERMS, EPI, 128, 128, 2, 4, 2, 0, 4>(a, s);
-        case 23: return launch_v<T, TERMS, EPI, 64, 64, 2, 2, 3, 0, 2>(a, s);
-        case 24: return launch_v<T, TERMS, EPI, 64, 64, 2, 2, 4, 0, 4>(a, s);
-        case 25: return launch_v<T, TERMS, EPI, 128, 128, 2, 4, 2, 0, 8>(a, s);
-        case 11: return launch_v<T, TERMS, EPI, 64, 64, 2, 2, 3, 1>(a, s);
-        case 12: return launch_v<T, TERMS, EPI, 64, 64, 2, 2, 3, 2>(a, s);
-        case 13: return launch_v<T, TERMS, EPI, 64, 64, 2, 2, 3, 3>(a, s);
-        case 14: return launch_v<T, TERMS, EPI, 64, 64, 2, 2, 3, 4>(a, s);
-        case 15: return launch_v<T, TERMS, EPI, 64, 64, 2, 2, 3, 5>(a, s);
-        case 16: return launch_v<T, TERMS, EPI, 128, 128, 2, 4, 2, 1>(a, s);
-        case 17: return launch_v<T, TERMS, EPI, 128, 128, 2, 4, 2, 2>(a, s);
-#endif
+        case GEMM_ST_64: return launch_v<T, TERMS, EPI, 64, 64, 2, 2, 3, 2>(a, s);    // ring of 3: 96 KiB (3-term formats), one workgroup per CU; 4 + 2 waves
+        case GEMM_ST_64X2: return launch_v<T, TERMS, EPI, 64, 64, 2, 2, 2, 4>(a, s);  // ring of 2: 64 KiB, two workgroups per CU; 4 + 4 waves
+        case GEMM_ST_128: return launch_v<T, TERMS, EPI, 128, 128, 2, 4, 2, 8>(a, s); // ring of 2: 128 KiB; 8 + 8 waves
     }
     return hipErrorInvalidValue;
 }

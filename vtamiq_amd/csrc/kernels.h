@@ -25,44 +25,9 @@ inline bool num_valid(Num n) {
     return (n.terms == 1 || n.terms == 3 || (n.terms == 2 && n.f16 == 1)) && (n.f16 == 0 || n.f16 == 1);
 }
 
-// ---- Every build switch of csrc/, in one place.  The PRODUCT library (python -m vtamiq_amd.build) defines NONE of them: the
-// code under them is measurement or experiment code that no shipped kernel contains (tests/test_layout.py greps the shipped objects).  Builds with
-// switches are made by tools/build_abl.sh NAME "-D..." into tools/_abl/NAME.so and loaded through VTQ_LIB_PATH.
-//   VTQ_WITH_FP8          the fp8 experiment (include/vtamiq_hip_fp8.h; python -m vtamiq_amd.build --fp8): e4m3 GEMM instantiations, fp8 entry points
-//   VTQ_MEASURE           makes VTQ_MEASURE_ENV getenv: VTQ_GEMM_FLAGS / _CUS / _CG / _SCHED / _STAGGER, VTQ_ATTN_VARIANT, VTQ_ATTN_LDS_PAD (A/B runs)
-//   VTQ_GEMM_DIAG         gemm.hip: s_memtime / s_memrealtime stamps around K loops, kernel and epilogue steps; shadow-VALU filler (profiles/r03_clock.txt)
-//   VTQ_EPI_ABL=1..4      gemm.hip epilogue ablations: 1 no GELU arithmetic, 2 no copy-out, 3 no global stores, 4 no LDS staging (r03_gemm_epilogue_ablation.txt)
-//   VTQ_EPI_ORDER=1|2     gemm.hip: both wave groups copy first / convert first in an epilogue interval (the plane-alternating form only)
-//   VTQ_RESID_DEFER=1     gemm.hip: residual epilogue with the copy-out's LDS reads issued before the next chunk's conversion (equal: profiles/r05_epilogue_balanced.txt)
-//   VTQ_EPI_BALANCED=0    gemm.hip: the plane-alternating passes of the two-plane bias / GELU epilogue (rounds 2 - 4) instead of the balanced ones (profiles/r05_epilogue_balanced.txt)
-//   VTQ_RESID_PLANES      gemm.hip: pricing build of a LayerNorm fold's producer side (profiles/r03_ln_fold_price.txt)
-//   VTQ_GEMM_ST_EXPLORE   gemm_st.hip: extra tile shapes and the load-only / compute-only modes of tools/st_bench.py (profiles/r05_gemm_tile_shapes.txt)
-//   VTQ_RL_ABL, VTQ_RL_MM, VTQ_RL_PRE, VTQ_RL_POST   gemm_rowln.hip: K-loop ablations, MFMA statement form, waits (profiles/r04_rowln_anatomy.txt)
-//   VTQ_ATTN_DIAG         attention.hip: per-wave phase stamps (profiles/r03_attention_anatomy.txt)
-//   VTQ_ATTN_NO_VMASK     attention.hip: without the zeroing of masked keys' V rows (profiles/r04_attention_vmask_ab.txt)
-//   VTQ_SW_NOFILL / NOMFMA / NOSTORE / NOQ / NODMA / PAIRED / DIST / HALFREADS   attention.hip pipelined kernel: skeleton ablations, read-ahead distance
-//   VTQ_SW_QPF=0 / VTQ_SW_EARLY_WRITE=0   attention.hip pipelined kernel: without the L2 prefetch of the next block's Q / with the finished block's output written mid-iteration (profiles/r06_attention_loop.txt)
-//   VTQ_SW_PRIO=1|2|3     attention.hip: s_setprio alternating between the two waves of a SIMD per phase / per fragment group / static for waves 4-7 (profiles/r05_attention_prio.txt)
-//   VTQ_SW_SEAM_STAGGER=n attention.hip: every second workgroup of an XCD starts n us late (profiles/r05_attention_seams.txt)
-//   VTQ_LIBM_ERF          dev_common.h: erff() instead of the fitted exact-erf GELU (accuracy cross-check)
-//   VTQ_GELU_PACKED=1     dev_common.h: the GELU polynomial as v_pk_fma_f32 (same bits, 30 instead of 44 instructions per 4 values; equal time: profiles/r05_gelu_packed.txt)
-//
-// Measurement knobs.  The PRODUCT library reads no environment variable and executes no measurement branch: every knob below exists only
-// in builds with -DVTQ_MEASURE (tools/build_abl.sh), where VTQ_MEASURE_ENV is getenv; in the shipped build it is a null constant (the
-// variable names do not even appear in the objects: tests/test_layout.py greps for them) and GemmArgs::flags is ignored by the kernels.
-#ifdef VTQ_MEASURE
-#define VTQ_MEASURE_ENV(name) getenv(name)
-#else
-#define VTQ_MEASURE_ENV(name) ((const char*)nullptr)
-#endif
-
-// GemmArgs::flags, measurement knobs (-DVTQ_MEASURE builds: environment VTQ_GEMM_FLAGS, read once per process)
-enum { GEMM_FLAG_WRAP_ROWS = 1,     // every tile writes the rows of row panel 0: no HBM write stream (timing experiments only)
-       GEMM_FLAG_NO_CHAIN = 2,      // no DMA chaining across a workgroup's consecutive tiles
-       GEMM_FLAG_DYNAMIC = 4,       // one schedule entry per workgroup, as many workgroups as entries (hardware dispatch order
-                                    // instead of the persistent lists): the round-1 launch form, for A/B timing
-       GEMM_FLAG_NO_EPILOGUE = 8,   // skip the epilogue (timing experiments only: output is not written)
-       GEMM_FLAG_WRAP_LOADS = 16 }; // every tile loads the first two A and W panels: operands always hit L2 (timing experiments only)
+// ---- The one build switch of csrc/: VTQ_WITH_FP8, the fp8 experiment (include/vtamiq_hip_fp8.h; python -m vtamiq_amd.build --fp8): e4m3 GEMM
+// instantiations and the fp8 entry points.  The product library (python -m vtamiq_amd.build) is built without it.  Neither library reads
+// an environment variable (tests/test_layout.py).
 
 // Where the sequences live in the row-major activation buffers: sequence s starts at row s*pitch + (s/per)*gap -- `per`
 // sequences per part-batch, each part-batch padded by `gap` rows to a multiple of 256 (the GEMM tile height).
@@ -96,18 +61,7 @@ struct GemmArgs {
     Fp8Obs obs;                                   // fp8 GELU form only (the one GEMM epilogue that writes e4m3 bytes)
     const int* sched;                             // set by launch_gemm: per-workgroup tile lists (gemm.hip build_schedule)
     int st_grid;                                  // set by launch_gemm_st: the XCD grid of the small-tile kernels, rows * 16 + columns (gemm_st.hip)
-    int flags;                                    // set by launch_gemm: GEMM_FLAG_* (-DVTQ_MEASURE builds; the product kernels read 0, gemm_flags())
-    // diagnostic builds (-DVTQ_GEMM_DIAG, tools/build_abl.sh) only; set by launch_gemm from gemm_set_diag, never read otherwise:
-    unsigned long long* diag;                     //   per workgroup 8 words: K-loop and whole-kernel s_memtime / s_memrealtime sums
-    int shadow;                                   //   dummy v_fma_f32 issued in every load phase (x8): the price of VALU work beside the partner's MFMAs
-    float* row_stats;                             //   -DVTQ_RESID_PLANES pricing build only: per row and column tile (mean, M2) of the new residual row
 };
-
-#ifdef VTQ_MEASURE
-__host__ __device__ inline int gemm_flags(const GemmArgs& a) { return a.flags; }
-#else
-__host__ __device__ constexpr int gemm_flags(const GemmArgs&) { return 0; }
-#endif
 
 hipError_t launch_gemm(const GemmArgs& a, Num num, int epilogue, hipStream_t s);
 // Tile shape of a GEMM launch.  launch_gemm picks one from (M, N, K, operand format) by gemm_tile_rule -- a pure speed choice: every
@@ -132,14 +86,10 @@ struct RowLnArgs {
     void* out; int64_t o_plane;                   // planes [M, 768] of the normalised rows
 };
 hipError_t launch_gemm_rowln(const RowLnArgs& a, Num num, hipStream_t s);
-// diagnostic builds: stamp buffer (256 workgroups x 8 words, device memory, or NULL) and shadow-VALU count of the following launches
 int attention_rule(int nseq, int S_pad, int H, int terms, int cus);    // host-only: the form launch_attention picks: 0 four-wave kernel, 1 pipelined kernel, 2 split
 void attention_set_variant(int v);               // test / measurement hook: -1 the rule, 0 / 1 / 2 as above
 void attention_set_map(int m);                   // measurement hook: block walk of the pipelined kernel, 0 = XCD-strided (default), 1 = contiguous / paired (round 3)
 void attention_set_cus(int cus);                 // measurement hook: size the persistent attention grid for `cus` CUs (0 = the device's)
-unsigned long long* gemm_diag_buffer();         // the buffer of gemm_set_diag (attention's diagnostic build shares it)
-void gemm_set_diag(unsigned long long* buf, int shadow);
-bool gemm_is_diag_build();
 // Build and upload (async on s) the persistent tile schedule of an (M, N, K) GEMM with wpl weight planes on the current device, if
 // it is not cached yet: called by the engine before the first launch of a forward so that launch_gemm itself never allocates
 hipError_t gemm_prepare(int M, int N, int K, int wpl, hipStream_t s);
@@ -258,7 +208,7 @@ hipError_t launch_repeat_mean(const float* q, double* out, int R, int N, hipStre
 hipError_t launch_rank_metrics(const double* a, const double* b, int N, int normalize, double* aa, double* bb, double* ra, double* rb,
                                long long* counts, double* out, hipStream_t s);
 
-#if defined(__HIPCC__) && defined(VTQ_DEV_COMMON)
+#if defined(__HIPCC__) && defined(VTAMIQ_DEV_COMMON_H)
 // 4 consecutive values of one row -> the plane sink (device side; dev_common.h must be included first)
 __device__ __forceinline__ void plane_store4(const PlaneOut& o, int64_t row, int col, float a, float b, float c, float d) {
     if (!o.p) return;
