@@ -393,6 +393,8 @@ __global__ __launch_bounds__(256) void attention_kernel(const T* __restrict__ qk
 // =====================================================================================================================
 // Helpers of the software-pipelined kernel below.
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+typedef short v4i16_t __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(3))) v4i16_t LdsV4i16;
 __device__ __forceinline__ void pp_barrier() {
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier();
@@ -778,8 +780,17 @@ __global__ __launch_bounds__(512) void attention_sw_kernel(const T* __restrict__
     };
     auto issue_v = [&](auto gc, const uint32_t (&vaddr)[2]) __attribute__((always_inline)) {       // PV group g = step * 2 + d
         constexpr int g = decltype(gc)::value, sl = (g + 8) % NS, step = g >> 1, d = g & 1, off = (step >> 1) * 4096 + (step & 1) * 2048;
-        PP_DS_TR(fr.va0[sl], vaddr[d], off);
-        PP_DS_TR(fr.va1[sl], vaddr[d], off + 1024);
+        if constexpr (NSPLIT == 1) {
+            // single plane: hipcc copies an asm destination here before its counted lgkmcnt (a v_mov of a read in flight, found by
+            // tests/asm_hazards.py), so these reads are the builtin hipcc counts itself; the empty "memory" asm keeps them below the
+            // barrier the ring slot was published by (s_barrier does not order memory for the compiler)
+            asm volatile("" ::: "memory");
+            fr.va0[sl] = __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((LdsV4i16*)(uintptr_t)(vaddr[d] + off)));
+            fr.va1[sl] = __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((LdsV4i16*)(uintptr_t)(vaddr[d] + off + 1024)));
+        } else {
+            PP_DS_TR(fr.va0[sl], vaddr[d], off);
+            PP_DS_TR(fr.va1[sl], vaddr[d], off + 1024);
+        }
         if constexpr (NSPLIT == 3) {
             PP_DS_TR(fr.vl0[sl], vaddr[d], off + TB);
             PP_DS_TR(fr.vl1[sl], vaddr[d], off + TB + 1024);
