@@ -73,22 +73,43 @@ struct Slot {
     bool loaded = false;
 };
 
+// One linear layer y = x W^T + b as the GEMM and skinny kernels read it: weight planes [N][K] (16-bit, `plane` elements from hi to
+// lo; fp8 mode: e4m3 rows + per-output-channel inverse scales) and an fp32 bias.  K is the row pitch of the packed planes, i.e. the
+// kernel's K: a tensor with shorter rows is zero-padded to it.
+struct Lin { void* w = nullptr; int64_t plane = 0; float* wscale = nullptr; float* b = nullptr; int N = 0, K = 0; };
+// rows [row0, row0 + n) of l as a layer of its own (esz: bytes per weight element)
+Lin lin_rows(const Lin& l, int64_t row0, int64_t n, int esz = 2) {
+    return Lin{(char*)l.w + row0 * l.K * esz, l.plane, l.wscale ? l.wscale + row0 : nullptr, l.b + row0, (int)n, l.K};
+}
+// Activation planes [rows][ld] of lnbuf / big / the tail and head buffers (`plane` elements from hi to lo)
+struct View { void* p = nullptr; int64_t plane = 0; int ld = 0; };
+
+// out = A W^T + b over M rows: the operands of one launch_gemm; epilogue-specific fields (gamma, x, row_map ...) are the caller's
+GemmArgs gemm_args(View a, const Lin& l, int M, View out = View{}, float ascale_inv = 0.0f) {
+    GemmArgs g{};
+    g.A = a.p; g.a_plane = a.plane; g.lda = a.ld; g.W = l.w; g.w_plane = l.plane; g.M = M; g.N = l.N; g.K = l.K; g.bias = l.b;
+    g.out = out.p; g.o_plane = out.plane; g.ldo = out.ld; g.wscale = l.wscale; g.ascale_inv = ascale_inv;
+    return g;
+}
+// the same for one skinny stage on R rows (CLS tail, DiffNet head); ya_planes: planes of its 16-bit output, if it writes one
+SkinnyArgs skinny_args(View x, const Lin& l, int R, int ya_planes) {
+    SkinnyArgs a{};
+    a.xa = x.p; a.xa_plane = x.plane; a.ldx = x.ld; a.W = l.w; a.w_plane = l.plane; a.R = R; a.N = l.N; a.K = l.K; a.bias = l.b;
+    a.ya_planes = ya_planes;
+    return a;
+}
+
 struct Layer {
-    void *wqkv, *wo, *w1, *w2;                 // 16-bit planes / e4m3 rows
-    int64_t pqkv, po, p1, p2;                  // plane strides
-    float *sqkv, *so, *s1, *s2;                // fp8 mode: per-output-channel inverse weight scales
-    float *bqkv, *bo, *b1, *b2, *ln1w, *ln1b, *ln2w, *ln2b, *g1, *g2;
+    Lin qkv, out, fc1, fc2;                    // qkv: query, key, value rows stacked ([3H][H])
+    float *ln1w = nullptr, *ln1b = nullptr, *ln2w = nullptr, *ln2b = nullptr, *g1 = nullptr, *g2 = nullptr;
     // Adapter pair 0 (transformer.py:177-194, 260-269): site 0 after attention, site 1 after the MLP.  down: [Hq_pad, H] planes
     // (rows >= H/4 zero), up: [H, Hq_pad] planes (K zero-padded); Hq_pad = H/4 rounded up to the GEMM tile (256)
-    void *ad_dn[2], *ad_up[2];
-    int64_t pad_dn[2], pad_up[2];
-    float *ad_bdn[2], *ad_bup[2];
+    Lin ad_dn[2], ad_up[2];
 };
-// One linear stage of the DiffNet head as the skinny-MFMA kernel reads it: fp16 hi/lo planes [2][ceil16(N)][Kp] (Kp = K padded
-// to the 32-deep k-step with zeros) + fp32 bias.  The head always runs the 3-term fp16 form, whatever the encoder's precision.
-struct HeadLin { void* wp = nullptr; int64_t plane = 0; int N = 0, K = 0, Kp = 0; const float* b = nullptr; };
-struct Rcab { float *slope, *w, *b, *wd, *bd, *wu, *bu, *wcat, *bcat; HeadLin cat, up; };   // wcat/bcat: [Wc ; Wd Wc], folded at load time
-struct Rg { std::vector<Rcab> rcabs; float *w, *b; HeadLin tail; };
+// The DiffNet head's linear stages are Lin too: fp16 hi/lo planes [2][ceil16(N)][K] (K padded to the skinny kernel's 32-deep k-step
+// with zeros), packed by pack_head.  The head always runs the 3-term fp16 form, whatever the encoder's precision.
+struct Rcab { float *slope, *w, *b, *wd, *bd, *wu, *bu, *wcat, *bcat; Lin cat, up; };   // wcat/bcat: [Wc ; Wd Wc], folded at load time
+struct Rg { std::vector<Rcab> rcabs; float *w, *b; Lin tail; };
 
 }  // namespace
 
@@ -103,25 +124,22 @@ struct vtq_engine {
     bool fp8_static = false, fp8_calibrated = false, calibrating = false;
     bool fp8_installed = false;        //   the current scales came from vtq_fp8_set_scales: a weight reload keeps them
     float* amax_slot = nullptr;        //   device word the producers report max |value| into during a calibration forward
-    float* spatch = nullptr;           //   inverse weight scales of the patch embedding
     int64_t PDp = 0;                   // patch_dim rounded up to the GEMM's K granule (row pitch of the packed patches / weight)
     int64_t Hqp = 0;                   // adapters: H / 4 rounded up to the GEMM tile (N of the down projection, K of the up projection)
     int H = 0, Mdim = 0, T = 0;
     std::vector<void*> allocs;
     std::unordered_map<std::string, Slot> slots;
     // ViT
-    void* wpatch = nullptr; int64_t ppatch = 0;
-    float *bpatch = nullptr, *cls = nullptr, *extra = nullptr, *pos_table = nullptr, *scale_table = nullptr, *encw = nullptr,
-          *encb = nullptr;
+    Lin patch;                         // patch embedding: [H][PDp]
+    float *cls = nullptr, *extra = nullptr, *pos_table = nullptr, *scale_table = nullptr, *encw = nullptr, *encb = nullptr;
     std::vector<Layer> layers;
     // head
     float* diff_gamma = nullptr;
     std::vector<Rg> rgs;
     float *qdw = nullptr, *qdb = nullptr, *p1w = nullptr, *p1b = nullptr, *p2a = nullptr, *p4w = nullptr, *p4b = nullptr;
-    HeadLin qd, p1, p4;
+    Lin qd, p1, p4;
     // workspace
     int capB = 0, capN = 0;
-    int64_t rows_alloc = 0;
     float* x = nullptr;
     void *lnbuf = nullptr, *big = nullptr;
     int64_t ln_plane = 0, big_plane = 0;
@@ -168,19 +186,30 @@ int add_f32(vtq_engine* e, const std::string& name, float** p, int64_t numel) {
     return 0;
 }
 
-// planes (or e4m3 rows) for a [rows_total, K] weight; sub-slot `name` covers rows [row0, row0 + rows)
-int add_split(vtq_engine* e, const std::string& name, void* base, int64_t plane, int64_t row0, int64_t rows, int64_t K,
-              float* scale_base = nullptr, int64_t Kp = 0) {
-    if (Kp == 0) Kp = K;
-    Slot s; s.dst = (char*)base + row0 * Kp * (e->fp8 ? 1 : 2); s.numel = rows * K; s.split = true; s.plane = plane; s.K = K; s.Kp = Kp;
-    s.scale = scale_base ? scale_base + row0 : nullptr;
-    e->slots[name] = s;
+// Allocates one linear layer of operand format `num`: [rows][K] weight planes (rows: N, or more where the kernel reads whole tiles),
+// an fp32 bias of its own unless `bias` names one, and for e4m3 weights the inverse scales.  zero: the padding no load slot covers
+// is read by the kernels and must be zero.
+int add_lin(vtq_engine* e, Lin& l, Num num, int64_t N, int64_t K, bool zero = false, float* bias = nullptr, int64_t rows = 0) {
+    if (rows == 0) rows = N;
+    l.N = (int)N; l.K = (int)K; l.plane = rows * K; l.b = bias;
+    const size_t wbytes = (size_t)l.plane * 2 * num.wpl();
+    if (dev_alloc(e, &l.w, wbytes) || (!bias && dev_alloc(e, (void**)&l.b, rows * sizeof(float))) ||
+        (num.f16 == 2 && dev_alloc(e, (void**)&l.wscale, rows * sizeof(float))))
+        return 1;
+    if (zero) {
+        HIP_TRY(hipMemset(l.w, 0, wbytes));
+        if (!bias) HIP_TRY(hipMemset(l.b, 0, rows * sizeof(float)));
+    }
     return 0;
 }
 
-int alloc_planes(vtq_engine* e, void** p, int64_t* plane, int64_t numel) {
-    *plane = numel;
-    return dev_alloc(e, p, (size_t)numel * 2 * e->wpl);
+// load slots `name`.weight ([rows, K] fp32; K < l.K: zero-padded to the planes' row pitch) and `name`.bias for rows [row0, row0 + rows) of l
+void lin_slots(vtq_engine* e, const Lin& l, const std::string& name, int64_t rows, int64_t K, int64_t row0 = 0) {
+    const Lin r = lin_rows(l, row0, rows, e->fp8 ? 1 : 2);
+    Slot w; w.dst = r.w; w.numel = rows * K; w.split = true; w.plane = r.plane; w.scale = r.wscale; w.K = K; w.Kp = r.K;
+    e->slots[name + ".weight"] = w;
+    Slot b; b.dst = r.b; b.numel = rows;
+    e->slots[name + ".bias"] = b;
 }
 
 int build(vtq_engine* e) {
@@ -192,10 +221,8 @@ int build(vtq_engine* e) {
     // the patch-embedding GEMM runs on K padded to 256 (two K tiles of every operand format): 768 as is, ViT-B/8's 192 -> 256
     e->PDp = round_up(PD, 256);
     e->Hqp = round_up(H / 4, 256);
-    if (alloc_planes(e, &e->wpatch, &e->ppatch, H * e->PDp)) return 1;
-    if (e->fp8 && dev_alloc(e, (void**)&e->spatch, H * sizeof(float))) return 1;
-    add_split(e, emb + "patch_embeddings.weight", e->wpatch, e->ppatch, 0, H, PD, e->spatch, e->PDp);
-    if (add_f32(e, emb + "patch_embeddings.bias", &e->bpatch, H)) return 1;
+    if (add_lin(e, e->patch, e->lin, H, e->PDp)) return 1;
+    lin_slots(e, e->patch, emb + "patch_embeddings", H, PD);
     if (add_f32(e, emb + "positional_embeddings.positional_embeddings", &e->pos_table, ((int64_t)c.pos_grid * c.pos_grid + 1) * H))
         return 1;
     if (c.num_scales > 1 && add_f32(e, emb + "scale_embeddings.scale_embeddings", &e->scale_table, ((int64_t)c.num_scales + 1) * H))
@@ -205,47 +232,31 @@ int build(vtq_engine* e) {
     e->layers.resize(c.num_layers);
     for (int i = 0; i < c.num_layers; ++i) {
         Layer& L = e->layers[i];
-        memset(&L, 0, sizeof L);
         const std::string p = enc + "layers." + std::to_string(i) + ".";
-        if (alloc_planes(e, &L.wqkv, &L.pqkv, 3 * H * H) || alloc_planes(e, &L.wo, &L.po, H * H) ||
-            alloc_planes(e, &L.w1, &L.p1, M * H) || alloc_planes(e, &L.w2, &L.p2, H * M))
-            return 1;
-        if (dev_alloc(e, (void**)&L.bqkv, 3 * H * sizeof(float))) return 1;
-        if (e->fp8 && (dev_alloc(e, (void**)&L.sqkv, 3 * H * sizeof(float)) || dev_alloc(e, (void**)&L.so, H * sizeof(float)) ||
-                       dev_alloc(e, (void**)&L.s1, M * sizeof(float)) || dev_alloc(e, (void**)&L.s2, H * sizeof(float))))
+        if (add_lin(e, L.qkv, e->lin, 3 * H, H) || add_lin(e, L.out, e->lin, H, H) || add_lin(e, L.fc1, e->lin, M, H) ||
+            add_lin(e, L.fc2, e->lin, H, M))
             return 1;
         const char* qkvn[3] = {"query", "key", "value"};
-        for (int j = 0; j < 3; ++j) {
-            add_split(e, p + "attn." + qkvn[j] + ".weight", L.wqkv, L.pqkv, j * H, H, H, L.sqkv);
-            Slot s; s.dst = L.bqkv + j * H; s.numel = H;
-            e->slots[p + "attn." + qkvn[j] + ".bias"] = s;
-        }
+        for (int j = 0; j < 3; ++j) lin_slots(e, L.qkv, p + "attn." + qkvn[j], H, H, j * H);
         if (e->att.terms == 3) {       // 3-term attention takes Q in log2 units: (x W_q + b_q) * kQLog2Scale, folded into W_q and b_q
             e->slots[p + "attn.query.weight"].mul = kQLog2Scale;
             e->slots[p + "attn.query.bias"].mul = kQLog2Scale;
         }
-        add_split(e, p + "attn.out.weight", L.wo, L.po, 0, H, H, L.so);
-        add_split(e, p + "ffn.fc1.weight", L.w1, L.p1, 0, M, H, L.s1);
-        add_split(e, p + "ffn.fc2.weight", L.w2, L.p2, 0, H, M, L.s2);
-        if (add_f32(e, p + "attn.out.bias", &L.bo, H) || add_f32(e, p + "ffn.fc1.bias", &L.b1, M) ||
-            add_f32(e, p + "ffn.fc2.bias", &L.b2, H) || add_f32(e, p + "attention_norm.weight", &L.ln1w, H) ||
-            add_f32(e, p + "attention_norm.bias", &L.ln1b, H) || add_f32(e, p + "ffn_norm.weight", &L.ln2w, H) ||
-            add_f32(e, p + "ffn_norm.bias", &L.ln2b, H))
+        lin_slots(e, L.out, p + "attn.out", H, H);
+        lin_slots(e, L.fc1, p + "ffn.fc1", M, H);
+        lin_slots(e, L.fc2, p + "ffn.fc2", H, M);
+        if (add_f32(e, p + "attention_norm.weight", &L.ln1w, H) || add_f32(e, p + "attention_norm.bias", &L.ln1b, H) ||
+            add_f32(e, p + "ffn_norm.weight", &L.ln2w, H) || add_f32(e, p + "ffn_norm.bias", &L.ln2b, H))
             return 1;
         if (c.use_layer_scale && (add_f32(e, p + "ls1.gamma", &L.g1, H) || add_f32(e, p + "ls2.gamma", &L.g2, H))) return 1;
         if (c.num_adapters > 0) {
             const int64_t Hq = H / 4, Hqp = e->Hqp;
             for (int site = 0; site < 2; ++site) {
                 const std::string q = p + "adapter" + std::to_string(site + 1) + ".adapter.";
-                if (alloc_planes(e, &L.ad_dn[site], &L.pad_dn[site], Hqp * H) || alloc_planes(e, &L.ad_up[site], &L.pad_up[site], H * Hqp) ||
-                    dev_alloc(e, (void**)&L.ad_bdn[site], Hqp * sizeof(float)))
-                    return 1;
-                HIP_TRY(hipMemset(L.ad_dn[site], 0, (size_t)Hqp * H * 2 * e->wpl));      // rows >= Hq: zero weights, zero bias -> gelu(0) = 0
-                HIP_TRY(hipMemset(L.ad_bdn[site], 0, Hqp * sizeof(float)));
-                add_split(e, q + "0.weight", L.ad_dn[site], L.pad_dn[site], 0, Hq, H);
-                { Slot sb; sb.dst = L.ad_bdn[site]; sb.numel = Hq; e->slots[q + "0.bias"] = sb; }
-                add_split(e, q + "2.weight", L.ad_up[site], L.pad_up[site], 0, H, Hq, nullptr, Hqp);
-                if (add_f32(e, q + "2.bias", &L.ad_bup[site], H)) return 1;
+                // down: rows >= Hq keep zero weights and a zero bias -> gelu(0) = 0
+                if (add_lin(e, L.ad_dn[site], e->lin, Hqp, H, true) || add_lin(e, L.ad_up[site], e->lin, H, Hqp)) return 1;
+                lin_slots(e, L.ad_dn[site], q + "0", Hq, H);
+                lin_slots(e, L.ad_up[site], q + "2", H, Hq);
             }
             for (int a = 3; a <= 2 * c.num_adapters; ++a) {          // pairs >= 1 exist in the state_dict; the forward never reads them
                 const std::string q = p + "adapter" + std::to_string(a) + ".adapter.";
@@ -283,12 +294,7 @@ int build(vtq_engine* e) {
         add_f32(e, "q_predictor.4.bias", &e->p4b, 1))
         return 1;
     // fp16 hi/lo planes of every head matrix (filled by pack_head after each weight load)
-    auto head_lin = [&](HeadLin& L, int N, int K, const float* bias) {
-        L.N = N; L.K = K; L.Kp = (int)round_up(K, 32); L.b = bias;
-        L.plane = round_up(N, 16) * L.Kp;
-        if (dev_alloc(e, &L.wp, (size_t)L.plane * 2 * 2)) return 1;
-        return hipMemset(L.wp, 0, (size_t)L.plane * 2 * 2) == hipSuccess ? 0 : fail("hipMemset failed");
-    };
+    auto head_lin = [&](Lin& L, int N, int K, float* bias) { return add_lin(e, L, Num{1, 3}, N, round_up(K, 32), true, bias, round_up(N, 16)); };
     if (c.calibrate) {
         for (auto& R : e->rgs) {
             for (auto& r : R.rcabs)
@@ -304,24 +310,26 @@ int build(vtq_engine* e) {
 
 // fp32 matrices of the head -> the fp16 planes the skinny kernel streams (after the CA fold); enqueued on s
 int pack_head(vtq_engine* e, hipStream_t s) {
-    auto pack = [&](const HeadLin& L, const float* W) {
-        HIP_TRY(launch_rows_to_planes(W, L.K, nullptr, L.wp, L.plane, L.Kp, L.N, L.K, 1, 2, s));
+    auto pack = [&](const Lin& L, const float* W, int K) {       // K: row length of W (L.K is its 32-padded pitch)
+        HIP_TRY(launch_rows_to_planes(W, K, nullptr, L.w, L.plane, L.K, L.N, K, 1, 2, s));
         return 0;
     };
+    const int H = e->H, hid = e->cfg.ca_hidden;
     for (auto& R : e->rgs) {
         for (auto& r : R.rcabs) {
-            HIP_TRY(launch_fold_ca(r.w, r.b, r.wd, r.bd, r.wcat, r.bcat, e->H, e->cfg.ca_hidden, s));
-            if (pack(r.cat, r.wcat) || pack(r.up, r.wu)) return 1;
+            HIP_TRY(launch_fold_ca(r.w, r.b, r.wd, r.bd, r.wcat, r.bcat, H, hid, s));
+            if (pack(r.cat, r.wcat, H) || pack(r.up, r.wu, hid)) return 1;
         }
-        if (pack(R.tail, R.w)) return 1;
+        if (pack(R.tail, R.w, H)) return 1;
     }
-    if (e->cfg.calibrate && pack(e->qd, e->qdw)) return 1;
-    return pack(e->p1, e->p1w) || pack(e->p4, e->p4w);
+    if (e->cfg.calibrate && pack(e->qd, e->qdw, H)) return 1;
+    return pack(e->p1, e->p1w, H) || pack(e->p4, e->p4w, H / 4);
 }
 
 struct Geometry {
     int S, S_pad, nseq;          // S_pad: row pitch of a sequence (= S: sequences are packed back to back)
     int64_t M_pad, P_pad, rows_alloc;
+    int64_t R_pad;               // rows of the skinny-stage plane buffers (CLS tail, head): one per sequence, padded to the kernel's 64
     SeqMap sm;
 };
 
@@ -337,31 +345,43 @@ Geometry geometry(const vtq_engine* e, int B, int N, int nimg = 2) {
     g.M_pad = round_up((int64_t)g.nseq * g.S_pad, 256);
     g.P_pad = round_up((int64_t)nimg * B * N, 256);
     g.rows_alloc = (g.M_pad > g.P_pad ? g.M_pad : g.P_pad) + 128;   // +128: attention over-read slack behind the last sequence
+    g.R_pad = round_up(g.nseq, 64);
     g.sm = SeqMap{g.S_pad, g.nseq, (int)(g.M_pad - (int64_t)g.nseq * g.S_pad)};
     return g;
 }
 
-// capacity for up to `B` sequence pairs
-int64_t capacity_rows(const vtq_engine* e, int B, int N) {
-    const int64_t seq_rows = round_up((int64_t)2 * B * (N + e->T), 256);
-    const int64_t patch_rows = round_up((int64_t)2 * B * N, 256);
-    return (seq_rows > patch_rows ? seq_rows : patch_rows) + 128;
-}
+// One workspace buffer: the engine member it fills, its `planes` planes of `elems` elements of `esz` bytes (the plane stride goes
+// to *stride where the engine keeps one), and whether reserve() zero-fills it.
+struct WsBuf { void** ptr; int64_t* stride; int64_t elems; int esz, planes; bool zero; };
 
-size_t workspace_bytes(const vtq_engine* e, int B, int N) {
-    const int64_t rows = capacity_rows(e, B, N), P_pad = round_up((int64_t)2 * B * N, 256);
-    const int64_t H = e->H, Wmax = (3 * H > e->Mdim ? 3 * H : e->Mdim);
-    size_t b = 0;
-    b += (size_t)rows * H * 4;                            // residual stream fp32
-    b += (size_t)rows * H * 2 * e->apl;                   // LN / attention output planes
-    b += (size_t)rows * Wmax * 2 * e->apl;                // qkv | mlp hidden | packed patches planes
-    b += (size_t)P_pad * 4 * 3;                           // pos/scale indices, row map
-    b += (size_t)2 * B * H * 4 * 6;                       // head ping-pong buffers (pairwise: 2 scores per item)
-    b += (size_t)2 * B * 3 * H * 4;                       // CLS-only last-layer rows (fp32)
-    const size_t ra = (size_t)round_up((int64_t)2 * B, 64);
-    b += ra * (2 * H + e->hidp + H / 4) * 2 * 2;          // head planes (fp16 hi/lo)
-    b += ra * (H + e->Mdim) * 2 * e->apl;                 // CLS-tail planes
-    return b;
+// THE description of the workspace for a capacity of B sequence pairs (2B sequences) of N patches: reserve() allocates it,
+// vtq_workspace_bytes sums it.  Zero-filled are the buffers of which a kernel reads more than a forward writes: padded rows of x /
+// lnbuf / big are computed on (never consumed) and must not breed NaNs; rows >= R and the K-padding columns of the skinny stages'
+// planes are read by their MFMAs.
+std::vector<WsBuf> workspace(vtq_engine* e, int B, int N) {
+    const Geometry g = geometry(e, B, N);
+    const int64_t H = e->H, Md = e->Mdim, Wmax = (3 * H > Md ? 3 * H : Md), rows = g.rows_alloc, R = g.R_pad;
+    const int apl = e->apl;
+    std::vector<WsBuf> w = {
+        {(void**)&e->x, nullptr, rows * H, 4, 1, true},                       // residual stream fp32
+        {&e->lnbuf, &e->ln_plane, rows * H, 2, apl, true},                    // LayerNorm / attention output planes
+        {&e->big, &e->big_plane, rows * Wmax, 2, apl, true},                  // qkv | mlp hidden | packed patches planes
+        {(void**)&e->pidx, nullptr, g.P_pad, 4, 1, false},                    // pos / scale indices, row map
+        {(void**)&e->sidx, nullptr, g.P_pad, 4, 1, false},
+        {(void**)&e->row_map, nullptr, g.P_pad, 4, 1, false},
+        {(void**)&e->hhid, nullptr, g.nseq * H, 4, 1, false},                 // head fp32 rows (pairwise: 2 scores per item)
+        {(void**)&e->xcls, nullptr, g.nseq * H, 4, 1, false},                 // CLS-only last layer (fp32 rows)
+        {(void**)&e->lncls, nullptr, g.nseq * H, 4, 1, false},
+        {(void**)&e->qcls, nullptr, g.nseq * H, 4, 1, false},
+        {&e->hp[0], &e->hp_plane, R * H, 2, 2, true},                         // head planes (fp16 hi/lo)
+        {&e->hp[1], &e->hp_plane, R * H, 2, 2, true},
+        {&e->ht, &e->ht_plane, R * e->hidp, 2, 2, true},
+        {&e->hq, &e->hq_plane, R * (H / 4), 2, 2, true},
+        {&e->tl, &e->tl_plane, R * H, 2, apl, true},                          // CLS-tail planes (encoder format)
+        {&e->th, &e->th_plane, R * Md, 2, apl, true},
+    };
+    for (float*& hb : e->hb) w.push_back({(void**)&hb, nullptr, g.nseq * H, 4, 1, false});   // head ping-pong rows
+    return w;
 }
 
 int reserve(vtq_engine* e, int B, int N) {
@@ -371,45 +391,14 @@ int reserve(vtq_engine* e, int B, int N) {
     for (void* p : e->ws_allocs) (void)hipFree(p);
     e->ws_allocs.clear();
     e->x = nullptr;
-    struct { int64_t rows_alloc, P_pad; } g{capacity_rows(e, nB, nN), round_up((int64_t)2 * nB * nN, 256)};
-    const int64_t H = e->H, Wmax = (3 * H > e->Mdim ? 3 * H : e->Mdim);
-    e->rows_alloc = g.rows_alloc;
-    e->ln_plane = g.rows_alloc * H;
-    e->big_plane = g.rows_alloc * Wmax;
-    if (dev_alloc(e, (void**)&e->x, (size_t)g.rows_alloc * H * 4, true) ||
-        dev_alloc(e, &e->lnbuf, (size_t)e->ln_plane * 2 * e->apl, true) ||
-        dev_alloc(e, &e->big, (size_t)e->big_plane * 2 * e->apl, true) ||
-        dev_alloc(e, (void**)&e->pidx, (size_t)g.P_pad * 4, true) || dev_alloc(e, (void**)&e->sidx, (size_t)g.P_pad * 4, true) ||
-        dev_alloc(e, (void**)&e->row_map, (size_t)g.P_pad * 4, true) ||
-        dev_alloc(e, (void**)&e->hhid, (size_t)2 * nB * H * 4, true))
-        return 1;
-    for (int i = 0; i < 5; ++i)
-        if (dev_alloc(e, (void**)&e->hb[i], (size_t)2 * nB * H * 4, true)) return 1;
-    if (dev_alloc(e, (void**)&e->xcls, (size_t)2 * nB * H * 4, true) || dev_alloc(e, (void**)&e->lncls, (size_t)2 * nB * H * 4, true) ||
-        dev_alloc(e, (void**)&e->qcls, (size_t)2 * nB * H * 4, true))
-        return 1;
-    {
-        const int64_t ra = round_up((int64_t)2 * nB, 64);
-        e->r_alloc = (int)ra;
-        e->hp_plane = ra * H; e->ht_plane = ra * e->hidp; e->hq_plane = ra * (H / 4);
-        e->tl_plane = ra * H; e->th_plane = ra * e->Mdim;
-        if (dev_alloc(e, &e->hp[0], (size_t)e->hp_plane * 4, true) || dev_alloc(e, &e->hp[1], (size_t)e->hp_plane * 4, true) ||
-            dev_alloc(e, &e->ht, (size_t)e->ht_plane * 4, true) || dev_alloc(e, &e->hq, (size_t)e->hq_plane * 4, true) ||
-            dev_alloc(e, &e->tl, (size_t)e->tl_plane * 2 * e->apl, true) || dev_alloc(e, &e->th, (size_t)e->th_plane * 2 * e->apl, true))
-            return 1;
-        // rows >= R and the K-padding columns are read by the MFMA stages: zero once, never written
-        HIP_TRY(hipMemset(e->hp[0], 0, (size_t)e->hp_plane * 4));
-        HIP_TRY(hipMemset(e->hp[1], 0, (size_t)e->hp_plane * 4));
-        HIP_TRY(hipMemset(e->ht, 0, (size_t)e->ht_plane * 4));
-        HIP_TRY(hipMemset(e->hq, 0, (size_t)e->hq_plane * 4));
-        HIP_TRY(hipMemset(e->tl, 0, (size_t)e->tl_plane * 2 * e->apl));
-        HIP_TRY(hipMemset(e->th, 0, (size_t)e->th_plane * 2 * e->apl));
+    for (const WsBuf& b : workspace(e, nB, nN)) {
+        const size_t bytes = (size_t)b.elems * b.esz * b.planes;
+        if (dev_alloc(e, b.ptr, bytes, true)) return 1;
+        if (b.stride) *b.stride = b.elems;
+        if (b.zero) HIP_TRY(hipMemset(*b.ptr, 0, bytes));
     }
-    // finite contents everywhere: padded rows are computed on (never consumed) and must not breed NaNs
-    HIP_TRY(hipMemset(e->x, 0, (size_t)g.rows_alloc * H * 4));
-    HIP_TRY(hipMemset(e->lnbuf, 0, (size_t)e->ln_plane * 2 * e->apl));
-    HIP_TRY(hipMemset(e->big, 0, (size_t)e->big_plane * 2 * e->apl));
     HIP_TRY(hipDeviceSynchronize());
+    e->r_alloc = (int)geometry(e, nB, nN).R_pad;
     e->capB = nB;
     e->capN = nN;
     return 0;
@@ -457,176 +446,141 @@ int fp8_stage(vtq_engine* e, hipStream_t s, float& sc, F launch) {
 // All encoder layers for the g.nseq sequences, enqueued on s.
 int run_encoder(vtq_engine* e, const Geometry& g, hipStream_t s, bool prune) {
     const vtq_config& c = e->cfg;
-    const int H = e->H, Md = e->Mdim, T = e->T, L = c.num_layers, f16 = e->f16, apl = e->apl;
+    const int H = e->H, Md = e->Mdim, T = e->T, L = c.num_layers, f16 = e->f16, apl = e->apl, Hqp = (int)e->Hqp;
     const Num lin = e->lin;
     const int M = (int)g.M_pad;
     float* x = e->x;
-    char* lnb = (char*)e->lnbuf;
-    char* big = (char*)e->big;                               // QKV (ld 3H) and the MLP hidden (ld M) alias: never live together
+    // the two activation buffers, as planes of row length ld.  QKV (ld 3H) and the MLP hidden (ld M) alias in `big`: never live together
+    auto lnv = [&](int ld) { return View{e->lnbuf, e->ln_plane, ld}; };
+    auto bigv = [&](int ld) { return View{e->big, e->big_plane, ld}; };
     float *xcls = e->xcls, *lncls = e->lncls, *qcls = e->qcls;
     const int64_t trace_stride = (int64_t)g.nseq * T * H;
     // LayerNorm inside the residual GEMMs (gemm_rowln.hip): the out-proj launch also writes LayerNorm 2's planes, the fc2 launch the
     // NEXT layer's LayerNorm 1 planes; only layer 0's LayerNorm 1 (behind the patch embedding) is a launch of its own.  Not while a
     // test stops the encoder between stages (vtq_debug_stop_after addresses the separate stages).
     const bool fused = e->fuse_ln && e->dbg_stop < 0;
-    auto resid_ln = [&](const void* A, int64_t a_plane, int lda, const void* W, int64_t w_plane, int K, const float* bias, const float* gamma,
-                        const float* lnw, const float* lnbias) -> hipError_t {
-        RowLnArgs a{};
-        a.A = A; a.a_plane = a_plane; a.lda = lda; a.W = W; a.w_plane = w_plane; a.M = M; a.N = H; a.K = K; a.bias = bias; a.gamma = gamma; a.x = x;
-        a.ln_w = lnw; a.ln_b = lnbias; a.out = lnb; a.o_plane = e->ln_plane;
-        return launch_gemm_rowln(a, lin, s);
+    // fp8 mode (VTQ_PREC_FP8): LayerNorm / attention / GELU outputs are e4m3 bytes with the scales s_* (`sc`; see kSPatch), weights
+    // are e4m3 rows with per-output-channel scales (de-scaled in the GEMM epilogue); the QKV output is one fp16 plane
+    const bool f8m = e->fp8;
+    // lnbuf = LayerNorm(x; w, b) for all M rows
+    auto layernorm = [&](const float* w, const float* b, float& sc) -> int {
+        Prof p(e, s, VTQ_K_LN);
+        if (f8m)
+            return fp8_stage(e, s, sc, [&](float v, Fp8Obs ob) {
+                HIP_TRY(launch_layernorm(x, w, b, e->lnbuf, e->ln_plane, M, H, 2, 1, s, v, ob));
+                return 0;
+            });
+        HIP_TRY(launch_layernorm(x, w, b, e->lnbuf, e->ln_plane, M, H, f16, apl, s));
+        return 0;
+    };
+    // One residual branch: x += gamma * h, h = A W^T + b (A: activations scaled by 1 / ascale_inv in fp8 mode).
+    //   fused: the same launch also writes lnbuf = LayerNorm(x; lnw, lnbias) (lnw NULL: none).
+    //   Adapter pair 0 at `site` (transformer.py:279-283): h <- h + up(gelu(down(h))) BEFORE LayerScale and the residual add.  The
+    //   residual GEMM already added gamma * h; the adapter's delta follows as two more GEMMs from h's own planes, written first into
+    //   `spare` (the activation buffer A is not in): down (N = H/4 padded to the tile, GELU epilogue) into A's buffer, which is
+    //   consumed by then, up (K = the padded H/4) with the same LayerScale into x.
+    const bool adapters = c.num_adapters > 0;
+    auto residual = [&](View a, View spare, const Lin& l, float ascale_inv, const float* gamma, const float* lnw, const float* lnbias,
+                        const Layer& Ly, int site) -> int {
+        const View h{spare.p, spare.plane, H}, t{a.p, a.plane, Hqp};
+        if (adapters) HIP_TRY(launch_gemm(gemm_args(a, l, M, h, ascale_inv), lin, EPI_BIAS, s));
+        if (fused) {
+            RowLnArgs r{};
+            r.A = a.p; r.a_plane = a.plane; r.lda = a.ld; r.W = l.w; r.w_plane = l.plane; r.M = M; r.N = H; r.K = l.K; r.bias = l.b;
+            r.gamma = gamma; r.x = x; r.ln_w = lnw; r.ln_b = lnbias; r.out = e->lnbuf; r.o_plane = e->ln_plane;
+            HIP_TRY(launch_gemm_rowln(r, lin, s));
+        } else {
+            GemmArgs r = gemm_args(a, l, M, View{}, ascale_inv);
+            r.gamma = gamma; r.x = x;
+            HIP_TRY(launch_gemm(r, lin, EPI_RESID, s));
+        }
+        if (adapters) {
+            HIP_TRY(launch_gemm(gemm_args(h, Ly.ad_dn[site], M, t), lin, EPI_BIAS_GELU, s));
+            GemmArgs u = gemm_args(t, Ly.ad_up[site], M);
+            u.gamma = gamma; u.x = x;
+            HIP_TRY(launch_gemm(u, lin, EPI_RESID, s));
+        }
+        return 0;
     };
     for (int i = 0; i < L; ++i) {
         const Layer& Ly = e->layers[i];
+        if (!(fused && i > 0) && layernorm(Ly.ln1w, Ly.ln1b, e->s_ln1[i])) return 1;
         if (prune && i == L - 1) {
             // ---- last layer: K/V for every row, everything else for the 2B CLS rows only (cls_tail.hip) ------------
             const int R = g.nseq;
-            if (!(fused && i > 0)) { Prof p(e, s, VTQ_K_LN); HIP_TRY(launch_layernorm(x, Ly.ln1w, Ly.ln1b, lnb, e->ln_plane, M, H, f16, apl, s)); }
-            {
+            {   // key and value projections: rows H .. 3H-1 of the packed QKV weight, into their columns of the QKV planes
                 Prof p(e, s, VTQ_K_QKV);
-                GemmArgs a{};
-                a.A = lnb; a.a_plane = e->ln_plane; a.lda = H;
-                a.W = (const char*)Ly.wqkv + (size_t)H * H * 2; a.w_plane = Ly.pqkv;
-                a.M = M; a.N = 2 * H; a.K = H; a.bias = Ly.bqkv + H;
-                a.out = big + (size_t)H * 2; a.o_plane = e->big_plane; a.ldo = 3 * H;
-                HIP_TRY(launch_gemm(a, lin, EPI_BIAS, s));
+                const View kv{(char*)e->big + (size_t)H * 2, e->big_plane, 3 * H};
+                HIP_TRY(launch_gemm(gemm_args(lnv(H), lin_rows(Ly.qkv, H, 2 * H), M, kv), lin, EPI_BIAS, s));
             }
             {
                 Prof p(e, s, VTQ_K_HEAD);
                 // skinny MFMA stages on the R CLS rows (skinny.hip); activations between them as planes in the encoder's format
-                auto stage = [&](const void* xa, int64_t xpl, int ldx, const void* W, int64_t wpl_, int N, int K, const float* bias) {
-                    SkinnyArgs a{};
-                    a.xa = xa; a.xa_plane = xpl; a.ldx = ldx; a.W = W; a.w_plane = wpl_; a.R = R; a.N = N; a.K = K; a.bias = bias;
-                    a.ya_planes = apl;
-                    return a;
-                };
+                const View tlv{e->tl, e->tl_plane, H}, thv{e->th, e->th_plane, Md};
                 const PlaneOut tl{e->tl, e->tl_plane, H, f16, apl, nullptr};       // every row kernel of the tail writes its consumer's planes
                 HIP_TRY(launch_rows_ln(x + (int64_t)e->iqa_token * H, (int64_t)g.S_pad * H, Ly.ln1w, Ly.ln1b, lncls, xcls, R, H, tl, s));
                 {   // query projection: rows 0 .. H-1 of the packed QKV weight
-                    SkinnyArgs a = stage(e->tl, e->tl_plane, H, Ly.wqkv, Ly.pqkv, H, H, Ly.bqkv);
+                    SkinnyArgs a = skinny_args(tlv, lin_rows(Ly.qkv, 0, H), R, apl);
                     a.epi = SK_PLAIN; a.y = qcls; a.ldy = H; a.ycols = H;
                     HIP_TRY(launch_skinny(a, lin, s));
                 }
-                HIP_TRY(launch_cls_attention(qcls, big, e->big_plane, nullptr, R, g.S, g.S_pad, H, f16, apl, tl, s, e->att.terms == 3));
+                HIP_TRY(launch_cls_attention(qcls, e->big, e->big_plane, nullptr, R, g.S, g.S_pad, H, f16, apl, tl, s, e->att.terms == 3));
                 {   // out-proj + LayerScale + residual, in place on the CLS rows
-                    SkinnyArgs a = stage(e->tl, e->tl_plane, H, Ly.wo, Ly.po, H, H, Ly.bo);
+                    SkinnyArgs a = skinny_args(tlv, Ly.out, R, apl);
                     a.epi = SK_RESID; a.gamma = Ly.g1; a.res = xcls; a.ldr = H; a.y = xcls; a.ldy = H; a.ycols = H;
                     HIP_TRY(launch_skinny(a, lin, s));
                 }
                 HIP_TRY(launch_rows_ln(xcls, H, Ly.ln2w, Ly.ln2b, lncls, nullptr, R, H, tl, s));
                 {   // fc1 + GELU -> planes
-                    SkinnyArgs a = stage(e->tl, e->tl_plane, H, Ly.w1, Ly.p1, Md, H, Ly.b1);
+                    SkinnyArgs a = skinny_args(tlv, Ly.fc1, R, apl);
                     a.epi = SK_GELU; a.ya = e->th; a.ya_plane = e->th_plane; a.ldya = Md;
                     HIP_TRY(launch_skinny(a, lin, s));
                 }
                 {   // fc2 + LayerScale + residual
-                    SkinnyArgs a = stage(e->th, e->th_plane, Md, Ly.w2, Ly.p2, H, Md, Ly.b2);
+                    SkinnyArgs a = skinny_args(thv, Ly.fc2, R, apl);
                     a.epi = SK_RESID; a.gamma = Ly.g2; a.res = xcls; a.ldr = H; a.y = xcls; a.ldy = H; a.ycols = H;
                     HIP_TRY(launch_skinny(a, lin, s));
                 }
             }
             break;
         }
-        // fp8 mode (VTQ_PREC_FP8): LayerNorm / attention / GELU outputs are e4m3 bytes with the static scales kS*, weights are
-        // e4m3 rows with per-output-channel scales (de-scaled in the GEMM epilogue); the QKV output is one fp16 plane
-        const bool f8m = e->fp8;
-        // Adapter pair 0 (transformer.py:279-283): h <- h + up(gelu(down(h))) on the branch output BEFORE LayerScale and the residual
-        // add.  The residual GEMM already added ls * h; the adapter's delta follows as two more GEMMs: down (N = H/4 padded to the
-        // tile, GELU epilogue) into `tmp`, up (K = the padded H/4) with the same LayerScale into x.
-        const bool adapters = c.num_adapters > 0;
-        auto adapter_site = [&](const Layer& L, int site, void* hsrc, int64_t hplane, void* tmp, int64_t tplane, const float* gamma) -> hipError_t {
-            GemmArgs d{};
-            d.A = hsrc; d.a_plane = hplane; d.lda = H; d.W = L.ad_dn[site]; d.w_plane = L.pad_dn[site];
-            d.M = M; d.N = (int)e->Hqp; d.K = H; d.bias = L.ad_bdn[site]; d.out = tmp; d.o_plane = tplane; d.ldo = (int)e->Hqp;
-            hipError_t err = launch_gemm(d, lin, EPI_BIAS_GELU, s);
-            if (err != hipSuccess) return err;
-            GemmArgs u{};
-            u.A = tmp; u.a_plane = tplane; u.lda = (int)e->Hqp; u.W = L.ad_up[site]; u.w_plane = L.pad_up[site];
-            u.M = M; u.N = H; u.K = (int)e->Hqp; u.bias = L.ad_bup[site]; u.gamma = gamma; u.x = x;
-            return launch_gemm(u, lin, EPI_RESID, s);
-        };
-        const int lnf = f8m ? 2 : f16, lnp = f8m ? 1 : apl;
-        if (!(fused && i > 0)) {
-            Prof p(e, s, VTQ_K_LN);
-            if (f8m) {
-                if (fp8_stage(e, s, e->s_ln1[i], [&](float sc, Fp8Obs ob) { HIP_TRY(launch_layernorm(x, Ly.ln1w, Ly.ln1b, lnb, e->ln_plane, M, H, 2, 1, s, sc, ob)); return 0; })) return 1;
-            } else HIP_TRY(launch_layernorm(x, Ly.ln1w, Ly.ln1b, lnb, e->ln_plane, M, H, lnf, lnp, s));
-        }
         if (e->dbg_stop == i * 7 + 0) return 0;
         {
             Prof p(e, s, VTQ_K_QKV);
-            GemmArgs a{};
-            a.A = lnb; a.a_plane = e->ln_plane; a.lda = H; a.W = Ly.wqkv; a.w_plane = Ly.pqkv;
-            a.M = M; a.N = 3 * H; a.K = H; a.bias = Ly.bqkv; a.out = big; a.o_plane = e->big_plane; a.ldo = 3 * H;
-            a.wscale = Ly.sqkv; a.ascale_inv = 1.0f / e->s_ln1[i];
-            HIP_TRY(launch_gemm(a, lin, EPI_BIAS, s));
+            HIP_TRY(launch_gemm(gemm_args(lnv(H), Ly.qkv, M, bigv(3 * H), 1.0f / e->s_ln1[i]), lin, EPI_BIAS, s));
         }
         if (e->dbg_stop == i * 7 + 1) return 0;
         {
             Prof p(e, s, VTQ_K_ATTN);
             if (f8m) {
-                if (fp8_stage(e, s, e->s_att[i], [&](float sc, Fp8Obs ob) { HIP_TRY(launch_attention(big, e->big_plane, lnb, e->ln_plane, g.nseq, g.S, g.S_pad, H, e->att, s, sc, ob, e->att.terms == 3)); return 0; })) return 1;
-            } else HIP_TRY(launch_attention(big, e->big_plane, lnb, e->ln_plane, g.nseq, g.S, g.S_pad, H, e->att, s, 0.0f, Fp8Obs{nullptr, nullptr}, e->att.terms == 3));
+                if (fp8_stage(e, s, e->s_att[i], [&](float sc, Fp8Obs ob) { HIP_TRY(launch_attention(e->big, e->big_plane, e->lnbuf, e->ln_plane, g.nseq, g.S, g.S_pad, H, e->att, s, sc, ob, e->att.terms == 3)); return 0; })) return 1;
+            } else HIP_TRY(launch_attention(e->big, e->big_plane, e->lnbuf, e->ln_plane, g.nseq, g.S, g.S_pad, H, e->att, s, 0.0f, Fp8Obs{nullptr, nullptr}, e->att.terms == 3));
             // forward_vit's attention maps: from the same QKV planes, before the out-proj (with adapters it reuses `big`)
             if (e->vit_probs)
-                HIP_TRY(launch_attention_probs(big, e->big_plane, e->vit_probs + (int64_t)i * g.nseq * (H / 64) * g.S * g.S, g.nseq, g.S, g.S_pad, H,
+                HIP_TRY(launch_attention_probs(e->big, e->big_plane, e->vit_probs + (int64_t)i * g.nseq * (H / 64) * g.S * g.S, g.nseq, g.S, g.S_pad, H,
                                                e->att, s, e->att.terms == 3));
         }
         if (e->dbg_stop == i * 7 + 2) return 0;
-        {
+        {   // x += ls1 * out-proj(attention); fused: lnbuf = LayerNorm 2 (x).  QKV is consumed: `big` is the spare buffer
             Prof p(e, s, VTQ_K_OUTPROJ);
-            GemmArgs a{};
-            a.A = lnb; a.a_plane = e->ln_plane; a.lda = H; a.W = Ly.wo; a.w_plane = Ly.po;
-            a.M = M; a.N = H; a.K = H; a.bias = Ly.bo;
-            a.wscale = Ly.so; a.ascale_inv = 1.0f / e->s_att[i];
-            if (adapters) {                      // the branch output h itself, as operand planes for the adapter (QKV is consumed: `big` is free)
-                GemmArgs hplanes = a;
-                hplanes.out = big; hplanes.o_plane = e->big_plane; hplanes.ldo = H;
-                HIP_TRY(launch_gemm(hplanes, lin, EPI_BIAS, s));
-            }
-            a.gamma = Ly.g1; a.x = x;
-            if (fused) HIP_TRY(resid_ln(lnb, e->ln_plane, H, Ly.wo, Ly.po, H, Ly.bo, Ly.g1, Ly.ln2w, Ly.ln2b));   // x += ls1 * h; lnbuf = LayerNorm 2 (x)
-            else
-            HIP_TRY(launch_gemm(a, lin, EPI_RESID, s));              // x += ls1 * h
-            if (adapters) HIP_TRY(adapter_site(Ly, 0, big, e->big_plane, lnb, e->ln_plane, Ly.g1));   // x += ls1 * (up(gelu(down(h))) )
+            if (residual(lnv(H), bigv(H), Ly.out, 1.0f / e->s_att[i], Ly.g1, Ly.ln2w, Ly.ln2b, Ly, 0)) return 1;
         }
         if (e->dbg_stop == i * 7 + 3) return 0;
-        if (!fused) {
-            Prof p(e, s, VTQ_K_LN);
-            if (f8m) {
-                if (fp8_stage(e, s, e->s_ln2[i], [&](float sc, Fp8Obs ob) { HIP_TRY(launch_layernorm(x, Ly.ln2w, Ly.ln2b, lnb, e->ln_plane, M, H, 2, 1, s, sc, ob)); return 0; })) return 1;
-            } else HIP_TRY(launch_layernorm(x, Ly.ln2w, Ly.ln2b, lnb, e->ln_plane, M, H, lnf, lnp, s));
-        }
+        if (!fused && layernorm(Ly.ln2w, Ly.ln2b, e->s_ln2[i])) return 1;
         if (e->dbg_stop == i * 7 + 4) return 0;
         {
             Prof p(e, s, VTQ_K_FC1);
-            GemmArgs a{};
-            a.A = lnb; a.a_plane = e->ln_plane; a.lda = H; a.W = Ly.w1; a.w_plane = Ly.p1;
-            a.M = M; a.N = Md; a.K = H; a.bias = Ly.b1; a.out = big; a.o_plane = e->big_plane; a.ldo = Md;
-            a.wscale = Ly.s1; a.ascale_inv = 1.0f / e->s_ln2[i];
+            const GemmArgs a = gemm_args(lnv(H), Ly.fc1, M, bigv(Md), 1.0f / e->s_ln2[i]);
             if (f8m) {
                 if (fp8_stage(e, s, e->s_gelu[i], [&](float sc, Fp8Obs ob) { GemmArgs b = a; b.out_scale = sc; b.obs = ob; HIP_TRY(launch_gemm(b, lin, EPI_BIAS_GELU, s)); return 0; })) return 1;
             } else HIP_TRY(launch_gemm(a, lin, EPI_BIAS_GELU, s));
         }
         if (e->dbg_stop == i * 7 + 5) return 0;
-        {
+        {   // x += ls2 * fc2(hidden); fused: lnbuf = the next layer's LayerNorm 1 (x) (none behind the last layer: final_diff normalises
+            // the CLS rows).  LayerNorm 2's planes are consumed: `lnbuf` is the spare buffer
             Prof p(e, s, VTQ_K_FC2);
-            GemmArgs a{};
-            a.A = big; a.a_plane = e->big_plane; a.lda = Md; a.W = Ly.w2; a.w_plane = Ly.p2;
-            a.M = M; a.N = H; a.K = Md; a.bias = Ly.b2;
-            a.wscale = Ly.s2; a.ascale_inv = 1.0f / e->s_gelu[i];
-            if (adapters) {                      // LayerNorm 2's planes are consumed: the branch output goes to `lnbuf`
-                GemmArgs hplanes = a;
-                hplanes.out = lnb; hplanes.o_plane = e->ln_plane; hplanes.ldo = H;
-                HIP_TRY(launch_gemm(hplanes, lin, EPI_BIAS, s));
-            }
-            a.gamma = Ly.g2; a.x = x;
-            if (fused) {                         // x += ls2 * h; lnbuf = the next layer's LayerNorm 1 (x) (none behind the last layer: final_diff normalises the CLS rows)
-                const Layer* nx = (i + 1 < L) ? &e->layers[i + 1] : nullptr;
-                HIP_TRY(resid_ln(big, e->big_plane, Md, Ly.w2, Ly.p2, Md, Ly.b2, Ly.g2, nx ? nx->ln1w : nullptr, nx ? nx->ln1b : nullptr));
-            } else
-            HIP_TRY(launch_gemm(a, lin, EPI_RESID, s));
-            if (adapters) HIP_TRY(adapter_site(Ly, 1, lnb, e->ln_plane, big, e->big_plane, Ly.g2));
+            const Layer* nx = (i + 1 < L) ? &e->layers[i + 1] : nullptr;
+            if (residual(bigv(Md), lnv(H), Ly.fc2, 1.0f / e->s_gelu[i], Ly.g2, nx ? nx->ln1w : nullptr, nx ? nx->ln1b : nullptr, Ly, 1)) return 1;
         }
         if (e->dbg_stop == i * 7 + 6) return 0;
         if (e->trace) HIP_TRY(launch_copy_tokens(x, e->trace + (i + 1) * trace_stride, g.nseq, g.sm, T, H, s));
@@ -648,12 +602,7 @@ int run_head(vtq_engine* e, const float* d, int HB, float* q_out, hipStream_t s,
     const int H = e->H;
     const Num h3{1, 3};
     if (HB > e->r_alloc) return fail("run_head: %d rows exceed the reserved %d", HB, e->r_alloc);
-    auto stage = [&](const void* xa, int64_t xpl, int ldx, const HeadLin& L) {
-        SkinnyArgs a{};
-        a.xa = xa; a.xa_plane = xpl; a.ldx = ldx; a.W = L.wp; a.w_plane = L.plane; a.R = HB; a.N = L.N; a.K = L.Kp; a.bias = L.b;
-        a.ya_planes = 2;
-        return a;
-    };
+    auto stage = [&](void* xa, int64_t xpl, int ldx, const Lin& L) { return skinny_args(View{xa, xpl, ldx}, L, HB, 2); };
     void *pin = e->hp[0], *pout = e->hp[1];
     if (!planes_ready) HIP_TRY(launch_rows_to_planes(d, H, head_first_slope(e), pin, e->hp_plane, H, HB, H, 1, 2, s));
     if (c.calibrate) {
@@ -711,6 +660,12 @@ int run_head(vtq_engine* e, const float* d, int HB, float* q_out, hipStream_t s,
         b.epi = SK_PLAIN; b.y = q_out; b.ldy = 1; b.ycols = 1;
         HIP_TRY(launch_skinny(b, h3, s));
     }
+    return 0;
+}
+
+int all_loaded(const vtq_engine* e, const char* who) {
+    for (auto& kv : e->slots)
+        if (!kv.second.loaded) return fail("%s: weight '%s' was never loaded", who, kv.first.c_str());
     return 0;
 }
 
@@ -833,7 +788,12 @@ int vtq_load_weights(vtq_handle e, const vtq_tensor_desc* descs, int32_t n, void
     return 0;
 }
 
-size_t vtq_workspace_bytes(vtq_handle e, int32_t B, int32_t N) { return e ? workspace_bytes(e, B, N) : 0; }
+size_t vtq_workspace_bytes(vtq_handle e, int32_t B, int32_t N) {
+    size_t bytes = 0;
+    if (e)
+        for (const WsBuf& b : workspace(e, B, N)) bytes += (size_t)b.elems * b.esz * b.planes;
+    return bytes;
+}
 
 int vtq_reserve(vtq_handle e, int32_t B, int32_t N) {
     if (!e || B < 1 || N < 1) return fail("vtq_reserve: bad argument");
@@ -958,8 +918,7 @@ static int forward_impl(vtq_handle e, int nimg, const float* const* patches, con
     if (use_scales)
         for (int k = 0; k < nimg; ++k)
             if (!scales[k]) return fail("Model uses scale embedding but scales is passed as None.");   // transformer.py:547-548
-    for (auto& kv : e->slots)
-        if (!kv.second.loaded) return fail("vtq_forward: weight '%s' was never loaded", kv.first.c_str());
+    if (all_loaded(e, "vtq_forward")) return 1;
     if (reserve(e, (nimg * B + 1) / 2, N)) return 1;       // capacity is kept in units of sequence pairs
     // fp8 mode: the first forward of an engine calibrates the activation scales on its own batch (see kSPatch); it synchronises
     // the stream once per quantisation point and returns this batch's scores computed with the final scales
@@ -981,37 +940,27 @@ static int forward_impl(vtq_handle e, int nimg, const float* const* patches, con
     }
 
     // ---- embeddings (transformer.py:526-562) -------------------------------------------------------------------
-    if (tokens_in) {
-        // pre-embedded input (transformer.py:534-535): `patches` are (B, N, H) feature rows; no patch convolution
-        Prof p(e, s, VTQ_K_CONVERT);
-        HIP_TRY(launch_embed_index(pos, use_scales ? scales : nullptr, nimg, e->pidx, e->sidx, e->row_map, B, N, (int)g.P_pad, g.sm, T,
-                                   c.pos_grid, c.num_scales, e->err_flag, s));
-        HIP_TRY(launch_zero_pad_rows(e->x, g.nseq, g.S, g.sm, H, (int)g.rows_alloc, s));
-        HIP_TRY(launch_tokens(e->x, e->cls, e->pos_table, e->extra, g.nseq, g.sm, T, H, s));
-        HIP_TRY(launch_embed_rows(patches, nimg, B * N, e->row_map, e->pidx, e->sidx, e->pos_table, use_scales ? e->scale_table : nullptr, e->x, H, s));
-    } else {
+    // 5-D patches: packed to planes here, then one GEMM whose epilogue adds the table rows and scatters into x.  Pre-embedded input
+    // (transformer.py:534-535): `patches` are (B, N, H) feature rows; no patch convolution, a row kernel adds the table rows
     {
         Prof p(e, s, VTQ_K_CONVERT);
-        if (e->fp8) {
+        if (!tokens_in && e->fp8) {
             if (fp8_stage(e, s, e->s_patch, [&](float sc, Fp8Obs ob) { HIP_TRY(launch_pack_patches(patches, nimg, e->big, e->big_plane, B * N, c.patch_dim, (int)g.P_pad, 2, 1, s, sc, (int)e->PDp, ob)); return 0; })) return 1;
-        } else HIP_TRY(launch_pack_patches(patches, nimg, e->big, e->big_plane, B * N, c.patch_dim, (int)g.P_pad, e->f16, e->apl, s, 1.0f, (int)e->PDp));
+        } else if (!tokens_in) HIP_TRY(launch_pack_patches(patches, nimg, e->big, e->big_plane, B * N, c.patch_dim, (int)g.P_pad, e->f16, e->apl, s, 1.0f, (int)e->PDp));
         HIP_TRY(launch_embed_index(pos, use_scales ? scales : nullptr, nimg, e->pidx, e->sidx, e->row_map, B, N, (int)g.P_pad, g.sm, T,
                                    c.pos_grid, c.num_scales, e->err_flag, s));
         HIP_TRY(launch_zero_pad_rows(e->x, g.nseq, g.S, g.sm, H, (int)g.rows_alloc, s));
         HIP_TRY(launch_tokens(e->x, e->cls, e->pos_table, e->extra, g.nseq, g.sm, T, H, s));
+        if (tokens_in)
+            HIP_TRY(launch_embed_rows(patches, nimg, B * N, e->row_map, e->pidx, e->sidx, e->pos_table, use_scales ? e->scale_table : nullptr, e->x, H, s));
     }
-    {
+    if (!tokens_in) {
         Prof p(e, s, VTQ_K_PATCH);
-        GemmArgs a{};
-        a.A = e->big; a.a_plane = e->big_plane; a.lda = (int)e->PDp;
-        a.W = e->wpatch; a.w_plane = e->ppatch;
-        a.M = (int)g.P_pad; a.N = H; a.K = (int)e->PDp;
-        a.bias = e->bpatch; a.x = e->x;
+        GemmArgs a = gemm_args(View{e->big, e->big_plane, (int)e->PDp}, e->patch, (int)g.P_pad, View{}, 1.0f / e->s_patch);
+        a.x = e->x;
         a.row_map = e->row_map; a.idx1 = e->pidx; a.table1 = e->pos_table;
         a.idx2 = e->sidx; a.table2 = use_scales ? e->scale_table : nullptr;
-        a.wscale = e->spatch; a.ascale_inv = 1.0f / e->s_patch;
         HIP_TRY(launch_gemm(a, e->lin, EPI_EMBED, s));
-    }
     }
     if (e->trace) HIP_TRY(launch_copy_tokens(e->x, e->trace, g.nseq, g.sm, T, H, s));
 
@@ -1096,34 +1045,39 @@ int vtq_fp8_reset(vtq_handle e) {
 }
 #endif
 
-int vtq_forward(vtq_handle e, const float* patches_ref, const float* patches_dist, const float* pos_ref, const float* pos_dist,
-                const float* scales_ref, const float* scales_dist, int32_t B, int32_t N, float* q_out, void* stream) {
-    const float* p[2] = {patches_ref, patches_dist};
+static int forward_pair(vtq_handle e, bool tokens_in, const float* in_ref, const float* in_dist, const float* pos_ref, const float* pos_dist,
+                        const float* scales_ref, const float* scales_dist, int32_t B, int32_t N, float* q_out, void* stream) {
+    const float* p[2] = {in_ref, in_dist};
     const float* ps[2] = {pos_ref, pos_dist};
     const float* sc[2] = {scales_ref, scales_dist};
-    return forward_impl(e, 2, p, ps, sc, B, N, q_out, stream);
+    return forward_impl(e, 2, p, ps, sc, B, N, q_out, stream, tokens_in);
+}
+
+int vtq_forward(vtq_handle e, const float* patches_ref, const float* patches_dist, const float* pos_ref, const float* pos_dist,
+                const float* scales_ref, const float* scales_dist, int32_t B, int32_t N, float* q_out, void* stream) {
+    return forward_pair(e, false, patches_ref, patches_dist, pos_ref, pos_dist, scales_ref, scales_dist, B, N, q_out, stream);
 }
 
 int vtq_forward_tokens(vtq_handle e, const float* feats_ref, const float* feats_dist, const float* pos_ref, const float* pos_dist,
                        const float* scales_ref, const float* scales_dist, int32_t B, int32_t N, float* q_out, void* stream) {
-    const float* p[2] = {feats_ref, feats_dist};
-    const float* ps[2] = {pos_ref, pos_dist};
-    const float* sc[2] = {scales_ref, scales_dist};
-    return forward_impl(e, 2, p, ps, sc, B, N, q_out, stream, true);
+    return forward_pair(e, true, feats_ref, feats_dist, pos_ref, pos_dist, scales_ref, scales_dist, B, N, q_out, stream);
+}
+
+static int forward_triplet(vtq_handle e, const char* who, bool tokens_in, const float* const* in, const float* const* pos,
+                           const float* const* scales, int32_t B, int32_t N, float* q_out, void* stream) {
+    if (!in || !pos) return fail("%s: null argument", who);
+    const float* sc[3] = {scales ? scales[0] : nullptr, scales ? scales[1] : nullptr, scales ? scales[2] : nullptr};
+    return forward_impl(e, 3, in, pos, sc, B, N, q_out, stream, tokens_in);
 }
 
 int vtq_forward_pairwise(vtq_handle e, const float* const* patches, const float* const* pos, const float* const* scales, int32_t B,
                          int32_t N, float* q_out, void* stream) {
-    if (!patches || !pos) return fail("vtq_forward_pairwise: null argument");
-    const float* sc[3] = {scales ? scales[0] : nullptr, scales ? scales[1] : nullptr, scales ? scales[2] : nullptr};
-    return forward_impl(e, 3, patches, pos, sc, B, N, q_out, stream);
+    return forward_triplet(e, "vtq_forward_pairwise", false, patches, pos, scales, B, N, q_out, stream);
 }
 
 int vtq_forward_pairwise_tokens(vtq_handle e, const float* const* feats, const float* const* pos, const float* const* scales, int32_t B,
                                 int32_t N, float* q_out, void* stream) {
-    if (!feats || !pos) return fail("vtq_forward_pairwise_tokens: null argument");
-    const float* sc[3] = {scales ? scales[0] : nullptr, scales ? scales[1] : nullptr, scales ? scales[2] : nullptr};
-    return forward_impl(e, 3, feats, pos, sc, B, N, q_out, stream, true);
+    return forward_triplet(e, "vtq_forward_pairwise_tokens", true, feats, pos, scales, B, N, q_out, stream);
 }
 
 int vtq_forward_vit(vtq_handle e, const float* in, int32_t tokens_in, const float* pos, const float* scales, int32_t B, int32_t N,
@@ -1259,8 +1213,7 @@ int vtq_k_skinny_linear(const void* xa, int64_t xa_plane, int32_t ldx, const voi
 
 int vtq_k_diffnet_head(vtq_handle e, const float* d, int32_t HB, float* q_out, void* stream) {
     if (!e || !d || !q_out || HB < 1) return fail("vtq_k_diffnet_head: bad argument");
-    for (auto& kv : e->slots)
-        if (!kv.second.loaded) return fail("vtq_k_diffnet_head: weight '%s' was never loaded", kv.first.c_str());
+    if (all_loaded(e, "vtq_k_diffnet_head")) return 1;
     if (reserve(e, (HB + 1) / 2, 1)) return 1;
     return run_head(e, d, HB, q_out, (hipStream_t)stream);
 }

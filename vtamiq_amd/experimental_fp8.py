@@ -24,7 +24,7 @@ import torch
 import torch.distributed as dist
 
 from . import _lib
-from .model import VTAMIQ
+from .model import VTAMIQ, _ptr
 
 
 class VTAMIQFp8(VTAMIQ):
@@ -113,18 +113,16 @@ class VTAMIQFp8(VTAMIQ):
         """Re-calibrate the activation scales on this batch (arguments as forward()); returns the batch's scores."""
         if self.precision != "fp8":
             raise RuntimeError("calibrate_fp8: precision is not 'fp8'")
-        device = patches[0].device
-        use_scales = self.spec.use_scale_embedding
+        patches_ref, patches_dist = patches
+        device, B, N, tokens_in, (pr, pd), (qr, qd), (sr, sdist) = self._inputs((patches_ref, patches_dist), pos, scales, warn_grad=False)
+        if tokens_in:
+            raise NotImplementedError("calibrate_fp8: the fp8 experiment has no pre-embedded input path")
         with torch.cuda.device(device):
             self.__dict__["_fp8_user"] = False            # before the engine is (re)built: its weight load must not re-install old user scales
             lib = self._ensure_engine(device)
-            t = [self._prep(x, device) for x in (patches[0], patches[1], pos[0], pos[1])]
-            sc = [self._prep(x, device) for x in scales] if use_scales else [None, None]
-            B, N = patches[0].shape[:2]
             q = torch.empty(B, device=device, dtype=torch.float32)
             stream = torch.cuda.current_stream(device).cuda_stream
-            self._check(lib.vtq_fp8_calibrate(self._engine, t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr(), t[3].data_ptr(),
-                                             sc[0].data_ptr() if use_scales else None, sc[1].data_ptr() if use_scales else None,
+            self._check(lib.vtq_fp8_calibrate(self._engine, pr.data_ptr(), pd.data_ptr(), qr.data_ptr(), qd.data_ptr(), _ptr(sr), _ptr(sdist),
                                              B, N, q.data_ptr(), stream))
         self.__dict__["_fp8_checked"] = 0
         self.fp8_scales()

@@ -32,6 +32,16 @@ _PRECISIONS = _lib.PRECISIONS
 DEFAULT_PRECISION = "auto"
 AUTO_FIRST, AUTO_FALLBACK = "fp16x3", "bf16x3"
 
+_TRAIN_MSG = ("the MI355X engine implements the eval/no-grad forward only (Dropout/DropPath of vtamiq.py:72-75 and "
+              "channel_attention.py:26-29 are train-time stochastic; backward is out of scope): call model.eval()")
+_POS_RANGE_MSG = "pos outside [0, 1): index out of range in the positional-embedding table (transformer.py:417-421)"
+_COUNT = {1: ("a", "tensor"), 2: ("two", "tensors"), 3: ("three", "tensors")}      # images per item, as the shape errors word it
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
 class _Params(nn.Module):
     """A container whose forward must never run."""
 
@@ -311,18 +321,21 @@ class VTAMIQ(nn.Module):
         it with its packed weights under its precision, so that a batch with non-finite inputs does not cost two engine builds and two
         weight re-packs per call.  Without park, parked engines are destroyed too."""
         eng = self.__dict__.get("_engine")
-        parked = self.__dict__.setdefault("_parked", {})
         if eng is not None:
             if park:
-                parked[self.__dict__.get("_engine_precision")] = (eng, self.__dict__.get("_weights_sig"))
+                self.__dict__.setdefault("_parked", {})[self.__dict__.get("_engine_precision")] = (eng, self.__dict__.get("_weights_sig"))
             else:
                 self._engine_lib().vtq_destroy(eng)
         if not park:
-            for h, _ in parked.values():
-                self._engine_lib().vtq_destroy(h)
-            parked.clear()
+            self._destroy_parked()
         self.__dict__["_engine"] = None
         self.__dict__["_weights_sig"] = None
+
+    def _destroy_parked(self):
+        parked = self.__dict__.setdefault("_parked", {})
+        for h, _ in parked.values():
+            self._engine_lib().vtq_destroy(h)
+        parked.clear()
 
     def _forget_packed_weights(self):
         self.__dict__["_weights_sig"] = None
@@ -348,17 +361,13 @@ class VTAMIQ(nn.Module):
         if one produced a non-finite CLS difference (operand range overflow, fp16 modes)."""
         if self._engine is None:
             return
-        flags = C.c_int32(0)
-        with torch.cuda.device(self._engine_device):
-            stream = torch.cuda.current_stream(self._engine_device).cuda_stream
-            self._check(self._engine_lib().vtq_input_errors(self._engine, C.byref(flags), stream))
-        flags.value |= self.__dict__.pop("_flags_seen", 0)       # bits an earlier look of a subclass already collected (and cleared)
-        if flags.value & 1:
-            raise IndexError("pos outside [0, 1): index out of range in the positional-embedding table (transformer.py:417-421)")
-        if flags.value & 4:                         # raised by the fp8 experiment's kernels only
+        flags = self._read_flags() | self.__dict__.pop("_flags_seen", 0)    # bits an earlier look of a subclass already collected (and cleared)
+        if flags & 1:
+            raise IndexError(_POS_RANGE_MSG)
+        if flags & 4:                               # raised by the fp8 experiment's kernels only
             raise FloatingPointError("fp8 experiment: an activation exceeded e4m3's range after scaling and was clamped to +-448 -- the "
                                      "calibrated scales do not fit this data; calibrate_fp8() on a representative batch")
-        if flags.value & 2:
+        if flags & 2:
             raise FloatingPointError(
                 f"non-finite encoder output in precision={self.engine_precision!r}: an activation or weight left the operand format's range "
                 "(fp16 modes: |v| <= 65504) or the inputs held inf / NaN; precision='bf16x3' has the fp32 range")
@@ -409,10 +418,7 @@ class VTAMIQ(nn.Module):
                     flags2 = (flags2 & 1) | (self._read_flags() & 1)
                 else:
                     # the switch is sticky: the parked fp16x3 engine (packed weights + workspace) will not be used again
-                    for h, _ in self.__dict__.get("_parked", {}).values():
-                        lib_ = self._engine_lib()
-                        lib_.vtq_destroy(h)
-                    self.__dict__.get("_parked", {}).clear()
+                    self._destroy_parked()
                     warnings.warn(f"[VTAMIQ] an activation or weight left the fp16 operand range (|v| > 65504) in precision "
                                   f"{AUTO_FIRST!r}: this model now runs {AUTO_FALLBACK!r} (fp32 operand range, the same 3-MFMA "
                                   "split; the call was repeated)")
@@ -420,7 +426,7 @@ class VTAMIQ(nn.Module):
             elif flags & 2:
                 warnings.warn("[VTAMIQ] non-finite scores in precision 'bf16x3': the inputs or weights of this call hold inf / NaN")
             if flags & 1:
-                raise IndexError("pos outside [0, 1): index out of range in the positional-embedding table (transformer.py:417-421)")
+                raise IndexError(_POS_RANGE_MSG)
         elif self.validate_inputs:
             self.check_inputs()
 
@@ -505,53 +511,64 @@ class VTAMIQ(nn.Module):
             t = t.float()                     # the loader hands everything over as f32 (train.py:254-255)
         return t if t.is_contiguous() else t.contiguous()
 
-    def forward(self, patches, pos, scales, _trace: Optional[torch.Tensor] = None):
-        if self.training:
-            raise NotImplementedError(
-                "the MI355X engine implements the eval/no-grad forward only (Dropout/DropPath of vtamiq.py:72-75 and "
-                "channel_attention.py:26-29 are train-time stochastic; backward is out of scope): call model.eval()")
-        patches_ref, patches_dist = patches
-        pos_ref, pos_dist = pos
-        scales_ref, scales_dist = scales
-        device = patches_ref.device
+    def _inputs(self, patches, pos, scales, warn_grad: bool = True):
+        """The input checks every entry point shares, for k = len(patches) images per item (1: forward_vit, 2: (ref, dist), 3: pairwise
+        triplet): the device check, the no-autograd warning, the shapes.  Returns (device, B, N, tokens_in, patches, pos, scales) with the
+        three tensor lists made fp32 and contiguous; scales is k Nones when the model has no scale embedding."""
+        k = len(patches)
+        how, noun = _COUNT[k]
+        spec, first = self.spec, patches[0]
+        device = first.device
         if device.type != "cuda":
             raise RuntimeError("VTAMIQ (vtamiq_amd) runs on an MI355X only: move the model and inputs to 'cuda'. "
                                "There is no CPU fallback on the product path.")
-        if torch.is_grad_enabled() and not self._warned_grad and any(p.requires_grad for p in self.parameters()):
+        if warn_grad and torch.is_grad_enabled() and not self._warned_grad and any(p.requires_grad for p in self.parameters()):
             warnings.warn("vtamiq_amd.VTAMIQ.forward returns scores without an autograd graph (inference engine)")
             self._warned_grad = True
+
+        def got(t):                               # the triplet form names the offending tensor, the others every tensor
+            return tuple(t.shape) if k == 3 else " / ".join(str(tuple(u.shape)) for u in patches)
         # Embeddings.forward (transformer.py:527-535): a 5-D tensor goes through the patch convolution, anything else is taken as pre-embedded
         # (B, N, H) rows -- whatever `use_patch_embedding` says; a model built without the convolution fails on 5-D input like the reference does
-        tokens_in = patches_ref.dim() != 5
+        tokens_in = first.dim() != 5
         if tokens_in:
-            if patches_ref.dim() != 3 or patches_ref.shape != patches_dist.shape or patches_ref.shape[2] != self.spec.hidden_size:
-                raise ValueError(f"pre-embedded input must be two (B,N,{self.spec.hidden_size}) tensors, got {tuple(patches_ref.shape)} / {tuple(patches_dist.shape)}")
-            B, N = patches_ref.shape[:2]
+            want = (*first.shape[:2], spec.hidden_size)
+            for t in patches:
+                if tuple(t.shape) != want:
+                    raise ValueError(f"pre-embedded input must be {how} (B,N,{spec.hidden_size}) {noun}, got {got(t)}")
         else:
-            if not self.spec.use_patch_embedding:
+            if not spec.use_patch_embedding:
                 raise AttributeError("'Embeddings' object has no attribute 'patch_embeddings' (use_patch_embedding=False: pass pre-embedded (B,N,H) rows)")
-            if patches_ref.shape != patches_dist.shape:
-                raise ValueError(f"patches must be two (B,N,3,P,P) tensors, got {tuple(patches_ref.shape)} / {tuple(patches_dist.shape)}")
-            B, N, Cc, P, P2 = patches_ref.shape
-            if (Cc, P, P2) != (3, self.spec.patch_size, self.spec.patch_size):
-                raise ValueError(f"patch shape {(Cc, P, P2)} != (3,{self.spec.patch_size},{self.spec.patch_size})")
-        if not self.spec.use_pos_embedding:
+            patch = (3, spec.patch_size, spec.patch_size)
+            want = (*first.shape[:2], *patch) if k == 3 else tuple(first.shape)      # (the triplet form reports a wrong patch shape here too)
+            for t in patches:
+                if tuple(t.shape) != want:
+                    raise ValueError(f"patches must be {how} (B,N,3,P,P) {noun}, got {got(t)}")
+            if tuple(first.shape[2:]) != patch:
+                raise ValueError(f"patch shape {tuple(first.shape[2:])} != (3,{spec.patch_size},{spec.patch_size})")
+        B, N = first.shape[:2]
+        if not spec.use_pos_embedding:
             # the reference never looks at `pos` then (transformer.py:539): whatever was passed, None included, has no effect.  The
             # engine's index kernel still wants coordinates: zeros (table row 1 of the all-zero table _ensure_engine installs)
-            pos_ref = pos_dist = torch.zeros(B, N, 2, device=device, dtype=torch.float32)
-        if tuple(pos_ref.shape) != (B, N, 2) or tuple(pos_dist.shape) != (B, N, 2):
-            raise ValueError("pos must be two (B,N,2) tensors")
-        use_scales = self.spec.use_scale_embedding
-        if use_scales:
-            if scales_ref is None or scales_dist is None:
-                raise ValueError("Model uses scale embedding but scales is passed as None.")   # transformer.py:547-548
-            if scales_ref.numel() != B * N or scales_dist.numel() != B * N:
-                raise ValueError("scales must be two (B,N) tensors")
+            pos = (torch.zeros(B, N, 2, device=device, dtype=torch.float32),) * k
+        if any(tuple(t.shape) != (B, N, 2) for t in pos):
+            raise ValueError(f"pos must be {how} (B,N,2) {noun}")
+        if not spec.use_scale_embedding:
+            scales = (None,) * k
+        elif scales is None or any(t is None for t in scales):
+            raise ValueError("Model uses scale embedding but scales is passed as None.")   # transformer.py:547-548
+        elif any(t.numel() != B * N for t in scales):
+            raise ValueError(f"scales must be {how} (B,N) {noun}")
         with torch.cuda.device(device):
-            pr, pd = self._prep(patches_ref, device), self._prep(patches_dist, device)
-            qr, qd = self._prep(pos_ref, device), self._prep(pos_dist, device)
-            sr = self._prep(scales_ref, device) if use_scales else None
-            sdist = self._prep(scales_dist, device) if use_scales else None
+            prep = lambda ts: [None if t is None else self._prep(t, device) for t in ts]
+            return device, B, N, tokens_in, prep(patches), prep(pos), prep(scales)
+
+    def forward(self, patches, pos, scales, _trace: Optional[torch.Tensor] = None):
+        if self.training:
+            raise NotImplementedError(_TRAIN_MSG)
+        patches_ref, patches_dist = patches
+        device, B, N, tokens_in, (pr, pd), (qr, qd), (sr, sdist) = self._inputs((patches_ref, patches_dist), pos, scales)
+        with torch.cuda.device(device):
             q = torch.empty(B, device=device, dtype=torch.float32)
             stream = torch.cuda.current_stream(device).cuda_stream
 
@@ -559,9 +576,8 @@ class VTAMIQ(nn.Module):
                 if _trace is not None:
                     self._check(lib.vtq_set_token_trace(self._engine, _trace.data_ptr()))
                 try:
-                    self._check((lib.vtq_forward_tokens if tokens_in else lib.vtq_forward)(self._engine, pr.data_ptr(), pd.data_ptr(), qr.data_ptr(), qd.data_ptr(),
-                                               sr.data_ptr() if use_scales else None, sdist.data_ptr() if use_scales else None,
-                                               B, N, q.data_ptr(), stream))
+                    self._check((lib.vtq_forward_tokens if tokens_in else lib.vtq_forward)(
+                        self._engine, pr.data_ptr(), pd.data_ptr(), qr.data_ptr(), qd.data_ptr(), _ptr(sr), _ptr(sdist), B, N, q.data_ptr(), stream))
                 finally:
                     if _trace is not None:
                         lib.vtq_set_token_trace(self._engine, None)
@@ -576,38 +592,13 @@ class VTAMIQ(nn.Module):
             raise NotImplementedError("the MI355X engine implements the eval/no-grad forward only: call model.eval()")
         if len(patches) != 3 or (self.spec.use_pos_embedding and len(pos) != 3):
             raise ValueError("forward_pairwise expects (ref, dist1, dist2) triplets")
-        device = patches[0].device
-        if device.type != "cuda":
-            raise RuntimeError("VTAMIQ (vtamiq_amd) runs on an MI355X only: move the model and inputs to 'cuda'. "
-                               "There is no CPU fallback on the product path.")
-        B, N = patches[0].shape[:2]
-        # Embeddings.forward (transformer.py:527-535), as in forward(): 5-D tensors go through the patch convolution, 3-D ones are pre-embedded rows
-        tokens_in = patches[0].dim() != 5
-        for t in patches:
-            if tokens_in:
-                if tuple(t.shape) != (B, N, self.spec.hidden_size):
-                    raise ValueError(f"pre-embedded input must be three (B,N,{self.spec.hidden_size}) tensors, got {tuple(t.shape)}")
-            elif not self.spec.use_patch_embedding:
-                raise AttributeError("'Embeddings' object has no attribute 'patch_embeddings' (use_patch_embedding=False: pass pre-embedded (B,N,H) rows)")
-            elif tuple(t.shape) != (B, N, 3, self.spec.patch_size, self.spec.patch_size):
-                raise ValueError(f"patches must be three (B,N,3,P,P) tensors, got {tuple(t.shape)}")
-        if not self.spec.use_pos_embedding:            # as in forward(): `pos` is not looked at
-            pos = (torch.zeros(B, N, 2, device=device, dtype=torch.float32),) * 3
-        for t in pos:
-            if tuple(t.shape) != (B, N, 2):
-                raise ValueError("pos must be three (B,N,2) tensors")
-        use_scales = self.spec.use_scale_embedding
-        if use_scales and (scales is None or any(t is None for t in scales)):
-            raise ValueError("Model uses scale embedding but scales is passed as None.")
+        device, B, N, tokens_in, pt, ps, sc = self._inputs(patches, pos, scales, warn_grad=False)
         with torch.cuda.device(device):
-            pt = [self._prep(t, device) for t in patches]
-            ps = [self._prep(t, device) for t in pos]
-            sc = [self._prep(t, device) for t in scales] if use_scales else None
             q = torch.empty(2 * B, device=device, dtype=torch.float32)
             arr = lambda ts: (C.c_void_p * 3)(*[t.data_ptr() for t in ts])
             stream = torch.cuda.current_stream(device).cuda_stream
             self._launch_checked(device, lambda lib: self._check((lib.vtq_forward_pairwise_tokens if tokens_in else lib.vtq_forward_pairwise)(
-                self._engine, arr(pt), arr(ps), arr(sc) if use_scales else None, B, N, q.data_ptr(), stream)))
+                self._engine, arr(pt), arr(ps), arr(sc) if sc[0] is not None else None, B, N, q.data_ptr(), stream)))
         return q[:B], q[B:]
 
     def forward_vit(self, patches, patches_pos, patches_scale, tokens_only=True, adapter_num=None):
@@ -619,59 +610,27 @@ class VTAMIQ(nn.Module):
           attn_weights   transformer.encoder.return_attention: L (B, num_heads, S, S) softmax probabilities; else []
         All fp32 on the input device.  The flags are read at every call, so setting them after construction takes effect."""
         if self.training:
-            raise NotImplementedError(
-                "the MI355X engine implements the eval/no-grad forward only (Dropout/DropPath of vtamiq.py:72-75 and "
-                "channel_attention.py:26-29 are train-time stochastic; backward is out of scope): call model.eval()")
+            raise NotImplementedError(_TRAIN_MSG)
         if self._FP8_EXPERIMENT:
             raise NotImplementedError("forward_vit is not available for the fp8 experiment's model (it scores pairs only)")
         if adapter_num is not None and adapter_num >= 1 and self.spec.num_adapters > 0:
             # backbone.py:55-57: None / negative selects pair 0 when the model has adapters; a model without adapters ignores the number
             # (transformer.py:277-278), as the engine does
             raise NotImplementedError(f"adapter_num={adapter_num}: the engine applies adapter pair 0 only (adapter_num None, negative or 0)")
-        device = patches.device
-        if device.type != "cuda":
-            raise RuntimeError("VTAMIQ (vtamiq_amd) runs on an MI355X only: move the model and inputs to 'cuda'. "
-                               "There is no CPU fallback on the product path.")
-        if torch.is_grad_enabled() and not self._warned_grad and any(p.requires_grad for p in self.parameters()):
-            warnings.warn("vtamiq_amd.VTAMIQ.forward returns scores without an autograd graph (inference engine)")
-            self._warned_grad = True
-        spec = self.spec
-        tokens_in = patches.dim() != 5           # Embeddings.forward (transformer.py:527-535), as in forward()
-        if tokens_in:
-            if patches.dim() != 3 or patches.shape[2] != spec.hidden_size:
-                raise ValueError(f"pre-embedded input must be a (B,N,{spec.hidden_size}) tensor, got {tuple(patches.shape)}")
-            B, N = patches.shape[:2]
-        else:
-            if not spec.use_patch_embedding:
-                raise AttributeError("'Embeddings' object has no attribute 'patch_embeddings' (use_patch_embedding=False: pass pre-embedded (B,N,H) rows)")
-            B, N, Cc, P, P2 = patches.shape
-            if (Cc, P, P2) != (3, spec.patch_size, spec.patch_size):
-                raise ValueError(f"patch shape {(Cc, P, P2)} != (3,{spec.patch_size},{spec.patch_size})")
-        if not spec.use_pos_embedding:           # as in forward(): `pos` is not looked at
-            patches_pos = torch.zeros(B, N, 2, device=device, dtype=torch.float32)
-        if tuple(patches_pos.shape) != (B, N, 2):
-            raise ValueError("pos must be a (B,N,2) tensor")
-        use_scales = spec.use_scale_embedding
-        if use_scales:
-            if patches_scale is None:
-                raise ValueError("Model uses scale embedding but scales is passed as None.")   # transformer.py:547-548
-            if patches_scale.numel() != B * N:
-                raise ValueError("scales must be a (B,N) tensor")
-        enc = self.transformer.encoder
+        device, B, N, tokens_in, (pt,), (pp,), (ps,) = self._inputs((patches,), (patches_pos,), (patches_scale,))
+        spec, enc = self.spec, self.transformer.encoder
         want_states, want_probs = bool(enc.return_layers), bool(enc.return_attention)
         L, T, H, nh = spec.num_layers, spec.num_tokens, spec.hidden_size, spec.num_heads
         S = N + T
         R = T if tokens_only else S
         with torch.no_grad(), torch.cuda.device(device):
-            pt, pp = self._prep(patches, device), self._prep(patches_pos, device)
-            ps = self._prep(patches_scale, device) if use_scales else None
             x = torch.empty(B, R, H, device=device, dtype=torch.float32)
             states = torch.empty(L, B, R, H, device=device, dtype=torch.float32) if want_states else None
             probs = torch.empty(L, B, nh, S, S, device=device, dtype=torch.float32) if want_probs else None
             stream = torch.cuda.current_stream(device).cuda_stream
             self._launch_checked(device, lambda lib: self._check(lib.vtq_forward_vit(
-                self._engine, pt.data_ptr(), int(tokens_in), pp.data_ptr(), ps.data_ptr() if use_scales else None, B, N, int(not tokens_only),
-                x.data_ptr(), states.data_ptr() if want_states else None, probs.data_ptr() if want_probs else None, stream)))
+                self._engine, pt.data_ptr(), int(tokens_in), pp.data_ptr(), _ptr(ps), B, N, int(not tokens_only),
+                x.data_ptr(), _ptr(states), _ptr(probs), stream)))
         return x, (list(probs.unbind(0)) if want_probs else []), (list(states.unbind(0)) if want_states else [])
 
     # ---- measurement helpers (bench.py) ---------------------------------------------------------------------
