@@ -9,9 +9,13 @@
  *   - every pointer is a DEVICE pointer unless stated otherwise; the caller (torch) owns all inputs/outputs,
  *     the library owns only packed weights and its workspace;
  *   - all calls are asynchronous on the hipStream_t passed in (void* here so the header needs no HIP include);
- *     no internal synchronisation except where stated;
+ *     no internal synchronisation except where stated, and except ONE wait that any launching call may make: the first time a
+ *     process runs the persistent 256x256 GEMM at a new (device, tile grid) -- from vtq_reserve, from the top of a forward, or from
+ *     vtq_k_gemm -- its tile schedule (a few KiB) is uploaded on `stream` and the host waits for `stream` before the schedule enters
+ *     the process-wide cache, so that every later launch, on whichever stream of that device, finds it complete;
  *   - int return: 0 = ok, non-zero = error; text via vtq_last_error(); no exceptions cross the ABI;
- *   - a handle is not thread-safe; one process per GPU.
+ *   - a handle is not thread-safe: one thread at a time per handle.  Different handles may be used from different threads and on
+ *     different streams at the same time; what they share (the schedule cache, each kernel's first-use configuration) is guarded.
  */
 #ifndef VTAMIQ_HIP_H
 #define VTAMIQ_HIP_H

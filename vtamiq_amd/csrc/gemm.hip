@@ -841,7 +841,6 @@ struct DevSched { int* dev; int nwg; };
 hipError_t schedule_for(int ntm, int ntn, int cg, DevSched& ds, hipStream_t s) {
     static std::mutex mu;
     static std::map<std::tuple<int, int, int, int, int>, DevSched> cache;
-    static std::vector<std::vector<int>*> staged;              // host images of uploads in flight on some stream: kept for the process lifetime
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;
@@ -850,15 +849,17 @@ hipError_t schedule_for(int ntm, int ntn, int cg, DevSched& ds, hipStream_t s) {
     auto it = cache.find(key);
     if (it != cache.end()) { ds = it->second; return hipSuccess; }
     // First use of a shape on this device.  The engine does this from vtq_reserve / the top of vtq_forward (gemm_prepare), never
-    // between the launches of a forward; the per-kernel test entry points may land here from a launch.  The upload is an async
-    // copy on the launch stream (ordered before the kernel that reads it) from a host image that stays alive.
-    std::vector<int>* h = new std::vector<int>(build_schedule(ntm, ntn, cg));
+    // between the launches of a forward; the per-kernel test entry points may land here from a launch.  The cache serves EVERY
+    // stream of the device, so an entry is published only once its upload has COMPLETED: the copy goes onto the caller's stream
+    // and the host waits for that stream here, under the lock.  Whichever stream finds the entry later may launch at once, and
+    // the host image dies here.  Once per (device, shape) for the process lifetime; include/vtamiq_hip.h names this wait.
+    const std::vector<int> h = build_schedule(ntm, ntn, cg);
     DevSched d{nullptr, kXcds * cus_per_xcd()};
-    e = hipMalloc(&d.dev, h->size() * sizeof(int));
-    if (e != hipSuccess) { delete h; return e; }
-    e = hipMemcpyAsync(d.dev, h->data(), h->size() * sizeof(int), hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) { (void)hipFree(d.dev); delete h; return e; }
-    staged.push_back(h);
+    e = hipMalloc(&d.dev, h.size() * sizeof(int));
+    if (e != hipSuccess) return e;
+    e = hipMemcpyAsync(d.dev, h.data(), h.size() * sizeof(int), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) { (void)hipFree(d.dev); return e; }
     cache[key] = d;
     ds = d;
     return hipSuccess;
