@@ -279,6 +279,21 @@ int  vtq_k_skinny_linear(const void* xa, int64_t xa_plane, int32_t ldx, const vo
                          const float* aux, int32_t ldr, int32_t nsplit, float* y, int32_t ldy, int32_t ycols, void* ya, int64_t ya_plane,
                          int32_t ldya, int32_t pcol0, const float* next_slope, void* stream);
 
+/* The folded single-query attention of the CLS-only last layer (csrc/cls_tail.hip) with its value projection: for each of nseq sequences
+ * (S fp32 rows of H at x + r * seq_stride, in elements) and its one query q[r][H] (fp32; q_log2 != 0, 3-term formats only: already scaled by
+ * 1/sqrt(64) * log2(e)):
+ *     ctx[r][64h + d] = sum_s softmax_s(q_h . K_h[s] / sqrt(64)) V[s][64h + d],   K, V = the key / value projections of LayerNorm(x; ln_w, ln_b)
+ * evaluated WITHOUT forming K or V: scores against u = W_k,h^T q_h, a weighted sum of the normalised rows, then W_v of that sum.
+ * wqkv: the packed [3H][H] query | key | value weight as 16-bit planes of format `num` (VTQ_NUM_*), bqkv fp32 [3H] (only the value part is read:
+ * q . b_k is constant per head).  Caller workspace: u fp32 [nseq][H/64][H]; part fp32 [nseq][ceil(S / vtq_k_cls_fold_chunk_rows())][H/64][H + 2];
+ * z: 16-bit planes [planes of an activation][ceil64(nseq)][H/64 * H], z_plane elements apart.  ctx: fp32 [nseq][H].  H = 768 | 1024.
+ * A sequence's result depends on its own rows and on S only, never on nseq. */
+int  vtq_k_cls_fold(const float* q, const void* wqkv, int64_t w_plane, const float* bqkv, const float* x, int64_t seq_stride,
+                    const float* ln_w, const float* ln_b, int32_t nseq, int32_t S, int32_t H, int32_t num, int32_t q_log2,
+                    float* u, float* part, void* z, int64_t z_plane, float* ctx, void* stream);
+/* HOST-only: rows of a sequence per partial of vtq_k_cls_fold (a compile-time constant). */
+int  vtq_k_cls_fold_chunk_rows(void);
+
 /* The DiffNet head + quality predictor alone (quality_decoder -> q_predictor, vtamiq.py:114-117, channel_attention.py:13-86) with
  * the handle's loaded weights: d fp32 [HB][H] = diff_scale(cls_ref - cls_dist) -> q_out fp32 [HB]. */
 int  vtq_k_diffnet_head(vtq_handle h, const float* d, int32_t HB, float* q_out, void* stream);

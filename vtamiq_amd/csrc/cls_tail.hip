@@ -1,11 +1,12 @@
 // Last encoder layer, CLS row only.
 //
 // VTAMIQ consumes token 0 of the encoder output and nothing else (modules/vtamiq/vtamiq.py:104-108), so in the LAST
-// EncoderLayer (modules/VisionTransformer/transformer.py:275-285) only the K/V projections need every row; the query,
-// the attention output, out-proj, LayerNorm_2 and the MLP are needed for the 2B CLS rows alone.  This file holds the row
-// LayerNorm and the single-query attention of that tail; its four linear stages run on the MFMA pipe (skinny.hip).  Results are
-// identical in exact arithmetic to running the full layer and reading row 0 (SURVEY.md 8d allows the pruning; bench reports
-// executed flops).
+// EncoderLayer (modules/VisionTransformer/transformer.py:275-285) the query, the attention output, out-proj, LayerNorm_2 and the
+// MLP are needed for the 2B CLS rows alone -- and with ONE query per (sequence, head) the key and value projections of the other rows
+// fold into that query ("the folded single-query attention" below), so no other row is normalised into planes or projected: the layer
+// reads the fp32 residual rows once.  This file holds the row LayerNorm and that attention; the tail's five linear stages run on the
+// MFMA pipe (skinny.hip).  Results are identical in exact arithmetic to running the full layer and reading row 0 (SURVEY.md 8d allows
+// the pruning; bench reports executed flops).
 #include <mutex>
 
 #include "dev_common.h"
@@ -49,110 +50,283 @@ __global__ __launch_bounds__(256) void rows_ln_kernel(const float* __restrict__ 
     }
 }
 
-// attention of the single CLS query of each (sequence, head) over the S keys of the sequence; K, V from the packed 16-bit planes.
-// One 4-wave workgroup per (sequence, head): thread t scores keys t, t+256, ... (one 128-byte K row per plane per key); for the
-// PV sum thread t owns 8 output dims (t & 7) of key group t >> 3 and walks keys kg, kg+32, ... with 16-byte V loads, four keys
-// in flight; partial maxima / sums / outputs meet in LDS.
-template <typename T, int NPL>
-__global__ __launch_bounds__(256) void cls_attention_kernel(const float* __restrict__ q, const T* __restrict__ qkv, int64_t plane,
-                                                            float* __restrict__ out, int S, int S_pad, int H, PlaneOut po, int q_log2) {
-    typedef typename Vec<T>::x8 tx8;
-    extern __shared__ __attribute__((aligned(16))) float cls_smem[];     // [8] red | [32][64] part | [S] scores
-    float* red = cls_smem;
-    float (*part)[64] = (float (*)[64])(cls_smem + 8);
-    float* ps = cls_smem + 8 + 32 * 64;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int head = blockIdx.x, seq = blockIdx.y;
-    const int ld = 3 * H;
-    const T* kb = qkv + ((int64_t)seq * S_pad) * ld + H + head * 64;
-    const T* vb = kb + H;
-    // scores: 8 threads per key, each one 16-byte chunk of the key row, so a wave instruction reads 8 whole 128-byte rows (one
-    // thread per key made every load touch 64 different lines and thrashed the L1: 127 us at 64 x 501 x 12 heads)
-    const int kg = tid >> 3, dc = (tid & 7) * 8;
-    float qv[8];
-    {
-        const float4 t0 = *(const float4*)(q + (int64_t)seq * H + head * 64 + dc), t1 = *(const float4*)(q + (int64_t)seq * H + head * 64 + dc + 4);
-        qv[0] = t0.x; qv[1] = t0.y; qv[2] = t0.z; qv[3] = t0.w; qv[4] = t1.x; qv[5] = t1.y; qv[6] = t1.z; qv[7] = t1.w;
+// ---- the folded single-query attention of the tail ------------------------------------------------------------------
+// With one query per (sequence, head) the key and value projections re-associate exactly (ln_s = LayerNorm_1(x_s)):
+//   score[s,h] = q_h . (W_k,h ln_s + b_k,h) = (W_k,h^T q_h) . ln_s + const(h)          const(h) drops out of the softmax
+//   ctx_h      = sum_s p[s,h] (W_v,h ln_s + b_v,h) = W_v,h (sum_s p[s,h] ln_s) + b_v,h  (sum_s p = 1)
+// so the tail needs neither K nor V of any row: u = W_k^T q per (sequence, head) (cls_key_fold_kernel), one streaming pass over the
+// sequence's fp32 residual rows that normalises them and forms z_h = sum_s p[s,h] ln_s (cls_fold_attention_kernel, partials per
+// row chunk; cls_fold_combine_kernel), and the value projection of z on the skinny MFMA path (skinny.hip, xcol64).
+// Everything a result depends on -- chunk bounds, the order of every sum -- is a function of S alone: never of the number of
+// sequences, the CU count or arrival order (the scores of a pair do not depend on the batch it is in).
+constexpr int kFoldChunk = 64;     // rows of a sequence per partial (m, l, z)
+constexpr int kFoldSub = 32;       // rows normalised into LDS at a time (two per chunk, running maximum between them)
+constexpr int kFoldPad = 16;       // floats between LDS rows: the z product's B reads (4 rows x 16 columns per instruction) hit 64 different banks
+
+// u[r][h][:] = sum_d q[r][64 h + d] * W_k[64 h + d][:]: a combination of 64 weight rows (hi [+ lo] planes as float).
+// One workgroup of H threads per (head, 4 rows): the weight rows are read once for its 4 queries.  Thread (g, t) owns columns 4t .. 4t + 3
+// of the 16 weight rows d = 16 g .. 16 g + 15, all requested before the first is used (one exposed latency; walking the 64 rows in one
+// thread cost 45 us); the four row groups meet in LDS and are added in the order g = 0, 1, 2, 3.
+template <typename T, int WPL>
+__global__ __launch_bounds__(1024) void cls_key_fold_kernel(const float* __restrict__ q, const T* __restrict__ wk, int64_t w_plane, int ldw,
+                                                            float* __restrict__ u, int R, int H) {
+    typedef typename Vec<T>::x4 tx4;
+    __shared__ float qs[4][64];
+    __shared__ __attribute__((aligned(16))) float red[3][4][1024];
+    const int head = blockIdx.x, nh = gridDim.x, r0 = blockIdx.y * 4;
+    const int ct = H >> 2, g = threadIdx.x / ct, c = 4 * (threadIdx.x - g * ct);
+    const T* wr = wk + ((int64_t)head * 64 + g * 16) * ldw + c;
+    tx4 wh[16], wl[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        wh[i] = *(const tx4*)(wr + (int64_t)i * ldw);
+        if constexpr (WPL == 2) wl[i] = *(const tx4*)(wr + (int64_t)i * ldw + w_plane);
     }
+    if (threadIdx.x < 256) {
+        const int rr = threadIdx.x >> 6, d = threadIdx.x & 63;
+        qs[rr][d] = (r0 + rr < R) ? q[(int64_t)(r0 + rr) * H + head * 64 + d] : 0.f;
+    }
+    __syncthreads();
+    float acc[4][4];
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[rr][e] = 0.f;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        float w[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            w[e] = (float)wh[i][e];
+            if constexpr (WPL == 2) w[e] += (float)wl[i][e];
+        }
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) {
+            const float qd = qs[rr][g * 16 + i];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) acc[rr][e] = fmaf(qd, w[e], acc[rr][e]);
+        }
+    }
+    if (g > 0) {
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) *(float4*)&red[g - 1][rr][c] = float4{acc[rr][0], acc[rr][1], acc[rr][2], acc[rr][3]};
+    }
+    __syncthreads();
+    if (g > 0) return;
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const float4 o = *(const float4*)&red[k][rr][c];
+            acc[rr][0] += o.x; acc[rr][1] += o.y; acc[rr][2] += o.z; acc[rr][3] += o.w;
+        }
+        if (r0 + rr < R) *(float4*)(u + ((int64_t)(r0 + rr) * nh + head) * H + c) = float4{acc[rr][0], acc[rr][1], acc[rr][2], acc[rr][3]};
+    }
+}
+
+// One workgroup (8 waves) per (sequence, chunk of kFoldChunk rows): partial[seq][chunk] = z[nh][H] | (m, l)[nh] with
+//   m_h = max_s score[s,h],  l_h = sum_s e(score[s,h] - m_h),  z_h = sum_s e(score[s,h] - m_h) ln_s      (s over the chunk's rows < S)
+// and e = exp2 (q_log2: q arrived in log2 units) or exp of 0.125 * the dot product, as the attention kernels have it.  Per kFoldSub rows:
+//   1. wave w normalises rows 4w .. 4w+3 (the two-pass statistics of rows_ln_kernel) from registers into LDS; the next rows' global
+//      loads are issued behind the barrier and land under the products;
+//   2. scores [32 x 16 heads] = ln [32 x H] . u^T on the fp32-input MFMA (16x16x4): wave -> row block w & 1, quarter w >> 1 of H; the
+//      four quarters meet in LDS in a fixed order;
+//   3. running maximum per head, p = e(score - m), previous sums rescaled by e(m_old - m);
+//   4. z [16 heads x H] += p^T [16 x 32] . ln [32 x H] on the same MFMA: wave w owns the 16-column blocks w, w + 8, ...; l is the
+//      same product against a column of ones (wave 0), so it is summed in the same row order as z
+// Rows >= S are never read (p = 0 against zero rows); no other sequence's row is touched.
+template <int V4>
+__global__ __launch_bounds__(512) void cls_fold_attention_kernel(const float* __restrict__ x, int64_t seq_stride, const float* __restrict__ lw,
+                                                                 const float* __restrict__ lb, const float* __restrict__ u,
+                                                                 float* __restrict__ part, int S, int nh, int q_log2) {
+    constexpr int H = 256 * V4, LD = H + kFoldPad, NG = 4 * V4, NB = 2 * V4;
+    extern __shared__ __attribute__((aligned(16))) float fold_smem[];
+    float* rows = fold_smem;                                                         // [32][LD] normalised rows
+    float (*scp)[kFoldSub][16] = (float (*)[kFoldSub][16])(rows + kFoldSub * LD);    // [4][32][16] score parts of the quarters of H
+    float (*pr)[16] = (float (*)[16])(rows + kFoldSub * LD + 4 * kFoldSub * 16);     // [32][16] scores
+    float (*pp)[16] = (float (*)[16])(rows + kFoldSub * LD + 5 * kFoldSub * 16);     // [32][16] p
+    float* run = rows + kFoldSub * LD + 6 * kFoldSub * 16;                           // [2][16] running maximum (even / odd pass) | [16] rescale
+    const int tid = threadIdx.x, lane = tid & 63, fr = lane & 15, fq = lane >> 4;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int chunk = blockIdx.x, seq = blockIdx.y, c0 = chunk * kFoldChunk;
+    const float* xs = x + (int64_t)seq * seq_stride;
+    const int rb = wave & 1, kbase = (wave >> 1) * (H / 4);
+    // step 2's B operand: lane (head fr, k slot fq) holds u[head][kbase + 16 j + 4 fq + e] as element e of fragment j (heads >= nh: a copy
+    // of the last head, whose scores are dropped)
+    float4 uf[NG];
+    {
+        const float* ur = u + ((int64_t)seq * nh + (fr < nh ? fr : nh - 1)) * H + kbase + 4 * fq;
+#pragma unroll
+        for (int j = 0; j < NG; ++j) uf[j] = *(const float4*)(ur + 16 * j);
+    }
+    float4 v[4][V4];
+    auto load_rows = [&](int sub) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int srow = c0 + sub * kFoldSub + wave * 4 + i;
+            if (srow < S) {                                       // wave-uniform
+                const float4* xr = (const float4*)(xs + (int64_t)srow * H);
+#pragma unroll
+                for (int k = 0; k < V4; ++k) v[i][k] = xr[k * 64 + lane];
+            } else {
+#pragma unroll
+                for (int k = 0; k < V4; ++k) v[i][k] = float4{0.f, 0.f, 0.f, 0.f};
+            }
+        }
+    };
+    f32x4 acc[NB];
+#pragma unroll
+    for (int b = 0; b < NB; ++b) acc[b] = f32x4{0.f, 0.f, 0.f, 0.f};
+    f32x4 accl = {0.f, 0.f, 0.f, 0.f};                            // wave 0: l, as the product of p^T with a column of ones
+    if (tid < 16) run[tid] = -INFINITY;
+    const int left = S - c0;
+    const int nsub = left >= kFoldChunk ? kFoldChunk / kFoldSub : (left + kFoldSub - 1) / kFoldSub;
+    load_rows(0);
+    for (int sub = 0; sub < nsub; ++sub) {
+        const int s0 = c0 + sub * kFoldSub;
+        // 1. LayerNorm of this wave's four rows into LDS (weight and bias re-read per pass: L1 hits, and 8 V4 registers less across the products)
+        float4 w4[V4], b4[V4];
+#pragma unroll
+        for (int k = 0; k < V4; ++k) { w4[k] = ((const float4*)lw)[k * 64 + lane]; b4[k] = ((const float4*)lb)[k * 64 + lane]; }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int row = wave * 4 + i;
+            const bool live = s0 + row < S;
+            float s = 0.f;
+#pragma unroll
+            for (int k = 0; k < V4; ++k) s += (v[i][k].x + v[i][k].y) + (v[i][k].z + v[i][k].w);
+            const float mean = wave_sum(s) * (1.0f / H);
+            float qq = 0.f;
+#pragma unroll
+            for (int k = 0; k < V4; ++k) {
+                v[i][k].x -= mean; v[i][k].y -= mean; v[i][k].z -= mean; v[i][k].w -= mean;
+                qq += (v[i][k].x * v[i][k].x + v[i][k].y * v[i][k].y) + (v[i][k].z * v[i][k].z + v[i][k].w * v[i][k].w);
+            }
+            const float rstd = 1.0f / sqrtf(wave_sum(qq) * (1.0f / H) + 1e-6f);
+#pragma unroll
+            for (int k = 0; k < V4; ++k) {
+                float4 y = {v[i][k].x * rstd * w4[k].x + b4[k].x, v[i][k].y * rstd * w4[k].y + b4[k].y, v[i][k].z * rstd * w4[k].z + b4[k].z,
+                            v[i][k].w * rstd * w4[k].w + b4[k].w};
+                if (!live) y = float4{0.f, 0.f, 0.f, 0.f};
+                *(float4*)(rows + row * LD + (k * 64 + lane) * 4) = y;
+            }
+        }
+        __syncthreads();
+        if (sub + 1 < nsub) load_rows(sub + 1);
+        // 2. score parts of this wave's row block and quarter of H
+        {
+            f32x4 sa = {0.f, 0.f, 0.f, 0.f}, sb = {0.f, 0.f, 0.f, 0.f};
+            const float* ar = rows + (rb * 16 + fr) * LD + kbase + 4 * fq;
+#pragma unroll
+            for (int j = 0; j < NG; ++j) {
+                const float4 a = *(const float4*)(ar + 16 * j);
+                sa = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, uf[j].x, sa, 0, 0, 0);
+                sb = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, uf[j].y, sb, 0, 0, 0);
+                sa = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, uf[j].z, sa, 0, 0, 0);
+                sb = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, uf[j].w, sb, 0, 0, 0);
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) scp[wave >> 1][rb * 16 + 4 * fq + e][fr] = sa[e] + sb[e];      // D: row 4 fq + e, column (head) fr
+        }
+        __syncthreads();
+        // 3. thread (row, head): the score; the head's new maximum; p
+        const int row = tid >> 4, h = tid & 15;
+        {
+            float sc = (scp[0][row][h] + scp[1][row][h]) + (scp[2][row][h] + scp[3][row][h]);
+            if (!q_log2) sc *= 0.125f;
+            if (s0 + row >= S || h >= nh) sc = -INFINITY;
+            pr[row][h] = sc;
+        }
+        __syncthreads();
+        const float m_old = run[(sub & 1) * 16 + h];
+        float mx = m_old;
+#pragma unroll 8
+        for (int r = 0; r < kFoldSub; ++r) mx = fmaxf(mx, pr[r][h]);
+        {
+            const float d = pr[row][h] - mx;
+            pp[row][h] = h < nh ? (q_log2 ? exp2f(d) : expf(d)) : 0.f;
+            if (tid < 16) {
+                const float dm = m_old - mx;
+                run[((sub + 1) & 1) * 16 + h] = mx;
+                run[32 + h] = h < nh ? (q_log2 ? exp2f(dm) : expf(dm)) : 1.f;
+            }
+        }
+        __syncthreads();
+        // 4. z += p^T ln: A = p^T (lane: head fr, row 4 s + fq), B = ln (lane: row 4 s + fq, column n0 + fr)
+        {
+            if (sub > 0) {
+                const float4 al = *(const float4*)(run + 32 + 4 * fq);
+#pragma unroll
+                for (int b = 0; b < NB; ++b) { acc[b][0] *= al.x; acc[b][1] *= al.y; acc[b][2] *= al.z; acc[b][3] *= al.w; }
+                accl[0] *= al.x; accl[1] *= al.y; accl[2] *= al.z; accl[3] *= al.w;
+            }
+            float pa[kFoldSub / 4];
+#pragma unroll
+            for (int s = 0; s < kFoldSub / 4; ++s) pa[s] = pp[4 * s + fq][fr];
+#pragma unroll
+            for (int s = 0; s < kFoldSub / 4; ++s) {
+                const float* br = rows + (4 * s + fq) * LD + 16 * wave + fr;
+#pragma unroll
+                for (int b = 0; b < NB; ++b) acc[b] = __builtin_amdgcn_mfma_f32_16x16x4f32(pa[s], br[128 * b], acc[b], 0, 0, 0);
+                if (wave == 0) accl = __builtin_amdgcn_mfma_f32_16x16x4f32(pa[s], 1.0f, accl, 0, 0, 0);
+            }
+        }
+        __syncthreads();
+    }
+    float* pz = part + ((int64_t)seq * gridDim.x + chunk) * nh * (H + 2);
+#pragma unroll
+    for (int b = 0; b < NB; ++b)
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            if (4 * fq + e < nh) pz[(4 * fq + e) * H + 16 * wave + 128 * b + fr] = acc[b][e];       // D: row (head) 4 fq + e, column fr
+    if (tid < nh) pz[nh * H + 2 * tid] = run[(nsub & 1) * 16 + tid];
+    if (wave == 0 && fr == 0) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            if (4 * fq + e < nh) pz[nh * H + 2 * (4 * fq + e) + 1] = accl[e];
+    }
+}
+
+// zbar[seq][h][:] = sum_c e(m_c - m) z_c / sum_c e(m_c - m) l_c over the sequence's chunks in ascending order, written as the operand
+// planes of the value projection (row seq, columns h H ..).  One workgroup per (head, sequence), thread t owns columns 4t .. 4t + 3.
+__global__ __launch_bounds__(256) void cls_fold_combine_kernel(const float* __restrict__ part, int nchunks, int H, PlaneOut po, int q_log2) {
+    const int head = blockIdx.x, nh = gridDim.x, seq = blockIdx.y, c4 = 4 * threadIdx.x;
+    if (c4 >= H) return;
+    const int64_t ps = (int64_t)nh * (H + 2);
+    const float* pb = part + (int64_t)seq * nchunks * ps;
+    const float* ml = pb + (int64_t)nh * H + 2 * head;
+    // loads in batches (a chunk index past the end re-reads the last chunk and is not used): a loop of single dependent loads cost one
+    // memory latency per chunk
     float mx = -INFINITY;
-    auto score_key = [&](int key) {
-        const T* kr = kb + (int64_t)key * ld + dc;
-        const tx8 kh = *(const tx8*)kr;
-        tx8 kl;
-        if constexpr (NPL == 2) kl = *(const tx8*)(kr + plane);
-        float sc = 0.f;
+    for (int c0 = 0; c0 < nchunks; c0 += 8) {
+        float mv[8];
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            float kv = (float)kh[e];
-            if constexpr (NPL == 2) kv += (float)kl[e];
-            sc += qv[e] * kv;
-        }
-        return sc;
-    };
-    auto finish = [&](int key, float sc) {
-        sc += __shfl_xor(sc, 1, 64);
-        sc += __shfl_xor(sc, 2, 64);
-        sc += __shfl_xor(sc, 4, 64);
-        if (!q_log2) sc *= 0.125f;                     // q_log2: the scale (and log2 e) came with q
-        if ((tid & 7) == 0) ps[key] = sc;
-        mx = fmaxf(mx, sc);
-    };
-    {
-        int key = kg;
-        for (; key + 96 < S; key += 128) {
-            const float s0 = score_key(key), s1 = score_key(key + 32), s2 = score_key(key + 64), s3 = score_key(key + 96);
-            finish(key, s0); finish(key + 32, s1); finish(key + 64, s2); finish(key + 96, s3);
-        }
-        for (; key < S; key += 32) finish(key, score_key(key));
+        for (int i = 0; i < 8; ++i) mv[i] = ml[(c0 + i < nchunks ? c0 + i : nchunks - 1) * ps];
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+            if (c0 + i < nchunks) mx = fmaxf(mx, mv[i]);
     }
+    float l = 0.f, z[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int c0 = 0; c0 < nchunks; c0 += 4) {
+        float mv[4], lv[4];
+        float4 zc[4];
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-    if (lane == 0) red[wave] = mx;
-    __syncthreads();
-    mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    float sum = 0.f;
-    for (int key = tid; key < S; key += 256) {
-        const float p = q_log2 ? exp2f(ps[key] - mx) : expf(ps[key] - mx);
-        ps[key] = p;
-        sum += p;
-    }
-    sum = wave_sum(sum);
-    if (lane == 0) red[4 + wave] = sum;
-    __syncthreads();
-    sum = (red[4] + red[5]) + (red[6] + red[7]);
-    // out[d] = sum_key p[key] * V[key][d]
-    float o[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    auto acc_key = [&](int key) {
-        const T* vr = vb + (int64_t)key * ld + dc;
-        const tx8 vh = *(const tx8*)vr;
-        tx8 vl;
-        if constexpr (NPL == 2) vl = *(const tx8*)(vr + plane);
-        const float pk = ps[key];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            float vv = (float)vh[e];
-            if constexpr (NPL == 2) vv += (float)vl[e];
-            o[e] += pk * vv;
+        for (int i = 0; i < 4; ++i) {
+            const int64_t o = (c0 + i < nchunks ? c0 + i : nchunks - 1) * ps;
+            mv[i] = ml[o]; lv[i] = ml[o + 1];
+            zc[i] = *(const float4*)(pb + o + (int64_t)head * H + c4);
         }
-    };
-    int key = kg;
-    for (; key + 96 < S; key += 128) { acc_key(key); acc_key(key + 32); acc_key(key + 64); acc_key(key + 96); }
-    for (; key < S; key += 32) acc_key(key);
 #pragma unroll
-    for (int e = 0; e < 8; ++e) part[kg][dc + e] = o[e];
-    __syncthreads();
-    if (tid < 16) {
-        float t[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int g = 0; g < 32; ++g) {
-            const float4 pv = *(const float4*)&part[g][4 * tid];
-            t[0] += pv.x; t[1] += pv.y; t[2] += pv.z; t[3] += pv.w;
+        for (int i = 0; i < 4; ++i) {
+            if (c0 + i >= nchunks) break;
+            const float d = mv[i] - mx;
+            const float w = q_log2 ? exp2f(d) : expf(d);
+            l = fmaf(w, lv[i], l);
+            z[0] = fmaf(w, zc[i].x, z[0]); z[1] = fmaf(w, zc[i].y, z[1]); z[2] = fmaf(w, zc[i].z, z[2]); z[3] = fmaf(w, zc[i].w, z[3]);
         }
-        const float inv = 1.0f / sum;
-        const int col = head * 64 + 4 * tid;
-        if (out) *(float4*)(out + (int64_t)seq * H + col) = float4{t[0] * inv, t[1] * inv, t[2] * inv, t[3] * inv};
-        plane_store4(po, seq, col, t[0] * inv, t[1] * inv, t[2] * inv, t[3] * inv);
     }
+    const float inv = 1.0f / l;
+    plane_store4(po, seq, head * H + c4, z[0] * inv, z[1] * inv, z[2] * inv, z[3] * inv);
 }
 
 }  // namespace
@@ -166,14 +340,14 @@ hipError_t launch_rows_ln(const float* src, int64_t stride, const float* w, cons
     return hipGetLastError();
 }
 
+int cls_fold_chunk_rows() { return kFoldChunk; }
+
 namespace {
-constexpr int kClsLdsMax = 160 * 1024 - 4096;                 // leave room for the runtime's own LDS use
-constexpr int kClsFixed = (8 + 32 * 64) * 4;
-template <typename T, int NPL>
-hipError_t launch_cls_attention_t(const float* q, const void* qkv, int64_t plane, float* out, int nseq, int S, int S_pad, int H,
-                                  PlaneOut po, hipStream_t s, bool q_log2) {
-    const int lds = kClsFixed + ((S + 3) & ~3) * 4;
-    if (lds > 48 * 1024) {                                    // beyond the default limit: raise it once per device
+template <int V4>
+hipError_t launch_fold_attention(const float* x, int64_t seq_stride, const float* lw, const float* lb, const float* u, float* part, int nseq,
+                                 int S, int nh, int q_log2, hipStream_t s) {
+    constexpr int lds = (kFoldSub * (256 * V4 + kFoldPad) + 6 * kFoldSub * 16 + 48) * 4;
+    {   // beyond the default dynamic-LDS limit: raise it once per device
         static std::mutex mu;
         static bool configured[64] = {false};
         int dev = 0;
@@ -182,25 +356,35 @@ hipError_t launch_cls_attention_t(const float* q, const void* qkv, int64_t plane
         std::lock_guard<std::mutex> lk(mu);
         if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
         if (!configured[dev]) {
-            e = hipFuncSetAttribute((const void*)cls_attention_kernel<T, NPL>, hipFuncAttributeMaxDynamicSharedMemorySize, kClsLdsMax);
+            e = hipFuncSetAttribute((const void*)cls_fold_attention_kernel<V4>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
             if (e != hipSuccess) return e;
             configured[dev] = true;
         }
     }
-    hipLaunchKernelGGL((cls_attention_kernel<T, NPL>), dim3(H / 64, nseq), dim3(256), lds, s, q, (const T*)qkv, plane, out, S, S_pad, H, po, q_log2 ? 1 : 0);
+    hipLaunchKernelGGL((cls_fold_attention_kernel<V4>), dim3((S + kFoldChunk - 1) / kFoldChunk, nseq), dim3(512), lds, s, x, seq_stride, lw, lb, u,
+                       part, S, nh, q_log2);
     return hipGetLastError();
 }
 }  // namespace
 
-int cls_attention_max_seq() { return (kClsLdsMax - kClsFixed) / 4; }
-
-hipError_t launch_cls_attention(const float* q, const void* qkv, int64_t plane, float* out, int nseq, int S, int S_pad, int H,
-                                int f16_, int planes, PlaneOut po, hipStream_t s, bool q_log2) {
-    if (S < 1 || S > cls_attention_max_seq() || (planes != 1 && planes != 2)) return hipErrorInvalidValue;
-    if (!f16_) return planes == 1 ? launch_cls_attention_t<bf16, 1>(q, qkv, plane, out, nseq, S, S_pad, H, po, s, q_log2)
-                                  : launch_cls_attention_t<bf16, 2>(q, qkv, plane, out, nseq, S, S_pad, H, po, s, q_log2);
-    return planes == 1 ? launch_cls_attention_t<f16, 1>(q, qkv, plane, out, nseq, S, S_pad, H, po, s, q_log2)
-                       : launch_cls_attention_t<f16, 2>(q, qkv, plane, out, nseq, S, S_pad, H, po, s, q_log2);
+hipError_t launch_cls_fold(const float* q, const void* wk, int64_t w_plane, int ldw, int f16_, int wplanes, const float* x, int64_t seq_stride,
+                           const float* lw, const float* lb, float* u, float* part, int nseq, int S, int H, PlaneOut zo, hipStream_t s,
+                           bool q_log2) {
+    if (nseq < 1 || S < 1 || (H != 768 && H != 1024) || ldw < H || ldw % 4 || (wplanes != 1 && wplanes != 2) || seq_stride % 4 || !zo.p || zo.ld < (H / 64) * H)
+        return hipErrorInvalidValue;
+    const int nh = H / 64, nchunks = (S + kFoldChunk - 1) / kFoldChunk;
+    const dim3 gk(nh, (nseq + 3) / 4), blk(256);
+#define VTQ_KF(TT, NP) hipLaunchKernelGGL((cls_key_fold_kernel<TT, NP>), gk, dim3(H), 0, s, q, (const TT*)wk, w_plane, ldw, u, nseq, H)
+    if (!f16_) { if (wplanes == 1) VTQ_KF(bf16, 1); else VTQ_KF(bf16, 2); }
+    else { if (wplanes == 1) VTQ_KF(f16, 1); else VTQ_KF(f16, 2); }
+#undef VTQ_KF
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    e = H == 768 ? launch_fold_attention<3>(x, seq_stride, lw, lb, u, part, nseq, S, nh, q_log2 ? 1 : 0, s)
+                 : launch_fold_attention<4>(x, seq_stride, lw, lb, u, part, nseq, S, nh, q_log2 ? 1 : 0, s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(cls_fold_combine_kernel, dim3(nh, nseq), blk, 0, s, (const float*)part, nchunks, H, zo, q_log2 ? 1 : 0);
+    return hipGetLastError();
 }
 
 }  // namespace vtq

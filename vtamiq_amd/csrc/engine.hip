@@ -153,6 +153,9 @@ struct vtq_engine {
     void *tl = nullptr, *th = nullptr;   // CLS-tail planes (encoder format): [r_alloc][H], [r_alloc][M]
     int64_t tl_plane = 0, th_plane = 0;
     float *xcls = nullptr, *lncls = nullptr, *qcls = nullptr;   // CLS-only last layer (fp32 rows)
+    float *fold_u = nullptr, *fold_part = nullptr;              //   folded attention (cls_tail.hip): W_k^T q per (sequence, head); chunk partials
+    void* fold_z = nullptr;                                      //   its output planes (encoder format): [r_alloc][H / 64 * H]
+    int64_t fold_z_plane = 0;
     bool cls_prune = true;
     bool fuse_ln = false;                // VTQ_OPT_FUSED_LAYERNORM: residual GEMMs carry the next LayerNorm in their epilogue (gemm_rowln.hip)
     int32_t* err_host = nullptr;         // pinned landing word of vtq_input_errors (a pageable destination goes through the runtime's staging path)
@@ -362,6 +365,7 @@ std::vector<WsBuf> workspace(vtq_engine* e, int B, int N) {
     const Geometry g = geometry(e, B, N);
     const int64_t H = e->H, Md = e->Mdim, Wmax = (3 * H > Md ? 3 * H : Md), rows = g.rows_alloc, R = g.R_pad;
     const int apl = e->apl;
+    const int64_t nh = H / 64, chunks = (g.S + cls_fold_chunk_rows() - 1) / cls_fold_chunk_rows();
     std::vector<WsBuf> w = {
         {(void**)&e->x, nullptr, rows * H, 4, 1, true},                       // residual stream fp32
         {&e->lnbuf, &e->ln_plane, rows * H, 2, apl, true},                    // LayerNorm / attention output planes
@@ -379,6 +383,9 @@ std::vector<WsBuf> workspace(vtq_engine* e, int B, int N) {
         {&e->hq, &e->hq_plane, R * (H / 4), 2, 2, true},
         {&e->tl, &e->tl_plane, R * H, 2, apl, true},                          // CLS-tail planes (encoder format)
         {&e->th, &e->th_plane, R * Md, 2, apl, true},
+        {(void**)&e->fold_u, nullptr, g.nseq * nh * H, 4, 1, false},          // folded attention of the CLS-only last layer
+        {(void**)&e->fold_part, nullptr, g.nseq * chunks * nh * (H + 2), 4, 1, false},
+        {&e->fold_z, &e->fold_z_plane, R * nh * H, 2, apl, true},
     };
     for (float*& hb : e->hb) w.push_back({(void**)&hb, nullptr, g.nseq * H, 4, 1, false});   // head ping-pong rows
     return w;
@@ -504,15 +511,12 @@ int run_encoder(vtq_engine* e, const Geometry& g, hipStream_t s, bool prune) {
     };
     for (int i = 0; i < L; ++i) {
         const Layer& Ly = e->layers[i];
-        if (!(fused && i > 0) && layernorm(Ly.ln1w, Ly.ln1b, e->s_ln1[i])) return 1;
-        if (prune && i == L - 1) {
-            // ---- last layer: K/V for every row, everything else for the 2B CLS rows only (cls_tail.hip) ------------
+        const bool tail = prune && i == L - 1;
+        if (!(fused && i > 0) && !tail && layernorm(Ly.ln1w, Ly.ln1b, e->s_ln1[i])) return 1;
+        if (tail) {
+            // ---- last layer: the R consumed rows only (cls_tail.hip).  Their one query per head is folded into the key and value
+            // projections, so no other row is normalised or projected: the attention streams the fp32 residual rows themselves
             const int R = g.nseq;
-            {   // key and value projections: rows H .. 3H-1 of the packed QKV weight, into their columns of the QKV planes
-                Prof p(e, s, VTQ_K_QKV);
-                const View kv{(char*)e->big + (size_t)H * 2, e->big_plane, 3 * H};
-                HIP_TRY(launch_gemm(gemm_args(lnv(H), lin_rows(Ly.qkv, H, 2 * H), M, kv), lin, EPI_BIAS, s));
-            }
             {
                 Prof p(e, s, VTQ_K_HEAD);
                 // skinny MFMA stages on the R CLS rows (skinny.hip); activations between them as planes in the encoder's format
@@ -524,7 +528,17 @@ int run_encoder(vtq_engine* e, const Geometry& g, hipStream_t s, bool prune) {
                     a.epi = SK_PLAIN; a.y = qcls; a.ldy = H; a.ycols = H;
                     HIP_TRY(launch_skinny(a, lin, s));
                 }
-                HIP_TRY(launch_cls_attention(qcls, e->big, e->big_plane, nullptr, R, g.S, g.S_pad, H, f16, apl, tl, s, e->att.terms == 3));
+                {   // u = W_k^T q (rows H .. 2H-1 of the packed QKV weight; q . b_k is constant per head); zbar = softmax-weighted LayerNorm rows
+                    const Lin wk = lin_rows(Ly.qkv, H, H);
+                    const PlaneOut zo{e->fold_z, e->fold_z_plane, (H / 64) * H, f16, apl, nullptr};
+                    HIP_TRY(launch_cls_fold(qcls, wk.w, wk.plane, wk.K, f16, e->wpl, x, (int64_t)g.S_pad * H, Ly.ln1w, Ly.ln1b, e->fold_u, e->fold_part,
+                                            R, g.S, H, zo, s, e->att.terms == 3));
+                }
+                {   // value projection: ctx[64h ..] = W_v,h zbar_h + b_v (rows 2H .. 3H-1), head h reading columns h H .. of its row
+                    SkinnyArgs a = skinny_args(View{e->fold_z, e->fold_z_plane, (H / 64) * H}, lin_rows(Ly.qkv, 2 * H, H), R, apl);
+                    a.xcol64 = H; a.epi = SK_PLAIN; a.ya = e->tl; a.ya_plane = e->tl_plane; a.ldya = H;
+                    HIP_TRY(launch_skinny(a, lin, s));
+                }
                 {   // out-proj + LayerScale + residual, in place on the CLS rows
                     SkinnyArgs a = skinny_args(tlv, Ly.out, R, apl);
                     a.epi = SK_RESID; a.gamma = Ly.g1; a.res = xcls; a.ldr = H; a.y = xcls; a.ldy = H; a.ycols = H;
@@ -580,6 +594,7 @@ int run_encoder(vtq_engine* e, const Geometry& g, hipStream_t s, bool prune) {
             // the CLS rows).  LayerNorm 2's planes are consumed: `lnbuf` is the spare buffer
             Prof p(e, s, VTQ_K_FC2);
             const Layer* nx = (i + 1 < L) ? &e->layers[i + 1] : nullptr;
+            if (prune && i + 1 == L - 1) nx = nullptr;              // the CLS-only last layer normalises the rows it reads itself
             if (residual(bigv(Md), lnv(H), Ly.fc2, 1.0f / e->s_gelu[i], Ly.g2, nx ? nx->ln1w : nullptr, nx ? nx->ln1b : nullptr, Ly, 1)) return 1;
         }
         if (e->dbg_stop == i * 7 + 6) return 0;
@@ -972,11 +987,10 @@ static int forward_impl(vtq_handle e, int nimg, const float* const* patches, con
         HIP_TRY(hipMemsetAsync((char*)e->big + ((size_t)pl * e->big_plane + (size_t)g.M_pad * 3 * H) * 2, 0, (size_t)128 * 3 * H * 2, s));
 
     // ---- encoder (transformer.py:363-378, 275-285) -------------------------------------------------------------
-    // the trace tap needs every token row of the last layer; sequences longer than the CLS kernel's LDS score buffer run the
-    // full last layer instead (same result)
+    // the trace tap needs every token row of the last layer (the CLS-only tail itself takes any sequence length)
     // (fp8 mode runs the full last layer: its CLS row then goes through the same e4m3 GEMMs as every other row)
     // (forward_vit needs every row of the last layer: always the full last layer)
-    const bool prune = e->cls_prune && !e->trace && !e->fp8 && c.num_adapters == 0 && g.S <= cls_attention_max_seq() && nimg > 1;
+    const bool prune = e->cls_prune && !e->trace && !e->fp8 && c.num_adapters == 0 && nimg > 1;
     if (run_encoder(e, g, s, prune)) return 1;
     if (nimg == 1) {                 // ---- forward_vit: encoder_norm (transformer.py:376) of the requested rows, no head
         Prof p(e, s, VTQ_K_LN);
@@ -1208,6 +1222,28 @@ int vtq_k_skinny_linear(const void* xa, int64_t xa_plane, int32_t ldx, const voi
     a.y = y; a.ldy = ldy; a.ycols = ycols; a.ya = ya; a.ya_plane = ya_plane; a.ldya = ldya; a.ya_planes = nm.apl(); a.pcol0 = pcol0;
     a.next_slope = next_slope;
     HIP_TRY(launch_skinny(a, nm, (hipStream_t)stream));
+    return 0;
+}
+
+int vtq_k_cls_fold_chunk_rows(void) { return cls_fold_chunk_rows(); }
+
+int vtq_k_cls_fold(const float* q, const void* wqkv, int64_t w_plane, const float* bqkv, const float* x, int64_t seq_stride, const float* ln_w,
+                   const float* ln_b, int32_t nseq, int32_t S, int32_t H, int32_t num, int32_t q_log2, float* u, float* part, void* z,
+                   int64_t z_plane, float* ctx, void* stream) {
+    const Num nm = num_from_code(num);
+    if (!num_valid(nm) || nm.f16 > 1) return fail("vtq_k_cls_fold: operand format code %d", num);
+    if (!q || !wqkv || !bqkv || !x || !ln_w || !ln_b || !u || !part || !z || !ctx || nseq < 1 || S < 1 || (H != 768 && H != 1024))
+        return fail("vtq_k_cls_fold: bad argument");
+    if (q_log2 && nm.terms != 3) return fail("vtq_k_cls_fold: q_log2 applies to the 3-term formats only");
+    hipStream_t s = (hipStream_t)stream;
+    const int nh = H / 64;
+    const PlaneOut zo{z, z_plane, nh * H, nm.f16, nm.apl(), nullptr};
+    HIP_TRY(launch_cls_fold(q, (const char*)wqkv + (size_t)H * H * 2, w_plane, H, nm.f16, nm.wpl(), x, seq_stride, ln_w, ln_b, u, part, nseq, S, H, zo, s,
+                            q_log2 != 0));
+    SkinnyArgs a{};
+    a.xa = z; a.xa_plane = z_plane; a.ldx = nh * H; a.xcol64 = H; a.W = (const char*)wqkv + (size_t)2 * H * H * 2; a.w_plane = w_plane;
+    a.R = nseq; a.N = H; a.K = H; a.bias = bqkv + 2 * H; a.epi = SK_PLAIN; a.y = ctx; a.ldy = H; a.ycols = H; a.ya_planes = nm.apl();
+    HIP_TRY(launch_skinny(a, nm, s));
     return 0;
 }
 

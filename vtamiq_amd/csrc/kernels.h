@@ -162,6 +162,7 @@ hipError_t launch_fold_ca(const float* Wc, const float* bc, const float* Wd, con
 enum { SK_PLAIN = 0, SK_GELU = 1, SK_PRELU = 2, SK_RESID = 3, SK_GATE = 4, SK_CONVCAT = 5 };
 struct SkinnyArgs {
     const void* xa; int64_t xa_plane; int ldx;    // activation planes [apl][>= ceil64(R)][ldx] (16-bit), ldx >= K, ldx % 8 == 0
+    int xcol64;                                   // output channels 64 g .. 64 g + 63 read columns g * xcol64 .. + K - 1 of their row (0: all the same K columns)
     const void* W; int64_t w_plane;               // weight planes [wpl][ceil16(N)][K]
     int R, N, K;                                  // valid rows / outputs; K % 32 == 0 (zero-padded)
     const float* bias;                            // [N]
@@ -185,12 +186,16 @@ hipError_t launch_rows_to_planes(const float* x, int ldx, const float* slope, vo
 // ---- CLS-only tail of the last encoder layer (cls_tail.hip) -----------------------------------------------------------
 hipError_t launch_rows_ln(const float* src, int64_t stride, const float* w, const float* b, float* ln, float* copy, int rows, int H,
                           PlaneOut po, hipStream_t s);
-// K, V rows of the packed qkv planes (f16, planes); any S (the score buffer is dynamic LDS)
-// q_log2: q already carries 1/sqrt(64) * log2(e) (see launch_attention)
-hipError_t launch_cls_attention(const float* q, const void* qkv, int64_t plane, float* out, int nseq, int S, int S_pad, int H,
-                                int f16, int planes, PlaneOut po, hipStream_t s, bool q_log2 = false);
-// largest S launch_cls_attention accepts (LDS score buffer); longer sequences run the full last layer instead
-int cls_attention_max_seq();
+// Folded single-query attention of the tail (cls_tail.hip): with one query per (sequence, head) K and V are never formed.
+//   u[r][h][:] = W_k,h^T q[r][64h ..]   (wk: rows H .. 2H-1 of the packed QKV weight, `wplanes` planes of row pitch ldw, f16 as elsewhere)
+//   per sequence r, over its S fp32 rows x + r * seq_stride + s * H normalised with (lw, lb): softmax_s(u . ln_s) weighted sum of ln_s,
+//   written through zo as planes [r][h * H + c] (ld >= (H / 64) * H): the operand of the value projection (SkinnyArgs::xcol64 = H).
+// q_log2: q carries 1/sqrt(64) * log2(e) (see launch_attention).  Workspace: u fp32 [nseq][H / 64][H];
+// part fp32 [nseq][ceil(S / cls_fold_chunk_rows())][H / 64][H + 2].  H = 768 | 1024; any S.  A sequence's result depends on S alone.
+hipError_t launch_cls_fold(const float* q, const void* wk, int64_t w_plane, int ldw, int f16, int wplanes, const float* x, int64_t seq_stride,
+                           const float* lw, const float* lb, float* u, float* part, int nseq, int S, int H, PlaneOut zo, hipStream_t s,
+                           bool q_log2 = false);
+int cls_fold_chunk_rows();
 
 // ---- on-device image -> patch tensor (patches.hip) -------------------------------------------------------
 hipError_t launch_image_normalize(const uint8_t* in, float* out, int NI, int H, int W, const int* flips, const float* mean, const float* sd,

@@ -1,7 +1,8 @@
 // Skinny linear layers on the MFMA pipe: out[R, N] = act[R, K] * W[N, K]^T for a FEW rows (R = the batch's CLS rows).
 //
 // Two users, both chains of small dependent stages:
-//   * the CLS-only tail of the last encoder layer (query projection, out-proj, fc1, fc2 for the 2B CLS rows;
+//   * the CLS-only tail of the last encoder layer (query projection, value projection of the folded attention's per-head sums --
+//     SkinnyArgs::xcol64: each 64 output channels read their own K columns of a row --, out-proj, fc1, fc2 for the 2B CLS rows;
 //     modules/VisionTransformer/transformer.py:275-285 restricted to token 0, see cls_tail.hip), and
 //   * the DiffNet head + quality predictor on the [B, H] CLS difference (modules/vtamiq/vtamiq.py:12-23, 71-77, 111-117,
 //     modules/RCAN/channel_attention.py:13-86: every Conv1d(k=1) on (B, C, 1) is such a product).
@@ -35,7 +36,7 @@ __global__ __launch_bounds__(512) void skinny_linear_kernel(SkinnyArgs p) {   //
     const int fr = lane & 15, fq = lane >> 4;
     const int n0 = blockIdx.x * 16, r0 = blockIdx.y * (16 * RB);
     const T* wrow = (const T*)p.W + (int64_t)(n0 + fr) * p.K + 8 * fq;
-    const T* xrow = (const T*)p.xa + (int64_t)(r0 + fr) * p.ldx + 8 * fq;
+    const T* xrow = (const T*)p.xa + (int64_t)(r0 + fr) * p.ldx + (int64_t)(n0 >> 6) * p.xcol64 + 8 * fq;
     f32x4 acc[RB];
 #pragma unroll
     for (int rb = 0; rb < RB; ++rb) acc[rb] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -171,7 +172,7 @@ __global__ __launch_bounds__(256) void rows_to_planes_kernel(const float* __rest
 }  // namespace
 
 hipError_t launch_skinny(const SkinnyArgs& a, Num num, hipStream_t s) {
-    if (a.R < 1 || a.N < 1 || a.K < 32 || a.K % 32 || a.ldx % 8 || (a.ya && (a.pcol0 % 4 || a.ldya % 4)) || !num_valid(num)) return hipErrorInvalidValue;
+    if (a.R < 1 || a.N < 1 || a.K < 32 || a.K % 32 || a.ldx % 8 || a.xcol64 % 8 || (a.ya && (a.pcol0 % 4 || a.ldya % 4)) || !num_valid(num)) return hipErrorInvalidValue;
     // Rows per workgroup: every workgroup pulls its rows' activations through its CU's L1 (64 B / clk), which is what a stage's time is made
     // of beyond the exposed latency, so split the rows over workgroups (16 each) while the grid still fits the 256 CUs in one round, and
     // take 32 / 64 rows per workgroup for the wide stages (the tail's fc1).  The result does not depend on the choice: a row's sums are

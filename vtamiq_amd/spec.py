@@ -109,14 +109,16 @@ class ModelSpec:
 
     def flops_per_pair_executed(self, num_patches: int, cls_prune: bool = True) -> float:
         """Dense flops the engine actually executes per pair.  With the CLS-only last layer (only token 0 is consumed,
-        vtamiq.py:107-108) the last layer keeps the K/V projections for every row and runs Q, attention, out-proj and the
-        MLP for one row per image."""
+        vtamiq.py:107-108) the last layer runs Q, out-proj and the MLP for one row per image, and its attention with the one query
+        folded into the key and value projections (csrc/cls_tail.hip): per image W_k^T q and W_v zbar (2 H H each, in place of the
+        4 S H H of K and V for every row) and, in fp32, one dot product and one axpy of length H per row and head (4 S H nh; 8 S H nh
+        per pair) in place of the 4 S H of attention on formed K / V."""
         if not cls_prune or self.num_adapters > 0:      # the engine runs the full last layer when adapters are on
             return self.flops_per_pair(num_patches)
         H, M = self.hidden_size, self.mlp_dim
         S = self.seq_len(num_patches)
         full_last = 8.0 * S * H * H + 4.0 * S * H * M + 4.0 * S * S * H
-        pruned_last = 4.0 * S * H * H + (4.0 * H * H + 4.0 * H * M + 4.0 * S * H)
+        pruned_last = 4.0 * S * H * self.num_heads + (8.0 * H * H + 4.0 * H * M)
         return self.flops_per_pair(num_patches) - 2.0 * (full_last - pruned_last)
 
     # ---- state_dict layout (reference key names; SURVEY.md section 8b) -----------------------
