@@ -222,12 +222,23 @@ int  vtq_profile_enable(vtq_handle h, uint32_t class_mask);
 /* Synchronises the recorded events; ms_sum[k], launches[k] for k < VTQ_K_COUNT (HOST arrays); resets. */
 int  vtq_profile_collect(vtq_handle h, double* ms_sum, int64_t* launches);
 
-/* ---- per-kernel entry points (unit tests call these through the same ABI) ----------------------------- */
-/* fp32 [rows, cols] -> 16-bit planes (f16: 0 = bf16, 1 = fp16): dst (hi) and, when planes == 2, dst + plane_stride (lo). */
+/* ---- per-kernel entry points (unit tests call these through the same ABI) -----------------------------
+ * Every comment below states the EXTENT of each pointer argument: what a caller must allocate, what the entry may read and what it writes.
+ * Nothing outside the stated extent is written, and no byte outside it influences a result; tests/test_gpu_footprint.py pins both with guard
+ * bands around buffers of exactly these sizes.  A call with an argument documented as invalid returns non-zero and launches nothing.
+ * Strides and pitches are in ELEMENTS of the buffer's type. */
+/* fp32 [numel] -> 16-bit planes (f16: 0 = bf16, 1 = fp16): dst (hi) and, when planes == 2, dst + plane_stride (lo).  numel % 4 == 0.
+ * Reads src[0, numel); writes numel elements per plane; elements [numel, plane_stride) between the planes are not touched. */
 int  vtq_k_split(const float* src, void* dst, int64_t plane_stride, int64_t numel, int32_t f16, int32_t planes, void* stream);
 
-/* C[M,N] = A[M,K] * W[N,K]^T (+epilogue); A/W are 16-bit planes as above, format `num` = VTQ_NUM_*; M%256==0, N%256==0,
- * K%128==0 (one MFMA per product) or K%64==0.
+/* C[M,N] = A[M,K] * W[N,K]^T (+epilogue); A/W are 16-bit planes as above, format `num` = VTQ_NUM_*; M%256==0, N%256==0, N <= 4096,
+ * K%128==0 (one MFMA per product) or K%64==0, lda%16==0, ldo%8==0 -- for every tile shape (vtq_debug_gemm_variant): refused otherwise.
+ *   A      activation planes (1, or 2 for the 2- / 3-term formats) of [M][lda], a_plane apart: columns [0, K) of rows [0, M) are read, the
+ *          columns [K, lda) and the space between planes are not;
+ *   W      weight planes (2 for the 3-term formats, else 1) of [N][K], w_plane apart;   bias fp32 [N];   gamma fp32 [N] or NULL;
+ *   x_f32  fp32 [M][N] contiguous, read and written by epilogue 2 only;
+ *   out16  planes as the activations of `num`, [M][ldo], o_plane apart, written by epilogues 0 / 1 only: columns [0, N) of rows [0, M);
+ *          columns [N, ldo) and the space between planes are not touched.
  *   epilogue 0: out16  = acc + bias                 (1 or 2 planes, as the activations of `num`)
  *            1: out16  = gelu_erf(acc + bias)                              (transformer.py:212-215)
  *            2: x_f32 += gamma * (acc + bias)   (gamma NULL = 1)           (transformer.py:279,284) */
@@ -237,7 +248,9 @@ int  vtq_k_gemm(const void* A, int64_t a_plane, int32_t lda, const void* W, int6
                 void* out16, int64_t o_plane, int32_t ldo, void* stream);
 
 /* Whole-row residual GEMM with LayerNorm in its epilogue (csrc/gemm_rowln.hip; N = 768, num = VTQ_NUM_BF16X3 | VTQ_NUM_FP16X3, M % 128 == 0,
- * K % 32 == 0, K >= 128):
+ * K % 32 == 0, K >= 128, lda % 8 == 0).  A: 2 planes of [M][lda] (columns [0, K) read), W: 2 planes of [768][K]; bias / gamma / ln_w / ln_b
+ * fp32 [768]; x_f32 [M][768] and the 2 planes out16 [M][768] (o_plane apart): rows [0, M) only -- rows behind M of a taller buffer are
+ * neither read nor written:
  *     x_f32[M, 768] += gamma * (A[M, K] * W[768, K]^T + bias)          (out-proj / fc2 + LayerScale + residual, transformer.py:279, 284)
  *     out16 planes   = LayerNorm(x_f32; ln_w, ln_b, eps 1e-6)           (the NEXT block's attention_norm / ffn_norm, transformer.py:276, 281)
  * in one launch: the workgroup that owns a 128-row panel owns whole rows.  ln_w == NULL: no LayerNorm output (the x update only).
@@ -252,19 +265,27 @@ int  vtq_k_gemm_rowln(const void* A, int64_t a_plane, int32_t lda, const void* W
  * Returns the total length (writes at most cap entries; out may be NULL), or -1 on a bad shape.  No GPU needed. */
 int  vtq_k_gemm_schedule(int32_t M, int32_t N, int32_t K, int32_t wplanes, int32_t* out, int32_t cap);
 
-/* LayerNorm(eps=1e-6) rows of x[rows, H] fp32 -> 16-bit planes (transformer.py:253-254, 276, 281). */
+/* LayerNorm(eps=1e-6) rows of x[rows, H] fp32 -> 16-bit planes (transformer.py:253-254, 276, 281).  H = 768 | 1024; w, b fp32 [H]; out:
+ * `planes` planes of [rows][H], o_plane apart; elements [rows * H, o_plane) between the planes are not touched. */
 int  vtq_k_layernorm(const float* x, const float* w, const float* b, void* out, int64_t o_plane,
                      int32_t rows, int32_t H, int32_t f16, int32_t planes, void* stream);
 
 /* softmax(Q K^T / sqrt(64)) V per (sequence, head) on the packed qkv[rows, 3H] planes (num = VTQ_NUM_* with 1 or 3 terms);
- * sequences are S_pad rows apart, keys >= S are masked; out[rows, H] planes, heads merged (transformer.py:153-166). */
+ * sequences are S_pad rows apart, keys >= S are masked; out[rows, H] planes, heads merged (transformer.py:153-166).
+ * S_pad - 64 < S <= S_pad (a pitch that leaves a whole 64-key tile empty is refused).
+ *   qkv  planes of [rows][3H], `plane` apart, rows >= nseq * S_pad + (ceil128(S_pad) - S_pad): the kernels load whole 128-row query blocks
+ *        and 64-key tiles, so up to 127 rows BEHIND the last sequence are read (S_pad % 128 == 1; the engine allocates 128).  They must
+ *        be readable; their values -- zero, NaN or anything else -- reach no output, and neither do rows [S, S_pad) of a sequence as
+ *        keys or the next sequence's rows (masked scores are replaced, masked V rows zeroed before use).
+ *   out  planes of [nseq * S_pad][H], o_plane apart: EVERY row [0, nseq * S_pad) is stored -- rows [S, S_pad) of a sequence hold the
+ *        attention of those pad rows' own queries over the keys < S -- and nothing at or behind row nseq * S_pad. */
 int  vtq_k_attention(const void* qkv, int64_t plane, void* out, int64_t o_plane,
                      int32_t nseq, int32_t S, int32_t S_pad, int32_t H, int32_t num, void* stream);
 
 /* Attention probabilities of every (sequence, head) on the same qkv planes as vtq_k_attention (num = VTQ_NUM_* with 1 or 3 terms):
  * probs[nseq][H / 64][S][S] fp32 = softmax(Q K^T / sqrt(64)) over the keys < S of each sequence; q_log2 != 0 (3-term formats only): Q
  * already carries 1/sqrt(64) * log2(e), as the engine's query projection does in those formats.  Reads only rows [s * S_pad, s * S_pad + S)
- * of sequence s. */
+ * of sequence s (qkv: planes of nseq * S_pad rows suffice); writes exactly nseq * (H / 64) * S * S floats. */
 int  vtq_k_attention_probs(const void* qkv, int64_t plane, float* probs, int32_t nseq, int32_t S, int32_t S_pad, int32_t H, int32_t num,
                            int32_t q_log2, void* stream);
 
@@ -273,7 +294,13 @@ int  vtq_k_attention_probs(const void* qkv, int64_t plane, float* probs, int32_t
  *   epi 0 plain | 1 gelu_erf | 2 prelu(*post_slope) | 3 res + gamma * v (gamma NULL = 1) | 4 res + aux * sigmoid(v) |
  *       5 relu for columns >= nsplit (RCAB conv with the channel-attention squeeze folded in, channel_attention.py:45, 58-61)
  * Outputs: y fp32 [R][ldy], columns [0, ycols) (may be NULL); ya: 16-bit planes of columns [pcol0, N), stored at column
- * c - pcol0, as prelu(value, *next_slope) when next_slope != NULL (may be NULL). */
+ * c - pcol0, as prelu(value, *next_slope) when next_slope != NULL (may be NULL).
+ * Extents.  xa: rows [0, ceil64(R)) x columns [0, K) are read (ldx % 8 == 0); rows >= R must be readable, their values reach no output.
+ * W: rows [0, ceil16(N)) are read; rows >= N likewise.  Columns of xa and W that only pad K to a multiple of 32 must be ZERO (they are
+ * multiplied).  bias, gamma fp32 [N]; res, aux fp32 [R][ldr], columns [0, N) (epilogues 3 / 4); the slopes one float each.
+ * y: rows [0, R) x columns [0, ycols) are written (ldy % 4 == 0 unless ycols < 4), columns [ycols, ldy) are not.  ya: activation planes
+ * of [R][ldya], ya_plane apart, pcol0 % 4 == 0, ldya % 4 == 0, ldya >= ceil4(N - pcol0): rows [0, R) x columns [0, ceil4(N - pcol0)) are
+ * written, the columns >= N - pcol0 among them as zeros (the consumer's K padding); rows >= R are not. */
 int  vtq_k_skinny_linear(const void* xa, int64_t xa_plane, int32_t ldx, const void* W, int64_t w_plane, int32_t R, int32_t N, int32_t K,
                          int32_t num, int32_t epi, const float* bias, const float* post_slope, const float* gamma, const float* res,
                          const float* aux, int32_t ldr, int32_t nsplit, float* y, int32_t ldy, int32_t ycols, void* ya, int64_t ya_plane,
@@ -287,7 +314,10 @@ int  vtq_k_skinny_linear(const void* xa, int64_t xa_plane, int32_t ldx, const vo
  * wqkv: the packed [3H][H] query | key | value weight as 16-bit planes of format `num` (VTQ_NUM_*), bqkv fp32 [3H] (only the value part is read:
  * q . b_k is constant per head).  Caller workspace: u fp32 [nseq][H/64][H]; part fp32 [nseq][ceil(S / vtq_k_cls_fold_chunk_rows())][H/64][H + 2];
  * z: 16-bit planes [planes of an activation][ceil64(nseq)][H/64 * H], z_plane elements apart.  ctx: fp32 [nseq][H].  H = 768 | 1024.
- * A sequence's result depends on its own rows and on S only, never on nseq. */
+ * A sequence's result depends on its own rows and on S only, never on nseq.
+ * Extents: exactly the sizes above.  x: rows [0, S) of each sequence are read, the elements [S * H, seq_stride) behind them never
+ * (seq_stride % 4 == 0).  u, part and z need no initial value; rows [0, nseq) of z are written, rows [nseq, ceil64(nseq)) are read by
+ * the value projection and reach no output.  wqkv: rows [H, 3H) of every plane are read; ln_w, ln_b fp32 [H]; q fp32 [nseq][H]. */
 int  vtq_k_cls_fold(const float* q, const void* wqkv, int64_t w_plane, const float* bqkv, const float* x, int64_t seq_stride,
                     const float* ln_w, const float* ln_b, int32_t nseq, int32_t S, int32_t H, int32_t num, int32_t q_log2,
                     float* u, float* part, void* z, int64_t z_plane, float* ctx, void* stream);
@@ -295,7 +325,8 @@ int  vtq_k_cls_fold(const float* q, const void* wqkv, int64_t w_plane, const flo
 int  vtq_k_cls_fold_chunk_rows(void);
 
 /* The DiffNet head + quality predictor alone (quality_decoder -> q_predictor, vtamiq.py:114-117, channel_attention.py:13-86) with
- * the handle's loaded weights: d fp32 [HB][H] = diff_scale(cls_ref - cls_dist) -> q_out fp32 [HB]. */
+ * the handle's loaded weights: d fp32 [HB][H] = diff_scale(cls_ref - cls_dist) -> q_out fp32 [HB] (HB >= 1; exactly these extents are read
+ * and written: every intermediate lives in the handle's workspace). */
 int  vtq_k_diffnet_head(vtq_handle h, const float* d, int32_t HB, float* q_out, void* stream);
 
 /* ---- on-device image -> patch tensor; replaces the CPU loader's transform_img (data/utils.py:76-94) and the
@@ -304,25 +335,28 @@ int  vtq_k_diffnet_head(vtq_handle h, const float* d, int32_t HB, float* q_out, 
  * or NULL; mean/std: HOST float[3]. */
 int  vtq_k_image_normalize(const uint8_t* images, float* out, int32_t NI, int32_t H, int32_t W, const int32_t* flips,
                            const float* mean, const float* std_, void* stream);
-/* torch.nn.AvgPool2d(2): in [NC, H, W] -> out [NC, H/2, W/2]. */
+/* torch.nn.AvgPool2d(2): in [NC, H, W] -> out [NC, H/2, W/2] (an odd last row / column is dropped; H, W >= 2). */
 int  vtq_k_avgpool2(const float* in, float* out, int32_t NC, int32_t H, int32_t W, void* stream);
 /* levels: HOST array of nlevels (<= 4) DEVICE pointers to [NI, 3, hs[l], ws[l]]; samples DEVICE int32 [NI, N, 2] (row, col at the
  * patch's own scale); scale_ids DEVICE int32 [NI, N] or NULL (all scale 0); patch_size P = 16 | 8.  Outputs: patches [NI, N, 3, P, P],
- * pos [NI, N, 2] = clamp((sample + P/2) / (dim - P/2), 0, 1 - 1e-6), scales [NI, N] (fp32-cast ids, may be NULL). */
+ * pos [NI, N, 2] = clamp((sample + P/2) / (dim - P/2), 0, 1 - 1e-6), scales [NI, N] (fp32-cast ids, may be NULL).
+ * A sample must lie inside its level (0 <= row <= hs[l] - P, 0 <= col <= ws[l] - P: the kernel does not check; a corner patch reads the
+ * level's last element and nothing behind it).  patch_size other than 16 | 8 and nlevels outside 1 .. 4 are refused. */
 int  vtq_k_gather_patches(const float* const* levels, const int32_t* hs, const int32_t* ws, int32_t nlevels, const int32_t* samples,
                           const int32_t* scale_ids, float* patches, float* pos, float* scales, int32_t NI, int32_t N, int32_t patch_size,
                           void* stream);
 
 /* ---- validation-loop reductions; fp64 like the reference's numpy arrays ------------------------------------ */
 /* average_over_repeats (train.py:398-400): q fp32 [R, N] (repeat-major, as the concatenated passes of do_validation) ->
- * out fp64 [N] = mean over the R repeats, summed in repeat order. */
+ * out fp64 [N] = mean over the R repeats, summed in repeat order.  R, N >= 1. */
 int  vtq_k_repeat_mean(const float* q, double* out, int32_t R, int32_t N, void* stream);
 /* The fit-free part of compute_correlations (utils/misc/correlations.py:21-33) on two fp64 score vectors a, b [N]:
  *   work[0:N], work[N:2N]  = normalize_array(a), normalize_array(b) (image_tools.py:17-21; plain copies when normalize == 0)
  *   work[2N:3N], [3N:4N]   = their average-tie ranks
  *   counts[0] = 2 (concordant - discordant pairs), counts[1] = 2 (pairs tied in a), counts[2] = 2 (pairs tied in b)   (exact)
  *   out[0] = Spearman (Pearson of the ranks), out[1] = Pearson, out[2] = RMSE of the normalised vectors.
- * work: DEVICE fp64 [4N]; counts: DEVICE int64 [3]; out: DEVICE fp64 [3].  The host finishes Kendall's tau-b from the counts. */
+ * work: DEVICE fp64 [4N]; counts: DEVICE int64 [3]; out: DEVICE fp64 [3] (exactly; none needs an initial value).  N >= 2.  The host
+ * finishes Kendall's tau-b from the counts. */
 int  vtq_k_rank_metrics(const double* a, const double* b, int32_t N, int32_t normalize, double* work, int64_t* counts, double* out,
                         void* stream);
 

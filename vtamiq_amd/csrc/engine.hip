@@ -347,7 +347,10 @@ Geometry geometry(const vtq_engine* e, int B, int N, int nimg = 2) {
     g.nseq = nimg * B;
     g.M_pad = round_up((int64_t)g.nseq * g.S_pad, 256);
     g.P_pad = round_up((int64_t)nimg * B * N, 256);
-    g.rows_alloc = (g.M_pad > g.P_pad ? g.M_pad : g.P_pad) + 128;   // +128: attention over-read slack behind the last sequence
+    // +128: attention over-read slack behind the last sequence.  vtq_k_attention's contract (include/vtamiq_hip.h) is ceil128(S_pad) - S_pad
+    // <= 127 rows behind row nseq * S_pad <= M_pad, pinned by tests/test_gpu_footprint.py test_attention with exactly that many rows; 128 is
+    // that bound rounded to the GEMM half tile, and the length of the memset in forward_impl
+    g.rows_alloc = (g.M_pad > g.P_pad ? g.M_pad : g.P_pad) + 128;
     g.R_pad = round_up(g.nseq, 64);
     g.sm = SeqMap{g.S_pad, g.nseq, (int)(g.M_pad - (int64_t)g.nseq * g.S_pad)};
     return g;
@@ -982,7 +985,9 @@ static int forward_impl(vtq_handle e, int nimg, const float* const* patches, con
     // The last 64-key tile of the last sequence reads K / V rows up to 63 past M_pad in the QKV layout of `big`.  Masked keys
     // multiply by probability 0, which only holds for FINITE stale values: a previous forward that overflowed (inf / NaN, see
     // vtq_input_errors bit 1) with a larger batch would otherwise poison this one's first layer.  From layer 1 on the region
-    // holds this forward's own fc1 output.
+    // holds this forward's own fc1 output.  128 rows: geometry()'s slack, which covers the <= 127 rows behind the last sequence that
+    // vtq_k_attention may load (the 4-wave kernel's unconditional Q loads; tests/test_gpu_footprint.py test_attention pins that none of
+    // them reaches an output, for zeros and for NaNs alike).
     for (int pl = 0; pl < e->apl; ++pl)
         HIP_TRY(hipMemsetAsync((char*)e->big + ((size_t)pl * e->big_plane + (size_t)g.M_pad * 3 * H) * 2, 0, (size_t)128 * 3 * H * 2, s));
 

@@ -933,15 +933,18 @@ int gemm_tile_rule(int M, int N, int K, Num num, int cus) {
 }
 
 hipError_t launch_gemm(const GemmArgs& a, Num num, int epilogue, hipStream_t s) {
-    if (num_valid(num) && num.f16 != 2) {
+    // The shape rule of the entry (include/vtamiq_hip.h vtq_k_gemm) is checked BEFORE a tile shape is picked: the small-tile kernels would
+    // take N > 4096 or a one-term K % 128 == 64, so whether such a call was refused depended on (M, N) and on the device's CU count
+    // (tests/test_gpu_footprint.py test_rejected_calls_launch_nothing).
+    const int bk2 = (num.f16 == 2) ? 256 : ((num.terms == 1) ? 128 : 64);     // two K tiles: the DMA ring's buffer parity is fixed across tiles
+    if (a.M <= 0 || a.M % 256 || a.N <= 0 || a.N % 256 || a.N > 4096 || a.K <= 0 || a.K % bk2 || a.lda % 16 || !num_valid(num)) return hipErrorInvalidValue;
+    if (num.f16 != 2) {
         const int forced = g_tile_variant.load(std::memory_order_relaxed);
         int cus = 0;
         if (forced == GEMM_TILE_AUTO && device_cus(&cus)) return hipErrorInvalidDevice;      // the CU count of the CURRENT device (a partitioned part has fewer)
         const int v = forced != GEMM_TILE_AUTO ? forced : gemm_tile_rule(a.M, a.N, a.K, num, cus);
         if (v != GEMM_TILE_256) return launch_gemm_st(a, num, epilogue, v, s);
     }
-    const int bk2 = (num.f16 == 2) ? 256 : ((num.terms == 1) ? 128 : 64);     // two K tiles: the DMA ring's buffer parity is fixed across tiles
-    if (a.M <= 0 || a.M % 256 || a.N % 256 || a.N > 4096 || a.K <= 0 || a.K % bk2 || a.lda % 16 || !num_valid(num)) return hipErrorInvalidValue;
     if (num.f16 == 2) {
 #ifdef VTQ_WITH_FP8                                   // the fp8 experiment (include/vtamiq_hip_fp8.h): not in the product library
         if (!a.wscale) return hipErrorInvalidValue;
