@@ -99,7 +99,10 @@ void vtq_destroy(vtq_handle h);
  * the handle.  Unknown names are an error; every tensor of the configured topology must be present. */
 int  vtq_load_weights(vtq_handle h, const vtq_tensor_desc* descs, int32_t n, void* stream);
 
-/* Bytes of device workspace the handle holds for a (B pairs, N patches) call. */
+/* Bytes of device workspace the handle holds for a (B pairs, N patches) call.  A capacity of (B, N) is an upper bound for EVERY workspace
+ * buffer of a vtq_forward_varlen call of at most B pairs with at most N patches each (its token rows, patch rows, per-sequence rows,
+ * fold partials and per-call tables are all no larger than those of B uniform pairs of N patches): vtq_reserve(h, B, max n) ahead of
+ * such calls means none of them allocates. */
 size_t vtq_workspace_bytes(vtq_handle h, int32_t B, int32_t N);
 /* Grows the workspace ahead of time (hipMalloc happens here, or lazily on the first larger vtq_forward). */
 int  vtq_reserve(vtq_handle h, int32_t B, int32_t N);
@@ -113,6 +116,21 @@ int  vtq_forward(vtq_handle h,
                  const float* pos_ref, const float* pos_dist,
                  const float* scales_ref, const float* scales_dist,
                  int32_t B, int32_t N, float* q_out, void* stream);
+
+/* vtq_forward on B pairs with DIFFERENT patch counts: pair b has n_patches[b] >= 1 patches in both of its images (n_patches: HOST array
+ * of B entries, read before the call returns).  With SN = the sum of n_patches:
+ *   patches_* : (SN, 3, P, P) fp32 contiguous -- the pairs' patches one after the other      pos_* : (SN, 2)
+ *   scales_*  : (SN) or NULL, under the rule of vtq_forward                                   q_out : B scores
+ * q_out[b] has the bits vtq_forward gives for pair b alone (B = 1, N = n_patches[b]) on the same handle, in every numerics mode, with the
+ * CLS-only last layer and with VTQ_OPT_FULL_LAST_LAYER; with all n_patches equal the call is bit-identical to vtq_forward.  Sequences
+ * (n_patches[b] + T token rows) are packed back to back at their own length, all reference sequences, then all distorted ones; the
+ * call's tables (row offsets, patch-row prefix, attention block table) are built on the host and uploaded to buffers of THIS handle
+ * on `stream` ahead of the first launch.  Asynchronous on `stream` (a second call waits for the previous call's table upload, not for
+ * its kernels); vtq_input_errors bits 0 and 1 as vtq_forward.  Workspace: as vtq_forward(B, max n_patches) -- see vtq_workspace_bytes.
+ * Refused with vtq_last_error text and no launch: a NULL handle, tensor, n_patches or q_out; B < 1; an n_patches[b] < 1; the fp8
+ * experiment's handle; a set token trace buffer (vtq_set_token_trace). */
+int  vtq_forward_varlen(vtq_handle h, const float* patches_ref, const float* patches_dist, const float* pos_ref, const float* pos_dist,
+                        const float* scales_ref, const float* scales_dist, int32_t B, const int32_t* n_patches, float* q_out, void* stream);
 
 /* VTAMIQ.forward on PRE-EMBEDDED input: Embeddings.forward takes the (B, N, H) branch (transformer.py:534-535) -- what a model built with
  * use_patch_embedding=False is fed, and what the reference does with ANY 3-D `patches` tensor.  feats_*: (B, N, hidden_size) fp32, contiguous; everything
@@ -281,6 +299,22 @@ int  vtq_k_layernorm(const float* x, const float* w, const float* b, void* out, 
  *        attention of those pad rows' own queries over the keys < S -- and nothing at or behind row nseq * S_pad. */
 int  vtq_k_attention(const void* qkv, int64_t plane, void* out, int64_t o_plane,
                      int32_t nseq, int32_t S, int32_t S_pad, int32_t H, int32_t num, void* stream);
+
+/* vtq_k_attention over nseq sequences of DIFFERENT lengths packed back to back (csrc/attention_varlen.hip): sequence j is the seq_len[j] >= 1
+ * rows from row sum_{i<j} seq_len[i] (seq_len: HOST array); with R = the sum of all lengths:
+ *   qkv  planes of [rows][3H], `plane` apart, rows >= R + 127: the kernel loads whole 128-row query blocks and 64-key tiles from a
+ *        sequence's first row, so up to 127 rows BEHIND row R are read.  They must be readable; their values -- zero, NaN, inf --
+ *        reach no output, and neither do another sequence's rows (masked scores are replaced, masked V rows zeroed before use).
+ *   out  planes of [R][H], o_plane apart: rows [0, R) are stored, nothing at or behind row R.
+ * The rows of sequence j are bit-identical to vtq_k_attention(nseq = 1, S = S_pad = seq_len[j]) on that sequence's rows.  num: VTQ_NUM_*
+ * with 1 or 3 terms.  A test entry: it uploads its block table to a temporary and waits for `stream` before returning. */
+int  vtq_vl_attention(const void* qkv, int64_t plane, void* out, int64_t o_plane, int32_t nseq, const int32_t* seq_len, int32_t H, int32_t num,
+                      void* stream);
+/* HOST-only: the block table of vtq_vl_attention / vtq_forward_varlen for these lengths -- one entry of 4 ints per workgroup, in work-id
+ * order: {first row of the sequence, its length, 128-row query block, head}; the blocks of one (sequence, head) are consecutive work
+ * ids (the kernel keeps consecutive ids on one XCD: they share K / V in its L2).  Writes at most cap entries (out may be NULL); returns
+ * the number of entries = H / 64 * sum_j ceil(seq_len[j] / 128), or -1 on a bad argument.  No GPU needed. */
+int  vtq_vl_attention_blocks(int32_t nseq, const int32_t* seq_len, int32_t H, int32_t* out, int32_t cap);
 
 /* Attention probabilities of every (sequence, head) on the same qkv planes as vtq_k_attention (num = VTQ_NUM_* with 1 or 3 terms):
  * probs[nseq][H / 64][S][S] fp32 = softmax(Q K^T / sqrt(64)) over the keys < S of each sequence; q_log2 != 0 (3-term formats only): Q

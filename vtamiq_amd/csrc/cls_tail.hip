@@ -19,12 +19,12 @@ namespace {
 template <int V4>
 __global__ __launch_bounds__(256) void rows_ln_kernel(const float* __restrict__ src, int64_t stride, const float* __restrict__ w,
                                                       const float* __restrict__ b, float* __restrict__ ln, float* __restrict__ copy,
-                                                      int rows, PlaneOut po) {
+                                                      int rows, PlaneOut po, const int* __restrict__ vl_row0) {
     constexpr int H = 256 * V4;
     const int lane = threadIdx.x & 63;
     const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= rows) return;
-    const float4* xr = (const float4*)(src + r * stride);
+    const float4* xr = (const float4*)(src + (vl_row0 ? (int64_t)vl_row0[r] * H : r * stride));     // variable length: rows by table
     float4 v[V4];
     float s = 0.f;
 #pragma unroll
@@ -138,7 +138,7 @@ __global__ __launch_bounds__(1024) void cls_key_fold_kernel(const float* __restr
 template <int V4>
 __global__ __launch_bounds__(512) void cls_fold_attention_kernel(const float* __restrict__ x, int64_t seq_stride, const float* __restrict__ lw,
                                                                  const float* __restrict__ lb, const float* __restrict__ u,
-                                                                 float* __restrict__ part, int S, int nh, int q_log2) {
+                                                                 float* __restrict__ part, int S, int nh, int q_log2, VarSeq vl) {
     constexpr int H = 256 * V4, LD = H + kFoldPad, NG = 4 * V4, NB = 2 * V4;
     extern __shared__ __attribute__((aligned(16))) float fold_smem[];
     float* rows = fold_smem;                                                         // [32][LD] normalised rows
@@ -149,7 +149,13 @@ __global__ __launch_bounds__(512) void cls_fold_attention_kernel(const float* __
     const int tid = threadIdx.x, lane = tid & 63, fr = lane & 15, fq = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int chunk = blockIdx.x, seq = blockIdx.y, c0 = chunk * kFoldChunk;
-    const float* xs = x + (int64_t)seq * seq_stride;
+    // variable length: this sequence's own length and first row; the grid spans the chunks of the longest sequence, and a workgroup
+    // behind its sequence's last chunk has nothing to do (uniform over the workgroup, ahead of the first barrier)
+    if (vl.len) {
+        S = vl.len[seq];
+        if (c0 >= S) return;
+    }
+    const float* xs = x + (vl.row0 ? (int64_t)vl.row0[seq] * H : (int64_t)seq * seq_stride);
     const int rb = wave & 1, kbase = (wave >> 1) * (H / 4);
     // step 2's B operand: lane (head fr, k slot fq) holds u[head][kbase + 16 j + 4 fq + e] as element e of fragment j (heads >= nh: a copy
     // of the last head, whose scores are dropped)
@@ -289,11 +295,13 @@ __global__ __launch_bounds__(512) void cls_fold_attention_kernel(const float* __
 
 // zbar[seq][h][:] = sum_c e(m_c - m) z_c / sum_c e(m_c - m) l_c over the sequence's chunks in ascending order, written as the operand
 // planes of the value projection (row seq, columns h H ..).  One workgroup per (head, sequence), thread t owns columns 4t .. 4t + 3.
-__global__ __launch_bounds__(256) void cls_fold_combine_kernel(const float* __restrict__ part, int nchunks, int H, PlaneOut po, int q_log2) {
+__global__ __launch_bounds__(256) void cls_fold_combine_kernel(const float* __restrict__ part, int nchunks, int H, PlaneOut po, int q_log2,
+                                                               const int* __restrict__ vl_len) {
     const int head = blockIdx.x, nh = gridDim.x, seq = blockIdx.y, c4 = 4 * threadIdx.x;
     if (c4 >= H) return;
     const int64_t ps = (int64_t)nh * (H + 2);
-    const float* pb = part + (int64_t)seq * nchunks * ps;
+    const float* pb = part + (int64_t)seq * nchunks * ps;           // nchunks: the chunk pitch of `part` ...
+    if (vl_len) nchunks = (vl_len[seq] + kFoldChunk - 1) / kFoldChunk;   // ... and, variable length, this sequence's own chunk count
     const float* ml = pb + (int64_t)nh * H + 2 * head;
     // loads in batches (a chunk index past the end re-reads the last chunk and is not used): a loop of single dependent loads cost one
     // memory latency per chunk
@@ -332,10 +340,10 @@ __global__ __launch_bounds__(256) void cls_fold_combine_kernel(const float* __re
 }  // namespace
 
 hipError_t launch_rows_ln(const float* src, int64_t stride, const float* w, const float* b, float* ln, float* copy, int rows, int H,
-                          PlaneOut po, hipStream_t s) {
+                          PlaneOut po, hipStream_t s, const int* vl_row0) {
     const dim3 g((rows + 3) / 4), blk(256);
-    if (H == 768) hipLaunchKernelGGL(rows_ln_kernel<3>, g, blk, 0, s, src, stride, w, b, ln, copy, rows, po);
-    else if (H == 1024) hipLaunchKernelGGL(rows_ln_kernel<4>, g, blk, 0, s, src, stride, w, b, ln, copy, rows, po);
+    if (H == 768) hipLaunchKernelGGL(rows_ln_kernel<3>, g, blk, 0, s, src, stride, w, b, ln, copy, rows, po, vl_row0);
+    else if (H == 1024) hipLaunchKernelGGL(rows_ln_kernel<4>, g, blk, 0, s, src, stride, w, b, ln, copy, rows, po, vl_row0);
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }
@@ -345,7 +353,7 @@ int cls_fold_chunk_rows() { return kFoldChunk; }
 namespace {
 template <int V4>
 hipError_t launch_fold_attention(const float* x, int64_t seq_stride, const float* lw, const float* lb, const float* u, float* part, int nseq,
-                                 int S, int nh, int q_log2, hipStream_t s) {
+                                 int S, int nh, int q_log2, hipStream_t s, VarSeq vl) {
     constexpr int lds = (kFoldSub * (256 * V4 + kFoldPad) + 6 * kFoldSub * 16 + 48) * 4;
     {   // beyond the default dynamic-LDS limit: raise it once per device
         static std::mutex mu;
@@ -362,14 +370,15 @@ hipError_t launch_fold_attention(const float* x, int64_t seq_stride, const float
         }
     }
     hipLaunchKernelGGL((cls_fold_attention_kernel<V4>), dim3((S + kFoldChunk - 1) / kFoldChunk, nseq), dim3(512), lds, s, x, seq_stride, lw, lb, u,
-                       part, S, nh, q_log2);
+                       part, S, nh, q_log2, vl);
     return hipGetLastError();
 }
 }  // namespace
 
 hipError_t launch_cls_fold(const float* q, const void* wk, int64_t w_plane, int ldw, int f16_, int wplanes, const float* x, int64_t seq_stride,
                            const float* lw, const float* lb, float* u, float* part, int nseq, int S, int H, PlaneOut zo, hipStream_t s,
-                           bool q_log2) {
+                           bool q_log2, VarSeq vl) {
+    if ((vl.row0 != nullptr) != (vl.len != nullptr)) return hipErrorInvalidValue;
     if (nseq < 1 || S < 1 || (H != 768 && H != 1024) || ldw < H || ldw % 4 || (wplanes != 1 && wplanes != 2) || seq_stride % 4 || !zo.p || zo.ld < (H / 64) * H)
         return hipErrorInvalidValue;
     const int nh = H / 64, nchunks = (S + kFoldChunk - 1) / kFoldChunk;
@@ -380,10 +389,10 @@ hipError_t launch_cls_fold(const float* q, const void* wk, int64_t w_plane, int 
 #undef VTQ_KF
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    e = H == 768 ? launch_fold_attention<3>(x, seq_stride, lw, lb, u, part, nseq, S, nh, q_log2 ? 1 : 0, s)
-                 : launch_fold_attention<4>(x, seq_stride, lw, lb, u, part, nseq, S, nh, q_log2 ? 1 : 0, s);
+    e = H == 768 ? launch_fold_attention<3>(x, seq_stride, lw, lb, u, part, nseq, S, nh, q_log2 ? 1 : 0, s, vl)
+                 : launch_fold_attention<4>(x, seq_stride, lw, lb, u, part, nseq, S, nh, q_log2 ? 1 : 0, s, vl);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(cls_fold_combine_kernel, dim3(nh, nseq), blk, 0, s, (const float*)part, nchunks, H, zo, q_log2 ? 1 : 0);
+    hipLaunchKernelGGL(cls_fold_combine_kernel, dim3(nh, nseq), blk, 0, s, (const float*)part, nchunks, H, zo, q_log2 ? 1 : 0, vl.len);
     return hipGetLastError();
 }
 

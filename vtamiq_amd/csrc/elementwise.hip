@@ -110,10 +110,10 @@ __global__ __launch_bounds__(256) void pack_patches_kernel(ImgPtrs src, int nimg
 // *err (bit 0), which vtq_input_errors() reads back: never an out-of-bounds gather.
 __global__ void embed_index_kernel(ImgPtrs pos, ImgPtrs sc, int nimg, int* __restrict__ pidx, int* __restrict__ sidx,
                                    int* __restrict__ row_map, int B, int N, int rows_pad, SeqMap sm, int T, int grid, int num_scales,
-                                   int* __restrict__ err) {
+                                   int* __restrict__ err, const int* __restrict__ vl_prefix, const int* __restrict__ vl_row0) {
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= rows_pad) return;
-    const int BN = B * N;
+    const int BN = vl_prefix ? N : B * N;                 // variable length: N = the patches of one image (all pairs)
     const int img = r / BN;
     if (img >= nimg) { pidx[r] = 0; sidx[r] = 0; row_map[r] = -1; return; }
     const int rr = r - img * BN;
@@ -133,6 +133,15 @@ __global__ void embed_index_kernel(ImgPtrs pos, ImgPtrs sc, int nimg, int* __res
         si = (int)sv;
     }
     sidx[r] = si;
+    if (vl_prefix) {                                      // the pair whose patches hold row rr: vl_prefix[b] <= rr < vl_prefix[b + 1]
+        int lo = 0, hi = B;
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (vl_prefix[mid] <= rr) lo = mid; else hi = mid;
+        }
+        row_map[r] = vl_row0[img * B + lo] + T + (rr - vl_prefix[lo]);
+        return;
+    }
     const int b = rr / N, n = rr - b * N;
     row_map[r] = (int)seq_row(sm, img * B + b) + T + n;
 }
@@ -162,9 +171,9 @@ __global__ __launch_bounds__(256) void embed_rows_kernel(ImgPtrs feats, int nimg
 
 // Embeddings.forward_tokens (transformer.py:507-524): row 0 = cls + pos_table[0]; rows 1..T-1 = register tokens.
 __global__ void tokens_kernel(float* __restrict__ x, const float* __restrict__ cls, const float* __restrict__ pos_table,
-                              const float* __restrict__ extra, SeqMap sm, int T, int H) {
+                              const float* __restrict__ extra, SeqMap sm, int T, int H, const int* __restrict__ vl_row0) {
     const int seq = blockIdx.x, t = blockIdx.y;
-    float* dst = x + (seq_row(sm, seq) + t) * H;
+    float* dst = x + ((vl_row0 ? (int64_t)vl_row0[seq] : seq_row(sm, seq)) + t) * H;
     for (int c = threadIdx.x; c < H; c += blockDim.x) dst[c] = (t == 0) ? cls[c] + pos_table[c] : extra[(t - 1) * H + c];
 }
 
@@ -249,13 +258,15 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
 template <int V4>
 __global__ __launch_bounds__(64) void final_diff_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                         const float* __restrict__ b, const float* __restrict__ gamma,
-                                                        float* __restrict__ d, int B, SeqMap sm, PlaneOut po, int* __restrict__ err) {
+                                                        float* __restrict__ d, int B, SeqMap sm, PlaneOut po, int* __restrict__ err,
+                                                        const int* __restrict__ vl_row0) {
     constexpr int H = 256 * V4;
     const int lane = threadIdx.x;
     const int pb = blockIdx.x, j = blockIdx.y;           // j-th distorted image (0 for FR pairs; 0,1 for pairwise triplets)
     float4 yr[V4], yd[V4];
-    ln_row<V4>(x + seq_row(sm, pb) * H, w, b, lane, yr);
-    ln_row<V4>(x + seq_row(sm, (j + 1) * B + pb) * H, w, b, lane, yd);
+    const int sd = (j + 1) * B + pb;                     // vl_row0 (variable length): the sequences' first rows come from the table
+    ln_row<V4>(x + (vl_row0 ? (int64_t)vl_row0[pb] : seq_row(sm, pb)) * H, w, b, lane, yr);
+    ln_row<V4>(x + (vl_row0 ? (int64_t)vl_row0[sd] : seq_row(sm, sd)) * H, w, b, lane, yd);
 #pragma unroll
     for (int i = 0; i < V4; ++i) {
         float4 r = {yr[i].x - yd[i].x, yr[i].y - yd[i].y, yr[i].z - yd[i].z, yr[i].w - yd[i].w};
@@ -368,11 +379,13 @@ hipError_t launch_pack_patches(const float* const* imgs, int nimg, void* dst, in
 }
 
 hipError_t launch_embed_index(const float* const* pos, const float* const* sc, int nimg, int* pidx, int* sidx, int* row_map, int B, int N,
-                              int rows_pad, SeqMap sm, int T, int grid, int num_scales, int* err, hipStream_t s) {
+                              int rows_pad, SeqMap sm, int T, int grid, int num_scales, int* err, hipStream_t s, const int* vl_prefix,
+                              const int* vl_row0) {
+    if ((vl_prefix != nullptr) != (vl_row0 != nullptr)) return hipErrorInvalidValue;
     ImgPtrs pp{{pos[0], pos[1], nimg > 2 ? pos[2] : nullptr}};
     ImgPtrs sp{{sc ? sc[0] : nullptr, sc ? sc[1] : nullptr, (sc && nimg > 2) ? sc[2] : nullptr}};
     hipLaunchKernelGGL(embed_index_kernel, dim3((rows_pad + 255) / 256), dim3(256), 0, s, pp, sp, nimg, pidx, sidx, row_map, B, N, rows_pad,
-                       sm, T, grid, num_scales, err);
+                       sm, T, grid, num_scales, err, vl_prefix, vl_row0);
     return hipGetLastError();
 }
 
@@ -384,8 +397,8 @@ hipError_t launch_embed_rows(const float* const* feats, int nimg, int BN, const 
 }
 
 hipError_t launch_tokens(float* x, const float* cls, const float* pos_table, const float* extra, int nseq, SeqMap sm, int T,
-                         int H, hipStream_t s) {
-    hipLaunchKernelGGL(tokens_kernel, dim3(nseq, T), dim3(256), 0, s, x, cls, pos_table, extra, sm, T, H);
+                         int H, hipStream_t s, const int* vl_row0) {
+    hipLaunchKernelGGL(tokens_kernel, dim3(nseq, T), dim3(256), 0, s, x, cls, pos_table, extra, sm, T, H, vl_row0);
     return hipGetLastError();
 }
 
@@ -418,9 +431,9 @@ hipError_t launch_layernorm(const float* x, const float* w, const float* b, void
 }
 
 hipError_t launch_final_diff(const float* x, const float* ln_w, const float* ln_b, const float* gamma, float* d, int B, int ndist,
-                             SeqMap sm, int H, PlaneOut po, hipStream_t s, int* err) {
-    if (H == 768) hipLaunchKernelGGL(final_diff_kernel<3>, dim3(B, ndist), dim3(64), 0, s, x, ln_w, ln_b, gamma, d, B, sm, po, err);
-    else if (H == 1024) hipLaunchKernelGGL(final_diff_kernel<4>, dim3(B, ndist), dim3(64), 0, s, x, ln_w, ln_b, gamma, d, B, sm, po, err);
+                             SeqMap sm, int H, PlaneOut po, hipStream_t s, int* err, const int* vl_row0) {
+    if (H == 768) hipLaunchKernelGGL(final_diff_kernel<3>, dim3(B, ndist), dim3(64), 0, s, x, ln_w, ln_b, gamma, d, B, sm, po, err, vl_row0);
+    else if (H == 1024) hipLaunchKernelGGL(final_diff_kernel<4>, dim3(B, ndist), dim3(64), 0, s, x, ln_w, ln_b, gamma, d, B, sm, po, err, vl_row0);
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }

@@ -10,6 +10,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
+#include <climits>
 #include <cstring>
 #include <string>
 #include <unordered_map>
@@ -156,6 +157,13 @@ struct vtq_engine {
     float *fold_u = nullptr, *fold_part = nullptr;              //   folded attention (cls_tail.hip): W_k^T q per (sequence, head); chunk partials
     void* fold_z = nullptr;                                      //   its output planes (encoder format): [r_alloc][H / 64 * H]
     int64_t fold_z_plane = 0;
+    // vtq_forward_varlen: the per-call tables (sequence row offsets | lengths | patch-row prefix | attention block table), built on the host
+    // in a pinned image of this engine's own and uploaded on the call's stream ahead of the first launch.  vl_uploaded: recorded behind
+    // the upload, waited for before the next call rewrites the image.  Per engine: nothing of this is shared between handles.
+    int* vl_tab = nullptr;               //   device (workspace)
+    int* vl_host = nullptr;              //   pinned host image
+    size_t vl_host_ints = 0;
+    hipEvent_t vl_uploaded = nullptr;
     bool cls_prune = true;
     bool fuse_ln = false;                // VTQ_OPT_FUSED_LAYERNORM: residual GEMMs carry the next LayerNorm in their epilogue (gemm_rowln.hip)
     int32_t* err_host = nullptr;         // pinned landing word of vtq_input_errors (a pageable destination goes through the runtime's staging path)
@@ -356,6 +364,10 @@ Geometry geometry(const vtq_engine* e, int B, int N, int nimg = 2) {
     return g;
 }
 
+// ints of vtq_forward_varlen's device tables for nseq sequences of at most S rows: row offsets [nseq + 1], lengths [nseq], patch prefix
+// [nseq / 2 + 1] (padded to whole int4), then 4 per attention workgroup -- sum_j ceil(S_j / 128) <= nseq * ceil(S / 128) query blocks per head
+int64_t varlen_table_ints(int64_t nseq, int64_t S, int H) { return round_up(3 * nseq + 4, 4) + 4 * nseq * ((S + 127) / 128) * (H / 64); }
+
 // One workspace buffer: the engine member it fills, its `planes` planes of `elems` elements of `esz` bytes (the plane stride goes
 // to *stride where the engine keeps one), and whether reserve() zero-fills it.
 struct WsBuf { void** ptr; int64_t* stride; int64_t elems; int esz, planes; bool zero; };
@@ -391,6 +403,7 @@ std::vector<WsBuf> workspace(vtq_engine* e, int B, int N) {
         {&e->fold_z, &e->fold_z_plane, R * nh * H, 2, apl, true},
     };
     for (float*& hb : e->hb) w.push_back({(void**)&hb, nullptr, g.nseq * H, 4, 1, false});   // head ping-pong rows
+    w.push_back({(void**)&e->vl_tab, nullptr, varlen_table_ints(g.nseq, g.S, (int)H), 4, 1, false});   // vtq_forward_varlen's tables
     return w;
 }
 
@@ -453,8 +466,11 @@ int fp8_stage(vtq_engine* e, hipStream_t s, float& sc, F launch) {
     return launch(sc, Fp8Obs{nullptr, e->err_flag});
 }
 
-// All encoder layers for the g.nseq sequences, enqueued on s.
-int run_encoder(vtq_engine* e, const Geometry& g, hipStream_t s, bool prune) {
+// One vtq_forward_varlen call's device tables (in e->vl_tab): sequence j is the len[j] rows from row0[j]; `blocks`: attention_varlen.hip
+struct VarLen { const int* row0; const int* len; const int* prefix; const int* blocks; int nblocks; };
+
+// All encoder layers for the g.nseq sequences, enqueued on s.  vl != NULL: sequences of different lengths (g.S = the largest)
+int run_encoder(vtq_engine* e, const Geometry& g, hipStream_t s, bool prune, const VarLen* vl = nullptr) {
     const vtq_config& c = e->cfg;
     const int H = e->H, Md = e->Mdim, T = e->T, L = c.num_layers, f16 = e->f16, apl = e->apl, Hqp = (int)e->Hqp;
     const Num lin = e->lin;
@@ -525,7 +541,7 @@ int run_encoder(vtq_engine* e, const Geometry& g, hipStream_t s, bool prune) {
                 // skinny MFMA stages on the R CLS rows (skinny.hip); activations between them as planes in the encoder's format
                 const View tlv{e->tl, e->tl_plane, H}, thv{e->th, e->th_plane, Md};
                 const PlaneOut tl{e->tl, e->tl_plane, H, f16, apl, nullptr};       // every row kernel of the tail writes its consumer's planes
-                HIP_TRY(launch_rows_ln(x + (int64_t)e->iqa_token * H, (int64_t)g.S_pad * H, Ly.ln1w, Ly.ln1b, lncls, xcls, R, H, tl, s));
+                HIP_TRY(launch_rows_ln(x + (int64_t)e->iqa_token * H, (int64_t)g.S_pad * H, Ly.ln1w, Ly.ln1b, lncls, xcls, R, H, tl, s, vl ? vl->row0 : nullptr));
                 {   // query projection: rows 0 .. H-1 of the packed QKV weight
                     SkinnyArgs a = skinny_args(tlv, lin_rows(Ly.qkv, 0, H), R, apl);
                     a.epi = SK_PLAIN; a.y = qcls; a.ldy = H; a.ycols = H;
@@ -535,7 +551,7 @@ int run_encoder(vtq_engine* e, const Geometry& g, hipStream_t s, bool prune) {
                     const Lin wk = lin_rows(Ly.qkv, H, H);
                     const PlaneOut zo{e->fold_z, e->fold_z_plane, (H / 64) * H, f16, apl, nullptr};
                     HIP_TRY(launch_cls_fold(qcls, wk.w, wk.plane, wk.K, f16, e->wpl, x, (int64_t)g.S_pad * H, Ly.ln1w, Ly.ln1b, e->fold_u, e->fold_part,
-                                            R, g.S, H, zo, s, e->att.terms == 3));
+                                            R, g.S, H, zo, s, e->att.terms == 3, vl ? VarSeq{vl->row0, vl->len} : VarSeq{nullptr, nullptr}));
                 }
                 {   // value projection: ctx[64h ..] = W_v,h zbar_h + b_v (rows 2H .. 3H-1), head h reading columns h H .. of its row
                     SkinnyArgs a = skinny_args(View{e->fold_z, e->fold_z_plane, (H / 64) * H}, lin_rows(Ly.qkv, 2 * H, H), R, apl);
@@ -571,7 +587,8 @@ int run_encoder(vtq_engine* e, const Geometry& g, hipStream_t s, bool prune) {
             Prof p(e, s, VTQ_K_ATTN);
             if (f8m) {
                 if (fp8_stage(e, s, e->s_att[i], [&](float sc, Fp8Obs ob) { HIP_TRY(launch_attention(e->big, e->big_plane, e->lnbuf, e->ln_plane, g.nseq, g.S, g.S_pad, H, e->att, s, sc, ob, e->att.terms == 3)); return 0; })) return 1;
-            } else HIP_TRY(launch_attention(e->big, e->big_plane, e->lnbuf, e->ln_plane, g.nseq, g.S, g.S_pad, H, e->att, s, 0.0f, Fp8Obs{nullptr, nullptr}, e->att.terms == 3));
+            } else if (vl) HIP_TRY(launch_attention_varlen(e->big, e->big_plane, e->lnbuf, e->ln_plane, vl->blocks, vl->nblocks, H, e->att, s, e->att.terms == 3));
+            else HIP_TRY(launch_attention(e->big, e->big_plane, e->lnbuf, e->ln_plane, g.nseq, g.S, g.S_pad, H, e->att, s, 0.0f, Fp8Obs{nullptr, nullptr}, e->att.terms == 3));
             // forward_vit's attention maps: from the same QKV planes, before the out-proj (with adapters it reuses `big`)
             if (e->vit_probs)
                 HIP_TRY(launch_attention_probs(e->big, e->big_plane, e->vit_probs + (int64_t)i * g.nseq * (H / 64) * g.S * g.S, g.nseq, g.S, g.S_pad, H,
@@ -760,6 +777,8 @@ void vtq_destroy(vtq_handle e) {
     (void)hipDeviceSynchronize();
     for (void* p : e->allocs) (void)hipFree(p);
     if (e->err_host) (void)hipHostFree(e->err_host);
+    if (e->vl_host) (void)hipHostFree(e->vl_host);
+    if (e->vl_uploaded) (void)hipEventDestroy(e->vl_uploaded);
     for (void* p : e->ws_allocs) (void)hipFree(p);
     for (auto& ev : e->ev_used) { (void)hipEventDestroy(ev.a); (void)hipEventDestroy(ev.b); }
     for (auto& ev : e->ev_free) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
@@ -1082,6 +1101,125 @@ int vtq_forward_tokens(vtq_handle e, const float* feats_ref, const float* feats_
     return forward_pair(e, true, feats_ref, feats_dist, pos_ref, pos_dist, scales_ref, scales_dist, B, N, q_out, stream);
 }
 
+// B pairs of different patch counts through one launch sequence (include/vtamiq_hip.h).  Layout: sequences packed back to back at their
+// own length, all reference sequences, then all distorted ones; the packed patch rows likewise (image, pair, patch).  Every kernel is
+// row- or sequence-independent and the GEMMs are bitwise independent of M, so pair b's score has the bits of a B = 1 call on pair b.
+int vtq_forward_varlen(vtq_handle e, const float* patches_ref, const float* patches_dist, const float* pos_ref, const float* pos_dist,
+                       const float* scales_ref, const float* scales_dist, int32_t B, const int32_t* n_patches, float* q_out, void* stream) {
+    // the batch description first (it needs no handle), then the handle, then what the handle decides
+    if (!n_patches) return fail("vtq_forward_varlen: null n_patches");
+    if (B < 1) return fail("vtq_forward_varlen: B=%d", (int)B);
+    for (int b = 0; b < B; ++b)
+        if (n_patches[b] < 1) return fail("vtq_forward_varlen: n_patches[%d] = %d (every pair needs at least one patch)", b, (int)n_patches[b]);
+    if (!e) return fail("vtq_forward_varlen: null handle");
+    if (e->fp8) return fail("vtq_forward_varlen: not available for the fp8 experiment's engine");
+    if (!patches_ref || !patches_dist || !pos_ref || !pos_dist) return fail("vtq_forward_varlen: null tensor");
+    if (!q_out) return fail("vtq_forward_varlen: null output");
+    if (e->trace) return fail("vtq_forward_varlen: a token trace buffer is set (vtq_set_token_trace): the trace layout is per uniform batch");
+    const vtq_config& c = e->cfg;
+    const int H = e->H, T = e->T, nseq = 2 * B;
+    int64_t sumN = 0;
+    int maxN = 0;
+    for (int b = 0; b < B; ++b) {
+        sumN += n_patches[b];
+        if (n_patches[b] > maxN) maxN = n_patches[b];
+    }
+    const int64_t rows = 2 * (sumN + (int64_t)B * T);
+    if (rows + 512 > INT32_MAX / 4 || (int64_t)nseq * (maxN + T) + 512 > INT32_MAX / 4)
+        return fail("vtq_forward_varlen: %lld token rows exceed the 32-bit row index of the kernels", (long long)rows);
+    const bool use_scales = c.num_scales > 1;
+    if (use_scales && (!scales_ref || !scales_dist)) return fail("Model uses scale embedding but scales is passed as None.");   // transformer.py:547-548
+    if (all_loaded(e, "vtq_forward_varlen")) return 1;
+    if (reserve(e, B, maxN)) return 1;                      // an upper bound for every buffer: the batch is no larger than B pairs of maxN
+    hipStream_t s = (hipStream_t)stream;
+
+    Geometry g;
+    g.S = g.S_pad = maxN + T;                               // the largest sequence: the chunk pitch of the CLS fold's partials
+    g.nseq = nseq;
+    g.M_pad = round_up(rows, 256);
+    g.P_pad = round_up(2 * sumN, 256);
+    g.rows_alloc = (g.M_pad > g.P_pad ? g.M_pad : g.P_pad) + 128;
+    g.R_pad = round_up(nseq, 64);
+    g.sm = SeqMap{(int)rows, 1, (int)(g.M_pad - rows)};     // the whole batch as ONE run of rows: what the pad-row clear needs to know
+
+    // ---- the call's tables: host image, then ONE upload on `s` ahead of every launch ---------------------------------------------
+    const int off_len = nseq + 1, off_pfx = 2 * nseq + 1, off_blk = (int)round_up(3 * nseq + 4, 4);
+    VarLen vl{};
+    {
+        std::vector<int> len(nseq);
+        for (int j = 0; j < nseq; ++j) len[j] = n_patches[j % B] + T;
+        const std::vector<int> blocks = attention_varlen_blocks(len.data(), nseq, H);
+        const size_t ints = (size_t)off_blk + blocks.size();
+        if ((int64_t)ints > varlen_table_ints(e->capB * 2, e->capN + T, H)) return fail("vtq_forward_varlen: table of %zu ints exceeds the reserved workspace", ints);
+        if (!e->vl_uploaded) HIP_TRY(hipEventCreateWithFlags(&e->vl_uploaded, hipEventDisableTiming));
+        else HIP_TRY(hipEventSynchronize(e->vl_uploaded));  // the previous call's upload has read the image (long done, as a rule)
+        if (e->vl_host_ints < ints) {
+            if (e->vl_host) (void)hipHostFree(e->vl_host);
+            e->vl_host = nullptr; e->vl_host_ints = 0;
+            HIP_TRY(hipHostMalloc((void**)&e->vl_host, ints * sizeof(int), hipHostMallocDefault));
+            e->vl_host_ints = ints;
+        }
+        int* t = e->vl_host;
+        int64_t r = 0;
+        for (int j = 0; j < nseq; ++j) { t[j] = (int)r; t[off_len + j] = len[j]; r += len[j]; }
+        t[nseq] = (int)r;
+        int pf = 0;
+        for (int b = 0; b < B; ++b) { t[off_pfx + b] = pf; pf += n_patches[b]; }
+        t[off_pfx + B] = pf;
+        for (int k = off_pfx + B + 1; k < off_blk; ++k) t[k] = 0;
+        memcpy(t + off_blk, blocks.data(), blocks.size() * sizeof(int));
+        HIP_TRY(hipMemcpyAsync(e->vl_tab, t, ints * sizeof(int), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipEventRecord(e->vl_uploaded, s));
+        vl = VarLen{e->vl_tab, e->vl_tab + off_len, e->vl_tab + off_pfx, e->vl_tab + off_blk, (int)(blocks.size() / 4)};
+    }
+    {   // tile schedules of this batch's GEMM shapes (first forward of a tile grid only; see DESIGN.md section 4 for what bounds the cache)
+        const int wpl = e->wpl, M = (int)g.M_pad;
+        HIP_TRY(gemm_prepare((int)g.P_pad, H, (int)e->PDp, wpl, s));
+        HIP_TRY(gemm_prepare(M, 3 * H, H, wpl, s));
+        HIP_TRY(gemm_prepare(M, H, H, wpl, s));
+        HIP_TRY(gemm_prepare(M, e->Mdim, H, wpl, s));
+        HIP_TRY(gemm_prepare(M, H, e->Mdim, wpl, s));
+        if (c.num_adapters > 0) { HIP_TRY(gemm_prepare(M, (int)e->Hqp, H, wpl, s)); HIP_TRY(gemm_prepare(M, H, (int)e->Hqp, wpl, s)); }
+    }
+
+    // ---- embeddings: vtq_forward's launches, the sequence map replaced by the tables ----------------------------------------------
+    const float* patches[2] = {patches_ref, patches_dist};
+    const float* pos[2] = {pos_ref, pos_dist};
+    const float* scales[2] = {scales_ref, scales_dist};
+    {
+        Prof p(e, s, VTQ_K_CONVERT);
+        HIP_TRY(launch_pack_patches(patches, 2, e->big, e->big_plane, (int)sumN, c.patch_dim, (int)g.P_pad, e->f16, e->apl, s, 1.0f, (int)e->PDp));
+        HIP_TRY(launch_embed_index(pos, use_scales ? scales : nullptr, 2, e->pidx, e->sidx, e->row_map, B, (int)sumN, (int)g.P_pad, g.sm, T,
+                                   c.pos_grid, c.num_scales, e->err_flag, s, vl.prefix, vl.row0));
+        HIP_TRY(launch_zero_pad_rows(e->x, 1, (int)rows, g.sm, H, (int)g.rows_alloc, s));
+        HIP_TRY(launch_tokens(e->x, e->cls, e->pos_table, e->extra, nseq, g.sm, T, H, s, vl.row0));
+    }
+    {
+        Prof p(e, s, VTQ_K_PATCH);
+        GemmArgs a = gemm_args(View{e->big, e->big_plane, (int)e->PDp}, e->patch, (int)g.P_pad, View{}, 1.0f / e->s_patch);
+        a.x = e->x;
+        a.row_map = e->row_map; a.idx1 = e->pidx; a.table1 = e->pos_table;
+        a.idx2 = e->sidx; a.table2 = use_scales ? e->scale_table : nullptr;
+        HIP_TRY(launch_gemm(a, e->lin, EPI_EMBED, s));
+    }
+    // the 128 slack rows of the QKV layout behind M_pad (forward_impl has the reasoning): finite before the first layer reads them
+    for (int pl = 0; pl < e->apl; ++pl)
+        HIP_TRY(hipMemsetAsync((char*)e->big + ((size_t)pl * e->big_plane + (size_t)g.M_pad * 3 * H) * 2, 0, (size_t)128 * 3 * H * 2, s));
+
+    const bool prune = e->cls_prune && c.num_adapters == 0;
+    if (run_encoder(e, g, s, prune, &vl)) return 1;
+    {
+        Prof p(e, s, VTQ_K_HEAD);
+        float* d = e->hb[0];
+        const PlaneOut hp{e->hp[0], e->hp_plane, H, 1, 2, head_first_slope(e)};
+        const float* gamma = c.diff_scale ? e->diff_gamma : nullptr;
+        if (prune) HIP_TRY(launch_final_diff(e->xcls, e->encw, e->encb, gamma, d, B, 1, SeqMap{1, nseq, 0}, H, hp, s, e->err_flag));
+        else HIP_TRY(launch_final_diff(e->x + (int64_t)e->iqa_token * H, e->encw, e->encb, gamma, d, B, 1, g.sm, H, hp, s, e->err_flag, vl.row0));
+        if (run_head(e, d, B, q_out, s, true)) return 1;
+    }
+    return 0;
+}
+
 static int forward_triplet(vtq_handle e, const char* who, bool tokens_in, const float* const* in, const float* const* pos,
                            const float* const* scales, int32_t B, int32_t N, float* q_out, void* stream) {
     if (!in || !pos) return fail("%s: null argument", who);
@@ -1201,6 +1339,39 @@ int vtq_k_attention(const void* qkv, int64_t plane, void* out, int64_t o_plane, 
     const Num nm = num_from_code(num);
     if (!num_valid(nm) || nm.terms == 2) return fail("vtq_k_attention: operand format code %d", num);
     HIP_TRY(launch_attention(qkv, plane, out, o_plane, nseq, S, S_pad, H, nm, (hipStream_t)stream));
+    return 0;
+}
+
+int vtq_vl_attention_blocks(int32_t nseq, const int32_t* seq_len, int32_t H, int32_t* out, int32_t cap) {
+    if (nseq < 1 || !seq_len || H < 64 || H % 64) return -1;
+    int64_t rows = 0;
+    for (int j = 0; j < nseq; ++j) {
+        if (seq_len[j] < 1) return -1;
+        rows += seq_len[j];
+    }
+    if (rows + 512 > INT32_MAX / 4) return -1;
+    const std::vector<int> t = attention_varlen_blocks(seq_len, nseq, H);
+    if (out)
+        for (size_t i = 0; i < t.size() && (int64_t)i < (int64_t)cap * 4; ++i) out[i] = t[i];
+    return (int)(t.size() / 4);
+}
+
+int vtq_vl_attention(const void* qkv, int64_t plane, void* out, int64_t o_plane, int32_t nseq, const int32_t* seq_len, int32_t H, int32_t num,
+                     void* stream) {
+    const Num nm = num_from_code(num);
+    if (!num_valid(nm) || nm.terms == 2 || nm.f16 > 1) return fail("vtq_vl_attention: operand format code %d", num);
+    if (!qkv || !out || !seq_len) return fail("vtq_vl_attention: null argument");
+    const int nblocks = vtq_vl_attention_blocks(nseq, seq_len, H, nullptr, 0);
+    if (nblocks < 1) return fail("vtq_vl_attention: nseq=%d, H=%d or a sequence length < 1", (int)nseq, (int)H);
+    hipStream_t s = (hipStream_t)stream;
+    const std::vector<int> t = attention_varlen_blocks(seq_len, nseq, H);
+    int* dev = nullptr;
+    HIP_TRY(hipMalloc((void**)&dev, t.size() * sizeof(int)));
+    hipError_t err = hipMemcpyAsync(dev, t.data(), t.size() * sizeof(int), hipMemcpyHostToDevice, s);
+    if (err == hipSuccess) err = launch_attention_varlen(qkv, plane, out, o_plane, dev, nblocks, H, nm, s);
+    const hipError_t err2 = hipStreamSynchronize(s);        // the table is a temporary of this call
+    (void)hipFree(dev);
+    if (err != hipSuccess || err2 != hipSuccess) return fail("vtq_vl_attention: %s", hipGetErrorString(err != hipSuccess ? err : err2));
     return 0;
 }
 

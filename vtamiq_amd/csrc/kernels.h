@@ -33,6 +33,10 @@ inline bool num_valid(Num n) {
 // sequences per part-batch, each part-batch padded by `gap` rows to a multiple of 256 (the GEMM tile height).
 struct SeqMap { int pitch, per, gap; };
 __host__ __device__ inline int64_t seq_row(const SeqMap& m, int s) { return (int64_t)s * m.pitch + (int64_t)(s / m.per) * m.gap; }
+// Variable-length batches (vtq_forward_varlen): sequences of different lengths packed back to back.  Device tables, [nseq] each: the
+// first row of sequence j in the activation buffers (the prefix sum of the lengths) and its length S_j.  Both NULL = the uniform
+// SeqMap / (stride, S) form of the kernel that takes one; with tables the kernel addresses by them and computes the same arithmetic.
+struct VarSeq { const int* row0; const int* len; };
 
 // Optional 16-bit plane copy of a kernel's fp32 row output, in the form the next skinny stage reads (PReLU(*slope) first when
 // slope != NULL); p == NULL: none.
@@ -115,14 +119,17 @@ hipError_t launch_pack_patches(const float* const* imgs, int nimg, void* dst, in
 // per patch row r in [0, rows_pad): pos index, scale index (sc == nullptr: none), destination row in the residual stream (or -1);
 // positions outside [0, 1) are clamped into the table and flagged in *err (bit 0)
 hipError_t launch_embed_index(const float* const* pos, const float* const* sc, int nimg, int* pidx, int* sidx, int* row_map, int B, int N,
-                              int rows_pad, SeqMap sm, int T, int grid, int num_scales, int* err, hipStream_t s);
+                              int rows_pad, SeqMap sm, int T, int grid, int num_scales, int* err, hipStream_t s,
+                              const int* vl_prefix = nullptr, const int* vl_row0 = nullptr);
+// vl_prefix != NULL (variable length): vl_prefix[b] patches lie in front of pair b in each image, vl_prefix[B] = N = the patches of one
+// image (all pairs); patch row -> pair by search in the prefix, row_map = vl_row0[img * B + pair] + T + (row - vl_prefix[pair])
 
 // CLS (+pos row 0) and register tokens into the first T rows of every sequence
 // pre-embedded input (transformer.py:534-535): x[row_map[r]] = feats[r] + table1[pidx[r]] (+ table2[sidx[r]]); feats: nimg pointers to (B*N, H) fp32
 hipError_t launch_embed_rows(const float* const* feats, int nimg, int BN, const int* row_map, const int* pidx, const int* sidx,
                              const float* table1, const float* table2, float* x, int H, hipStream_t s);
 hipError_t launch_tokens(float* x, const float* cls, const float* pos_table, const float* extra, int nseq, SeqMap sm,
-                         int T, int H, hipStream_t s);
+                         int T, int H, hipStream_t s, const int* vl_row0 = nullptr);     // vl_row0: sequence j starts at row vl_row0[j]
 
 hipError_t launch_layernorm(const float* x, const float* w, const float* b, void* out, int64_t o_plane, int rows, int H,
                             int f16, int planes, hipStream_t s, float scale = 1.0f, Fp8Obs obs = Fp8Obs{nullptr, nullptr});
@@ -133,6 +140,12 @@ hipError_t launch_layernorm(const float* x, const float* w, const float* b, void
 // projection's weights); otherwise the kernels fold it into their Q fragments themselves (attention.hip prescale_q)
 hipError_t launch_attention(const void* qkv, int64_t plane, void* out, int64_t o_plane, int nseq, int S, int S_pad, int H,
                             Num num, hipStream_t s, float out8_scale = 0.0f, Fp8Obs obs = Fp8Obs{nullptr, nullptr}, bool q_log2 = false);
+// The same attention over sequences of different lengths packed back to back (attention_varlen.hip): `blocks` = DEVICE copy of
+// attention_varlen_blocks(), 4 ints per workgroup {first row, S_j, 128-row query block, head}.  A sequence's rows have the bits
+// launch_attention gives that sequence alone (nseq = 1, S = S_pad = S_j).  Rows read: as launch_attention, <= 127 behind the last sequence.
+hipError_t launch_attention_varlen(const void* qkv, int64_t plane, void* out, int64_t o_plane, const int* blocks, int nblocks, int H, Num num,
+                                   hipStream_t s, bool q_log2 = false);
+std::vector<int> attention_varlen_blocks(const int* seq_len, int nseq, int H);      // host only
 
 // softmax(Q K^T / sqrt(64)) of every (sequence, head) as fp32 probs[nseq][H / 64][S][S] (attention_probs.hip), from the same QKV planes
 // launch_attention reads; num.terms 1 or 3, q_log2 as there.  Reads rows [seq * S_pad, seq * S_pad + S) of each sequence only.
@@ -152,7 +165,7 @@ hipError_t launch_seq_rows_ln(const float* x, const float* ln_w, const float* ln
 
 // d[j*B + b] = gamma * (LN(x[row(b)]) - LN(x[row((j+1)*B + b)])), j < ndist  (final encoder_norm on the CLS rows only; vtamiq.py:104-111)
 hipError_t launch_final_diff(const float* x, const float* ln_w, const float* ln_b, const float* gamma, float* d, int B, int ndist,
-                             SeqMap sm, int H, PlaneOut po, hipStream_t s, int* err = nullptr);
+                             SeqMap sm, int H, PlaneOut po, hipStream_t s, int* err = nullptr, const int* vl_row0 = nullptr);
 
 // one-time RCAB weight fold [Wc ; Wd Wc], bcat = [bc ; Wd bc + bd] (head.hip)
 hipError_t launch_fold_ca(const float* Wc, const float* bc, const float* Wd, const float* bd, float* Wcat, float* bcat, int H, int hid,
@@ -185,7 +198,7 @@ hipError_t launch_rows_to_planes(const float* x, int ldx, const float* slope, vo
 
 // ---- CLS-only tail of the last encoder layer (cls_tail.hip) -----------------------------------------------------------
 hipError_t launch_rows_ln(const float* src, int64_t stride, const float* w, const float* b, float* ln, float* copy, int rows, int H,
-                          PlaneOut po, hipStream_t s);
+                          PlaneOut po, hipStream_t s, const int* vl_row0 = nullptr);     // vl_row0: row r is src + vl_row0[r] * H instead
 // Folded single-query attention of the tail (cls_tail.hip): with one query per (sequence, head) K and V are never formed.
 //   u[r][h][:] = W_k,h^T q[r][64h ..]   (wk: rows H .. 2H-1 of the packed QKV weight, `wplanes` planes of row pitch ldw, f16 as elsewhere)
 //   per sequence r, over its S fp32 rows x + r * seq_stride + s * H normalised with (lw, lb): softmax_s(u . ln_s) weighted sum of ln_s,
@@ -194,7 +207,9 @@ hipError_t launch_rows_ln(const float* src, int64_t stride, const float* w, cons
 // part fp32 [nseq][ceil(S / cls_fold_chunk_rows())][H / 64][H + 2].  H = 768 | 1024; any S.  A sequence's result depends on S alone.
 hipError_t launch_cls_fold(const float* q, const void* wk, int64_t w_plane, int ldw, int f16, int wplanes, const float* x, int64_t seq_stride,
                            const float* lw, const float* lb, float* u, float* part, int nseq, int S, int H, PlaneOut zo, hipStream_t s,
-                           bool q_log2 = false);
+                           bool q_log2 = false, VarSeq vl = VarSeq{nullptr, nullptr});
+// vl (variable length): sequence r is the vl.len[r] rows from x + vl.row0[r] * H; S = the LARGEST length (the chunk pitch of `part`);
+// a sequence's chunks are those of its own length, combined in chunk order: its result is what the uniform form gives for S = vl.len[r]
 int cls_fold_chunk_rows();
 
 // ---- on-device image -> patch tensor (patches.hip) -------------------------------------------------------

@@ -11,6 +11,7 @@ There is no CPU or eager fallback: a forward on CPU tensors, in train mode, or w
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 import warnings
 from typing import Optional
@@ -582,6 +583,63 @@ class VTAMIQ(nn.Module):
                     if _trace is not None:
                         lib.vtq_set_token_trace(self._engine, None)
             self._launch_checked(device, launch)
+        return q, None
+
+    def forward_varlen(self, patches, pos, scales, lengths):
+        """forward() on B pairs with DIFFERENT patch counts in one launch sequence: pair b has lengths[b] >= 1 patches in both images.
+          patches  (ref, dist): each the pairs' patches concatenated, (sum(lengths), 3, P, P) -- or a list of B per-pair (n_b, 3, P, P) tensors,
+                   concatenated here on the device
+          pos      (ref, dist) of (sum(lengths), 2), scales (ref, dist) of (sum(lengths),) or None as in forward(); lists likewise
+          lengths  a sequence of ints or a CPU integer tensor (a CUDA tensor is refused: reading it would synchronise the stream)
+        Returns (q, None), q (B,) fp32: q[b] has the bits `self((ref_b, dist_b), ...)` gives for pair b alone, in every precision; equal
+        lengths give the bits of forward().  The input / range policy ("auto", validate_inputs, check_inputs) is forward()'s."""
+        if self.training:
+            raise NotImplementedError(_TRAIN_MSG)
+        if self._FP8_EXPERIMENT:
+            raise NotImplementedError("forward_varlen is not available for the fp8 experiment's model")
+        if isinstance(lengths, torch.Tensor):
+            if lengths.device.type != "cpu":
+                raise ValueError("lengths must be a sequence of ints or a CPU integer tensor: a CUDA tensor would force a device synchronisation")
+            if lengths.dtype.is_floating_point or lengths.dtype.is_complex or lengths.dtype == torch.bool or lengths.dim() != 1:
+                raise ValueError("lengths must be a 1-D integer tensor")
+            lengths = lengths.tolist()
+        lens = [int(v) for v in lengths]
+        if not lens or any(v < 1 for v in lens) or any(int(v) != v for v in lengths):
+            raise ValueError(f"lengths must hold at least one pair and only integers >= 1, got {list(lengths)}")
+        B, total = len(lens), sum(lens)
+
+        def joined(ts, what, tail):                 # per-pair tensors -> the concatenated tensor, as one "batch" of sum(lengths) rows for _inputs
+            if ts is None:
+                return None
+            if len(ts) != 2:
+                raise ValueError(f"{what} must be a (ref, dist) pair")
+            out = []
+            for t in ts:
+                if t is None:
+                    out.append(None)
+                    continue
+                if isinstance(t, (list, tuple)):
+                    if len(t) != B or any(u.shape[0] != n for u, n in zip(t, lens)):
+                        raise ValueError(f"{what}: a list must hold one tensor per pair with lengths[b] rows each")
+                    t = torch.cat([u.reshape(u.shape[0], *tail) for u in t], 0)
+                if t.shape[0] != total or t.numel() != total * math.prod(tail):
+                    raise ValueError(f"{what}: {tuple(t.shape)} does not hold sum(lengths) = {total} rows of shape {tuple(tail)}")
+                out.append(t.reshape(1, total, *tail))
+            return tuple(out)
+        P = self.spec.patch_size
+        first = patches[0][0] if isinstance(patches[0], (list, tuple)) else patches[0]
+        if first.dim() != 4:
+            raise ValueError(f"forward_varlen takes patches as (sum(lengths), 3, {P}, {P}) tensors (pre-embedded input is not offered), got {tuple(first.shape)}")
+        pt = joined(patches, "patches", tuple(first.shape[1:]))
+        ps = joined(pos, "pos", (2,)) if self.spec.use_pos_embedding else pos
+        sc = joined(scales, "scales", ()) if self.spec.use_scale_embedding else None
+        device, _, _, _, (pr, pd), (qr, qd), (sr, sdist) = self._inputs(pt, ps, sc)
+        with torch.cuda.device(device):
+            q = torch.empty(B, device=device, dtype=torch.float32)
+            n_arr = (C.c_int32 * B)(*lens)
+            stream = torch.cuda.current_stream(device).cuda_stream
+            self._launch_checked(device, lambda lib: self._check(lib.vtq_forward_varlen(
+                self._engine, pr.data_ptr(), pd.data_ptr(), qr.data_ptr(), qd.data_ptr(), _ptr(sr), _ptr(sdist), B, n_arr, q.data_ptr(), stream)))
         return q, None
 
     def forward_pairwise(self, patches, pos, scales):
