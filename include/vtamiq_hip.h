@@ -163,6 +163,48 @@ int  vtq_forward_pairwise_tokens(vtq_handle h, const float* const* feats, const 
 int  vtq_forward_vit(vtq_handle h, const float* in, int32_t tokens_in, const float* pos, const float* scales, int32_t B, int32_t N,
                      int32_t all_tokens, float* out, float* states, float* probs, void* stream);
 
+/* ---- one-to-many scoring: M distorted images over G references, every reference encoded ONCE -------------------------------------------
+ * Full-reference data holds a few references with many distorted versions each; these entries encode G + M (or M) sequences where
+ * vtq_forward on the expanded pairs encodes 2 M.  Distorted image m is scored against reference ref_index[m]; ref_index is a HOST array of M
+ * entries in [0, G), in any order, with repeats and unused references allowed, read before the call returns and uploaded to a buffer of THIS
+ * handle on `stream` ahead of the first launch (through the handle's pinned image, as vtq_forward_varlen's tables: a second call waits for the
+ * previous call's upload, not for its kernels).
+ * The contract of all of them: q_out[m] has the bits vtq_forward gives for the single pair (reference ref_index[m], distorted m) (B = 1) on the
+ * same handle, in every numerics mode, with the CLS-only last layer and with VTQ_OPT_FULL_LAST_LAYER -- a score never depends on what else is
+ * in the batch.  vtq_input_errors bits 0 and 1 as vtq_forward; a NaN distorted image makes only its own score NaN, a NaN reference exactly
+ * the scores that point at it.  Asynchronous on `stream`.  Workspace: as vtq_forward with ceil(sequences / 2) pairs (vtq_workspace_bytes).
+ * Refused with vtq_last_error text and no launch: a NULL ref_index (where one is taken); G, M or N < 1; a ref_index[m] outside [0, G); a NULL
+ * handle, tensor or output; the fp8 experiment's handle; a set token trace buffer (vtq_set_token_trace).
+ *
+ * vtq_forward_group: references and distorted images in one batch of G + M sequences.
+ *   patches_ref : [G, N, 3, P, P] fp32 contiguous      pos_ref  : [G, N, 2]      scales_ref  : [G, N] or NULL, under the rule of vtq_forward
+ *   patches_dist: [M, N, 3, P, P]                      pos_dist : [M, N, 2]      scales_dist : [M, N] or NULL
+ *   ref_index   : HOST int32 [M]                       q_out    : [M] fp32
+ * The two patch tensors are read where they lie (no device-side concatenation). */
+int  vtq_forward_group(vtq_handle h, const float* patches_ref, const float* patches_dist, const float* pos_ref, const float* pos_dist,
+                       const float* scales_ref, const float* scales_dist, int32_t G, int32_t M, int32_t N, const int32_t* ref_index,
+                       float* q_out, void* stream);
+/* vtq_forward_group on PRE-EMBEDDED input (as vtq_forward_tokens): feats_ref [G, N, hidden_size], feats_dist [M, N, hidden_size]. */
+int  vtq_forward_group_tokens(vtq_handle h, const float* feats_ref, const float* feats_dist, const float* pos_ref, const float* pos_dist,
+                              const float* scales_ref, const float* scales_dist, int32_t G, int32_t M, int32_t N, const int32_t* ref_index,
+                              float* q_out, void* stream);
+/* The reference cache, for distorted images that arrive after their reference.  vtq_encode_reference encodes G SINGLE images
+ *   in : [G, N, 3, P, P] fp32 patches, or (tokens_in != 0) [G, N, hidden_size] pre-embedded rows;  pos : [G, N, 2];  scales : [G, N] or NULL
+ * and writes ref_rows : [G, hidden_size] fp32 (exactly G * hidden_size floats, caller-owned: they outlive any later call and any workspace
+ * growth) = the residual-stream row of the consumed token (vtq_set_iqa_token) after the last layer, BEFORE encoder_norm -- what the
+ * difference behind vtq_forward reads, so a later vtq_forward_cached does the same arithmetic.  The last layer runs in the form vtq_forward
+ * picks (the CLS-only tail unless VTQ_OPT_FULL_LAST_LAYER or adapters force the full layer), not vtq_forward_vit's always-full one.  A
+ * non-finite value in a row raises vtq_input_errors bit 1.  The rows belong to this handle's numerics mode, weights, options and consumed
+ * token: the caller keeps track of those (vtamiq_amd.ReferenceFeatures does). */
+int  vtq_encode_reference(vtq_handle h, const float* in, int32_t tokens_in, const float* pos, const float* scales, int32_t G, int32_t N,
+                          float* ref_rows, void* stream);
+/* vtq_forward_cached encodes the M distorted images only and takes the reference rows from ref_rows through ref_index:
+ *   ref_rows : [G, hidden_size] fp32 of vtq_encode_reference (read only: rows ref_index[m], nothing else)
+ *   in       : [M, N, 3, P, P] or (tokens_in != 0) [M, N, hidden_size];  pos : [M, N, 2];  scales : [M, N] or NULL;  q_out : [M] fp32
+ * N need not be the N the references were encoded with: nothing behind the encoder depends on it. */
+int  vtq_forward_cached(vtq_handle h, const float* ref_rows, int32_t G, const float* in, int32_t tokens_in, const float* pos,
+                        const float* scales, int32_t M, int32_t N, const int32_t* ref_index, float* q_out, void* stream);
+
 /* Input check.  The reference raises (IndexError / device assert) when a position lies outside [0, 1)
  * (transformer.py:417-421); vtq_forward clamps such an index into the table instead of gathering out of bounds and records it.
  * Bit 1: the CLS difference of some pair was not finite -- an operand left its format's range upstream (the fp16 operand modes

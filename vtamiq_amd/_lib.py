@@ -60,6 +60,12 @@ SIGNATURES = {
                                               C.c_int32, C.c_void_p, C.c_void_p]),
     "vtq_forward_vit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vtq_forward_group": (C.c_int, [C.c_void_p] + [C.c_void_p] * 6 + [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]),
+    "vtq_forward_group_tokens": (C.c_int, [C.c_void_p] + [C.c_void_p] * 6 + [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_void_p,
+                                           C.c_void_p]),
+    "vtq_encode_reference": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "vtq_forward_cached": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                     C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]),
     "vtq_set_token_trace": (C.c_int, [C.c_void_p, C.c_void_p]),
     "vtq_set_iqa_token": (C.c_int, [C.c_void_p, C.c_int32]),
     "vtq_debug_stop_after": (C.c_int, [C.c_void_p, C.c_int32]),

@@ -82,20 +82,33 @@ __global__ __launch_bounds__(256) void quant_rows_fp8_kernel(const float* __rest
 }
 
 // rows [k*BN, (k+1)*BN) from image k (k < nimg: ref, dist[, dist2]); rows >= nimg*BN zero.  K = 768 floats per row.
+// Unequal groups (vtq_forward_group: G references, M distorted images): image 0 holds R0 rows, every later image BN -- the inputs are read
+// where they lie, whatever their sizes.
 struct ImgPtrs { const float* p[3]; };
 
+// patch row r of the packed batch -> its image and its row inside that image
+__device__ __forceinline__ void img_of_row(int64_t r, int R0, int BN, int& img, int64_t& rr) {
+    if (r < R0) { img = 0; rr = r; return; }
+    const int64_t t = r - R0;
+    const int k = (int)(t / BN);
+    img = 1 + k;
+    rr = t - (int64_t)k * BN;
+}
+
 template <typename T, int NPL>
-__global__ __launch_bounds__(256) void pack_patches_kernel(ImgPtrs src, int nimg, T* __restrict__ dst, int64_t plane, int BN, int K4,
+__global__ __launch_bounds__(256) void pack_patches_kernel(ImgPtrs src, int nimg, T* __restrict__ dst, int64_t plane, int R0, int BN, int K4,
                                                            int Kp4, int64_t total4, float scale, Fp8Obs obs) {
     float m = 0.f;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total4; i += (int64_t)gridDim.x * blockDim.x) {
         const int64_t row = i / Kp4;                    // destination rows are Kp4 >= K4 quads wide, zero beyond K4
         const int c4 = (int)(i - row * Kp4);
-        const int img = (int)(row / BN);
+        int img;
+        int64_t rr;
+        img_of_row(row, R0, BN, img, rr);
         float4 v = {0.f, 0.f, 0.f, 0.f};
         if (img < nimg && c4 < K4) {
             const float* sp = img == 0 ? src.p[0] : (img == 1 ? src.p[1] : src.p[2]);
-            v = ((const float4*)sp)[(row - (int64_t)img * BN) * K4 + c4];
+            v = ((const float4*)sp)[rr * K4 + c4];
         }
         if constexpr (std::is_same<T, f8>::value) m = amax4(m, v.x, v.y, v.z, v.w);
         store4<T, NPL>(dst + i * 4, plane, v.x, v.y, v.z, v.w, scale);
@@ -109,14 +122,17 @@ __global__ __launch_bounds__(256) void pack_patches_kernel(ImgPtrs src, int nimg
 // pos outside [0, 1); here an out-of-range index (pos < 0, pos >= 1, NaN) is clamped into the table and reported through
 // *err (bit 0), which vtq_input_errors() reads back: never an out-of-bounds gather.
 __global__ void embed_index_kernel(ImgPtrs pos, ImgPtrs sc, int nimg, int* __restrict__ pidx, int* __restrict__ sidx,
-                                   int* __restrict__ row_map, int B, int N, int rows_pad, SeqMap sm, int T, int grid, int num_scales,
+                                   int* __restrict__ row_map, int B0, int B, int N, int rows_pad, SeqMap sm, int T, int grid, int num_scales,
                                    int* __restrict__ err, const int* __restrict__ vl_prefix, const int* __restrict__ vl_row0) {
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= rows_pad) return;
     const int BN = vl_prefix ? N : B * N;                 // variable length: N = the patches of one image (all pairs)
-    const int img = r / BN;
+    const int R0 = vl_prefix ? N : B0 * N;                // image 0 holds B0 sequences, every later image B (variable length: B0 = B)
+    int img;
+    int64_t rr64;
+    img_of_row(r, R0, BN, img, rr64);
     if (img >= nimg) { pidx[r] = 0; sidx[r] = 0; row_map[r] = -1; return; }
-    const int rr = r - img * BN;
+    const int rr = (int)rr64;
     const float* pb = img == 0 ? pos.p[0] : (img == 1 ? pos.p[1] : pos.p[2]);
     const float* pp = pb + (int64_t)rr * 2;
     const float g = (float)grid;
@@ -143,18 +159,20 @@ __global__ void embed_index_kernel(ImgPtrs pos, ImgPtrs sc, int nimg, int* __res
         return;
     }
     const int b = rr / N, n = rr - b * N;
-    row_map[r] = (int)seq_row(sm, img * B + b) + T + n;
+    row_map[r] = (int)seq_row(sm, (img == 0 ? 0 : B0 + (img - 1) * B) + b) + T + n;
 }
 
 // Embeddings.forward on PRE-EMBEDDED input (transformer.py:534-535: a (B, N, H) tensor skips the patch convolution): token row = feature row + positional
 // row + scale row, in the reference's order of additions (:540-552); the destinations and table indices are embed_index_kernel's.
-__global__ __launch_bounds__(256) void embed_rows_kernel(ImgPtrs feats, int nimg, int BN, const int* __restrict__ row_map, const int* __restrict__ pidx,
+__global__ __launch_bounds__(256) void embed_rows_kernel(ImgPtrs feats, int nimg, int R0, int BN, const int* __restrict__ row_map, const int* __restrict__ pidx,
                                                          const int* __restrict__ sidx, const float* __restrict__ table1,
                                                          const float* __restrict__ table2, float* __restrict__ x, int H4) {
     const int r = blockIdx.x;
-    const int img = r / BN, rr = r - img * BN;
+    int img;
+    int64_t rr;
+    img_of_row(r, R0, BN, img, rr);
     const float* fb = img == 0 ? feats.p[0] : (img == 1 ? feats.p[1] : feats.p[2]);
-    const float4* src = (const float4*)(fb + (int64_t)rr * H4 * 4);
+    const float4* src = (const float4*)(fb + rr * H4 * 4);
     const int orow = row_map[r];
     if (orow < 0) return;
     const float4* t1 = (const float4*)table1 + (int64_t)pidx[r] * H4;
@@ -253,6 +271,31 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
     }
 }
 
+// d[orow] = gamma * (LN(xr) - LN(xd)) for one (reference row, distorted row) pair: fp32 row and the head's planes, one wave.  THE
+// difference of every scoring entry point: final_diff_kernel and group_diff_kernel only differ in where the two rows come from.
+template <int V4>
+__device__ __forceinline__ void diff_rows(const float* __restrict__ xr, const float* __restrict__ xd, const float* __restrict__ w,
+                                          const float* __restrict__ b, const float* __restrict__ gamma, float* __restrict__ d,
+                                          int64_t orow, const PlaneOut& po, int* __restrict__ err, int lane) {
+    constexpr int H = 256 * V4;
+    float4 yr[V4], yd[V4];
+    ln_row<V4>(xr, w, b, lane, yr);
+    ln_row<V4>(xd, w, b, lane, yd);
+#pragma unroll
+    for (int i = 0; i < V4; ++i) {
+        float4 r = {yr[i].x - yd[i].x, yr[i].y - yd[i].y, yr[i].z - yd[i].z, yr[i].w - yd[i].w};
+        if (gamma) {
+            const float4 g4 = ((const float4*)gamma)[i * 64 + lane];
+            r.x *= g4.x; r.y *= g4.y; r.z *= g4.z; r.w *= g4.w;
+        }
+        ((float4*)(d + orow * H))[i * 64 + lane] = r;
+        plane_store4(po, orow, (i * 64 + lane) * 4, r.x, r.y, r.z, r.w);
+        // a non-finite CLS difference: some operand upstream left its format's range (fp16 planes: |v| > 65504) -- any inf / NaN in a
+        // sequence reaches its CLS row through the softmax.  Reported through vtq_input_errors bit 1.
+        if (err && !(isfinite(r.x) && isfinite(r.y) && isfinite(r.z) && isfinite(r.w))) atomicOr(err, 2);
+    }
+}
+
 // encoder_norm on the two CLS rows of pair b only (transformer.py:376 applies it to all rows; only token 0 is
 // consumed, vtamiq.py:107-108), then diff and diff_scale (vtamiq.py:111).
 template <int V4>
@@ -261,25 +304,38 @@ __global__ __launch_bounds__(64) void final_diff_kernel(const float* __restrict_
                                                         float* __restrict__ d, int B, SeqMap sm, PlaneOut po, int* __restrict__ err,
                                                         const int* __restrict__ vl_row0) {
     constexpr int H = 256 * V4;
-    const int lane = threadIdx.x;
     const int pb = blockIdx.x, j = blockIdx.y;           // j-th distorted image (0 for FR pairs; 0,1 for pairwise triplets)
-    float4 yr[V4], yd[V4];
     const int sd = (j + 1) * B + pb;                     // vl_row0 (variable length): the sequences' first rows come from the table
-    ln_row<V4>(x + (vl_row0 ? (int64_t)vl_row0[pb] : seq_row(sm, pb)) * H, w, b, lane, yr);
-    ln_row<V4>(x + (vl_row0 ? (int64_t)vl_row0[sd] : seq_row(sm, sd)) * H, w, b, lane, yd);
-#pragma unroll
-    for (int i = 0; i < V4; ++i) {
-        float4 r = {yr[i].x - yd[i].x, yr[i].y - yd[i].y, yr[i].z - yd[i].z, yr[i].w - yd[i].w};
-        if (gamma) {
-            const float4 g4 = ((const float4*)gamma)[i * 64 + lane];
-            r.x *= g4.x; r.y *= g4.y; r.z *= g4.z; r.w *= g4.w;
-        }
-        ((float4*)(d + (int64_t)(j * B + pb) * H))[i * 64 + lane] = r;
-        plane_store4(po, (int64_t)(j * B + pb), (i * 64 + lane) * 4, r.x, r.y, r.z, r.w);
-        // a non-finite CLS difference: some operand upstream left its format's range (fp16 planes: |v| > 65504) -- any inf / NaN in a
-        // sequence reaches its CLS row through the softmax.  Reported through vtq_input_errors bit 1.
-        if (err && !(isfinite(r.x) && isfinite(r.y) && isfinite(r.z) && isfinite(r.w))) atomicOr(err, 2);
+    diff_rows<V4>(x + (vl_row0 ? (int64_t)vl_row0[pb] : seq_row(sm, pb)) * H, x + (vl_row0 ? (int64_t)vl_row0[sd] : seq_row(sm, sd)) * H, w, b, gamma, d,
+                  (int64_t)(j * B + pb), po, err, threadIdx.x);
+}
+
+// The one-to-many form (vtq_forward_group, vtq_forward_cached): distorted image m against reference ref_index[m].  Reference row g lies at
+// xr + g * r_stride (the workspace's rows, or a caller's cached rows: vtq_encode_reference), distorted row m at xd + m * d_stride; strides
+// in elements.  ref_index: DEVICE table of M entries in [0, G), checked on the host.
+template <int V4>
+__global__ __launch_bounds__(64) void group_diff_kernel(const float* __restrict__ xr, int64_t r_stride, const float* __restrict__ xd,
+                                                        int64_t d_stride, const int* __restrict__ ref_index, const float* __restrict__ w,
+                                                        const float* __restrict__ b, const float* __restrict__ gamma, float* __restrict__ d,
+                                                        PlaneOut po, int* __restrict__ err) {
+    const int m = blockIdx.x;
+    diff_rows<V4>(xr + (int64_t)ref_index[m] * r_stride, xd + (int64_t)m * d_stride, w, b, gamma, d, (int64_t)m, po, err, threadIdx.x);
+}
+
+// vtq_encode_reference: rows src + r * stride (the consumed token's residual row of each sequence, BEFORE encoder_norm: exactly what the
+// difference kernels read) -> out[r][H], fp32.  A non-finite value raises bit 1 of the error word, as seq_rows_ln_kernel does.
+__global__ __launch_bounds__(256) void export_rows_kernel(const float* __restrict__ src, int64_t stride, float* __restrict__ out, int H4,
+                                                          int* __restrict__ err) {
+    const int r = blockIdx.x;
+    const float4* s4 = (const float4*)(src + (int64_t)r * stride);
+    float4* o = (float4*)out + (int64_t)r * H4;
+    bool ok = true;
+    for (int c = threadIdx.x; c < H4; c += blockDim.x) {
+        const float4 v = s4[c];
+        o[c] = v;
+        ok = ok && isfinite(v.x) && isfinite(v.y) && isfinite(v.z) && isfinite(v.w);
     }
+    if (err && !ok) atomicOr(err, 2);
 }
 
 // encoder_norm on `rows` token rows of every sequence (forward_vit, transformer.py:376): fp32 rows out[seq][rows][H], packed with
@@ -365,14 +421,16 @@ hipError_t launch_split(const float* src, void* dst, int64_t plane, int64_t nume
 }
 
 hipError_t launch_pack_patches(const float* const* imgs, int nimg, void* dst, int64_t plane, int BN, int K, int rows_pad, int f16_,
-                               int planes, hipStream_t s, float scale, int Kp, Fp8Obs obs) {
+                               int planes, hipStream_t s, float scale, int Kp, Fp8Obs obs, int R0) {
     if (Kp == 0) Kp = K;
+    if (R0 == 0) R0 = BN;
+    if (BN < 1 || R0 < 1) return hipErrorInvalidValue;
     if (K % 4 || Kp % 4 || Kp < K) return hipErrorInvalidValue;
     const int K4 = K / 4, Kp4 = Kp / 4;
     const int64_t total4 = (int64_t)rows_pad * Kp4;
     ImgPtrs ip{{imgs[0], imgs[1], nimg > 2 ? imgs[2] : nullptr}};
 #define VTQ_CALL(TT, NP) \
-    hipLaunchKernelGGL((pack_patches_kernel<TT, NP>), dim3(grid_for(total4, 256)), dim3(256), 0, s, ip, nimg, (TT*)dst, plane, BN, K4, Kp4, total4, scale, obs)
+    hipLaunchKernelGGL((pack_patches_kernel<TT, NP>), dim3(grid_for(total4, 256)), dim3(256), 0, s, ip, nimg, (TT*)dst, plane, R0, BN, K4, Kp4, total4, scale, obs)
     VTQ_FMT_DISPATCH(f16_, planes, VTQ_CALL);
 #undef VTQ_CALL
     return hipGetLastError();
@@ -380,19 +438,23 @@ hipError_t launch_pack_patches(const float* const* imgs, int nimg, void* dst, in
 
 hipError_t launch_embed_index(const float* const* pos, const float* const* sc, int nimg, int* pidx, int* sidx, int* row_map, int B, int N,
                               int rows_pad, SeqMap sm, int T, int grid, int num_scales, int* err, hipStream_t s, const int* vl_prefix,
-                              const int* vl_row0) {
+                              const int* vl_row0, int B0) {
     if ((vl_prefix != nullptr) != (vl_row0 != nullptr)) return hipErrorInvalidValue;
+    if (B0 == 0) B0 = B;
+    if (B < 1 || B0 < 1 || N < 1 || (vl_prefix && B0 != B)) return hipErrorInvalidValue;
     ImgPtrs pp{{pos[0], pos[1], nimg > 2 ? pos[2] : nullptr}};
     ImgPtrs sp{{sc ? sc[0] : nullptr, sc ? sc[1] : nullptr, (sc && nimg > 2) ? sc[2] : nullptr}};
-    hipLaunchKernelGGL(embed_index_kernel, dim3((rows_pad + 255) / 256), dim3(256), 0, s, pp, sp, nimg, pidx, sidx, row_map, B, N, rows_pad,
+    hipLaunchKernelGGL(embed_index_kernel, dim3((rows_pad + 255) / 256), dim3(256), 0, s, pp, sp, nimg, pidx, sidx, row_map, B0, B, N, rows_pad,
                        sm, T, grid, num_scales, err, vl_prefix, vl_row0);
     return hipGetLastError();
 }
 
 hipError_t launch_embed_rows(const float* const* feats, int nimg, int BN, const int* row_map, const int* pidx, const int* sidx,
-                             const float* table1, const float* table2, float* x, int H, hipStream_t s) {
+                             const float* table1, const float* table2, float* x, int H, hipStream_t s, int R0) {
+    if (R0 == 0) R0 = BN;
+    if (BN < 1 || R0 < 1) return hipErrorInvalidValue;
     ImgPtrs fp{{feats[0], feats[1], nimg > 2 ? feats[2] : nullptr}};
-    hipLaunchKernelGGL(embed_rows_kernel, dim3(nimg * BN), dim3(256), 0, s, fp, nimg, BN, row_map, pidx, sidx, table1, table2, x, H / 4);
+    hipLaunchKernelGGL(embed_rows_kernel, dim3(R0 + (nimg - 1) * BN), dim3(256), 0, s, fp, nimg, R0, BN, row_map, pidx, sidx, table1, table2, x, H / 4);
     return hipGetLastError();
 }
 
@@ -435,6 +497,21 @@ hipError_t launch_final_diff(const float* x, const float* ln_w, const float* ln_
     if (H == 768) hipLaunchKernelGGL(final_diff_kernel<3>, dim3(B, ndist), dim3(64), 0, s, x, ln_w, ln_b, gamma, d, B, sm, po, err, vl_row0);
     else if (H == 1024) hipLaunchKernelGGL(final_diff_kernel<4>, dim3(B, ndist), dim3(64), 0, s, x, ln_w, ln_b, gamma, d, B, sm, po, err, vl_row0);
     else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+hipError_t launch_group_diff(const float* xr, int64_t r_stride, const float* xd, int64_t d_stride, const int* ref_index, int M, const float* ln_w,
+                             const float* ln_b, const float* gamma, float* d, int H, PlaneOut po, hipStream_t s, int* err) {
+    if (M < 1 || !ref_index || r_stride % 4 || d_stride % 4) return hipErrorInvalidValue;
+    if (H == 768) hipLaunchKernelGGL(group_diff_kernel<3>, dim3(M), dim3(64), 0, s, xr, r_stride, xd, d_stride, ref_index, ln_w, ln_b, gamma, d, po, err);
+    else if (H == 1024) hipLaunchKernelGGL(group_diff_kernel<4>, dim3(M), dim3(64), 0, s, xr, r_stride, xd, d_stride, ref_index, ln_w, ln_b, gamma, d, po, err);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+hipError_t launch_export_rows(const float* src, int64_t stride, float* out, int rows, int H, hipStream_t s, int* err) {
+    if (rows < 1 || H % 4 || stride % 4) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(export_rows_kernel, dim3(rows), dim3(256), 0, s, src, stride, out, H / 4, err);
     return hipGetLastError();
 }
 

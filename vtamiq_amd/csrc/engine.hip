@@ -344,17 +344,17 @@ struct Geometry {
     SeqMap sm;
 };
 
-// nimg images per item: 1 = single images (vtq_forward_vit), 2 = (ref, dist) FR pair, 3 = (ref, dist1, dist2) pairwise triplet
-Geometry geometry(const vtq_engine* e, int B, int N, int nimg = 2) {
+// nseq sequences of N patches each -- any count: 2B or 3B for pairs and triplets, B single images, G + M for vtq_forward_group
+Geometry geometry_seq(const vtq_engine* e, int nseq, int N) {
     Geometry g;
     g.S = N + e->T;
     // No per-sequence padding: attention masks keys >= S (its last 64-key tile and last 128-query block run into the next
     // sequence's rows, or into the tail / the 128 slack rows: finite values, never stored), every other kernel is
     // row-independent.  Only the whole batch is padded, to the GEMM tile height.
     g.S_pad = g.S;
-    g.nseq = nimg * B;
+    g.nseq = nseq;
     g.M_pad = round_up((int64_t)g.nseq * g.S_pad, 256);
-    g.P_pad = round_up((int64_t)nimg * B * N, 256);
+    g.P_pad = round_up((int64_t)nseq * N, 256);
     // +128: attention over-read slack behind the last sequence.  vtq_k_attention's contract (include/vtamiq_hip.h) is ceil128(S_pad) - S_pad
     // <= 127 rows behind row nseq * S_pad <= M_pad, pinned by tests/test_gpu_footprint.py test_attention with exactly that many rows; 128 is
     // that bound rounded to the GEMM half tile, and the length of the memset in forward_impl
@@ -363,6 +363,8 @@ Geometry geometry(const vtq_engine* e, int B, int N, int nimg = 2) {
     g.sm = SeqMap{g.S_pad, g.nseq, (int)(g.M_pad - (int64_t)g.nseq * g.S_pad)};
     return g;
 }
+// nimg images per item: 1 = single images (vtq_forward_vit), 2 = (ref, dist) FR pair, 3 = (ref, dist1, dist2) pairwise triplet
+Geometry geometry(const vtq_engine* e, int B, int N, int nimg = 2) { return geometry_seq(e, nimg * B, N); }
 
 // ints of vtq_forward_varlen's device tables for nseq sequences of at most S rows: row offsets [nseq + 1], lengths [nseq], patch prefix
 // [nseq / 2 + 1] (padded to whole int4), then 4 per attention workgroup -- sum_j ceil(S_j / 128) <= nseq * ceil(S / 128) query blocks per head
@@ -465,6 +467,33 @@ int fp8_stage(vtq_engine* e, hipStream_t s, float& sc, F launch) {
     sc = fp8_pick_scale(m, sc);
     return launch(sc, Fp8Obs{nullptr, e->err_flag});
 }
+
+// One call's host-built table of `ints` ints -> e->vl_tab, as vtq_forward_varlen uploads its own: through the engine's pinned image, ONE
+// copy on `s` ahead of the first launch that reads it, recorded in vl_uploaded, which the next call waits for before it rewrites the image.
+// fill(image) writes the ints.  The workspace must be reserved first (the table lives in it).
+template <typename F>
+int upload_table(vtq_engine* e, const char* who, size_t ints, hipStream_t s, F fill) {
+    if ((int64_t)ints > varlen_table_ints(e->capB * 2, e->capN + e->T, e->H)) return fail("%s: table of %zu ints exceeds the reserved workspace", who, ints);
+    if (!e->vl_uploaded) HIP_TRY(hipEventCreateWithFlags(&e->vl_uploaded, hipEventDisableTiming));
+    else HIP_TRY(hipEventSynchronize(e->vl_uploaded));      // the previous call's upload has read the image (long done, as a rule)
+    if (e->vl_host_ints < ints) {
+        if (e->vl_host) (void)hipHostFree(e->vl_host);
+        e->vl_host = nullptr; e->vl_host_ints = 0;
+        HIP_TRY(hipHostMalloc((void**)&e->vl_host, ints * sizeof(int), hipHostMallocDefault));
+        e->vl_host_ints = ints;
+    }
+    fill(e->vl_host);
+    HIP_TRY(hipMemcpyAsync(e->vl_tab, e->vl_host, ints * sizeof(int), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipEventRecord(e->vl_uploaded, s));
+    return 0;
+}
+
+// The one-to-many forms of forward_impl (include/vtamiq_hip.h): which sequences a call encodes and where the head's reference rows come from.
+//   REF_GROUP   G references + B distorted images in one batch (nimg = 2), distorted image m scored against reference ref_index[m]
+//   REF_ENCODE  B single reference images (nimg = 1): the consumed token's residual row of each goes to the caller's `rows`, no head
+//   REF_CACHED  B single distorted images (nimg = 1) against the caller's G cached `rows`, through ref_index
+enum { REF_PAIRS = 0, REF_GROUP = 1, REF_ENCODE = 2, REF_CACHED = 3 };
+struct RefGroup { int mode; int G; const int32_t* ref_index; float* rows; const char* who; };
 
 // One vtq_forward_varlen call's device tables (in e->vl_tab): sequence j is the len[j] rows from row0[j]; `blocks`: attention_varlen.hip
 struct VarLen { const int* row0; const int* len; const int* prefix; const int* blocks; int nblocks; };
@@ -942,13 +971,19 @@ int vtq_profile_collect(vtq_handle e, double* ms_sum, int64_t* launches) {
 
 // nimg = 2: q_out[B] for (ref, dist); nimg = 3: q_out[2B] = scores of (ref, dist1) then (ref, dist2) with ref encoded once;
 // nimg = 1 (vtq_forward_vit): no head -- vit_out receives encoder_norm of `vit_rows` rows per image (e->vit_states / vit_probs set by the caller)
+// rg (vtq_forward_group / vtq_encode_reference / vtq_forward_cached): image 0 holds rg->G sequences instead of B (REF_GROUP), or the one image
+// is scored against / exported to the caller's rows; the head batch is then B, one score per distorted image
 static int forward_impl(vtq_handle e, int nimg, const float* const* patches, const float* const* pos, const float* const* scales,
-                        int32_t B, int32_t N, float* q_out, void* stream, bool tokens_in = false, float* vit_out = nullptr) {
+                        int32_t B, int32_t N, float* q_out, void* stream, bool tokens_in = false, float* vit_out = nullptr,
+                        const RefGroup* rg = nullptr) {
     if (!e) return fail("vtq_forward: null handle");
+    const int mode = rg ? rg->mode : REF_PAIRS;
+    const int B0 = mode == REF_GROUP ? rg->G : B;            // sequences of image 0
+    const int nseq = B0 + (nimg - 1) * B;
     if (tokens_in && e->fp8) return fail("vtq_forward_tokens: the fp8 experiment has no pre-embedded input path");
     for (int k = 0; k < nimg; ++k)
         if (!patches[k] || !pos[k]) return fail("vtq_forward: null tensor");
-    if (!q_out && nimg > 1) return fail("vtq_forward: null output");
+    if (!q_out && (nimg > 1 || mode == REF_CACHED)) return fail("vtq_forward: null output");
     if (B < 1 || N < 1) return fail("vtq_forward: B=%d N=%d", B, N);
     const vtq_config& c = e->cfg;
     const bool use_scales = c.num_scales > 1;
@@ -956,15 +991,17 @@ static int forward_impl(vtq_handle e, int nimg, const float* const* patches, con
         for (int k = 0; k < nimg; ++k)
             if (!scales[k]) return fail("Model uses scale embedding but scales is passed as None.");   // transformer.py:547-548
     if (all_loaded(e, "vtq_forward")) return 1;
-    if (reserve(e, (nimg * B + 1) / 2, N)) return 1;       // capacity is kept in units of sequence pairs
+    if (reserve(e, (nseq + 1) / 2, N)) return 1;           // capacity is kept in units of sequence pairs
     // fp8 mode: the first forward of an engine calibrates the activation scales on its own batch (see kSPatch); it synchronises
     // the stream once per quantisation point and returns this batch's scores computed with the final scales
     struct CalibGuard { vtq_engine* e; ~CalibGuard() { e->calibrating = false; } } calib_guard{e};
     if (e->fp8 && !e->fp8_static && !e->fp8_calibrated && e->dbg_stop < 0) e->calibrating = true;
-    const int ndist = nimg - 1, HB = ndist * B;            // head batch
+    const int ndist = nimg - 1, HB = mode == REF_PAIRS ? ndist * B : B;      // head batch
     hipStream_t s = (hipStream_t)stream;
-    const Geometry g = geometry(e, B, N, nimg);
+    const Geometry g = geometry_seq(e, nseq, N);
     const int H = e->H, T = e->T;
+    if (mode == REF_GROUP || mode == REF_CACHED)             // ref_index -> the device, ahead of every launch of this call
+        if (upload_table(e, rg->who, (size_t)B, s, [&](int* t) { for (int m = 0; m < B; ++m) t[m] = rg->ref_index[m]; })) return 1;
     {   // tile schedules of this geometry's GEMM shapes: built and uploaded here (first forward of a shape only), not inside a launch
         const int wpl = e->wpl, M = (int)g.M_pad;
         HIP_TRY(gemm_prepare((int)g.P_pad, H, (int)e->PDp, wpl, s));
@@ -983,13 +1020,13 @@ static int forward_impl(vtq_handle e, int nimg, const float* const* patches, con
         Prof p(e, s, VTQ_K_CONVERT);
         if (!tokens_in && e->fp8) {
             if (fp8_stage(e, s, e->s_patch, [&](float sc, Fp8Obs ob) { HIP_TRY(launch_pack_patches(patches, nimg, e->big, e->big_plane, B * N, c.patch_dim, (int)g.P_pad, 2, 1, s, sc, (int)e->PDp, ob)); return 0; })) return 1;
-        } else if (!tokens_in) HIP_TRY(launch_pack_patches(patches, nimg, e->big, e->big_plane, B * N, c.patch_dim, (int)g.P_pad, e->f16, e->apl, s, 1.0f, (int)e->PDp));
+        } else if (!tokens_in) HIP_TRY(launch_pack_patches(patches, nimg, e->big, e->big_plane, B * N, c.patch_dim, (int)g.P_pad, e->f16, e->apl, s, 1.0f, (int)e->PDp, Fp8Obs{nullptr, nullptr}, B0 * N));
         HIP_TRY(launch_embed_index(pos, use_scales ? scales : nullptr, nimg, e->pidx, e->sidx, e->row_map, B, N, (int)g.P_pad, g.sm, T,
-                                   c.pos_grid, c.num_scales, e->err_flag, s));
+                                   c.pos_grid, c.num_scales, e->err_flag, s, nullptr, nullptr, B0));
         HIP_TRY(launch_zero_pad_rows(e->x, g.nseq, g.S, g.sm, H, (int)g.rows_alloc, s));
         HIP_TRY(launch_tokens(e->x, e->cls, e->pos_table, e->extra, g.nseq, g.sm, T, H, s));
         if (tokens_in)
-            HIP_TRY(launch_embed_rows(patches, nimg, B * N, e->row_map, e->pidx, e->sidx, e->pos_table, use_scales ? e->scale_table : nullptr, e->x, H, s));
+            HIP_TRY(launch_embed_rows(patches, nimg, B * N, e->row_map, e->pidx, e->sidx, e->pos_table, use_scales ? e->scale_table : nullptr, e->x, H, s, B0 * N));
     }
     if (!tokens_in) {
         Prof p(e, s, VTQ_K_PATCH);
@@ -1014,9 +1051,10 @@ static int forward_impl(vtq_handle e, int nimg, const float* const* patches, con
     // the trace tap needs every token row of the last layer (the CLS-only tail itself takes any sequence length)
     // (fp8 mode runs the full last layer: its CLS row then goes through the same e4m3 GEMMs as every other row)
     // (forward_vit needs every row of the last layer: always the full last layer)
-    const bool prune = e->cls_prune && !e->trace && !e->fp8 && c.num_adapters == 0 && nimg > 1;
+    // (vtq_encode_reference / vtq_forward_cached encode single images in the form vtq_forward would pick: their rows meet in one difference)
+    const bool prune = e->cls_prune && !e->trace && !e->fp8 && c.num_adapters == 0 && (nimg > 1 || mode != REF_PAIRS);
     if (run_encoder(e, g, s, prune)) return 1;
-    if (nimg == 1) {                 // ---- forward_vit: encoder_norm (transformer.py:376) of the requested rows, no head
+    if (nimg == 1 && mode == REF_PAIRS) {                 // ---- forward_vit: encoder_norm (transformer.py:376) of the requested rows, no head
         Prof p(e, s, VTQ_K_LN);
         HIP_TRY(launch_seq_rows_ln(e->x, e->encw, e->encb, vit_out, g.nseq, g.sm, e->vit_rows, H, s, e->err_flag));
         return 0;
@@ -1027,8 +1065,18 @@ static int forward_impl(vtq_handle e, int nimg, const float* const* patches, con
         Prof p(e, s, VTQ_K_HEAD);
         float* d = e->hb[0];
         const PlaneOut hp{e->hp[0], e->hp_plane, H, 1, 2, head_first_slope(e)};      // the first head stage's input planes
-        if (prune) HIP_TRY(launch_final_diff(e->xcls, e->encw, e->encb, c.diff_scale ? e->diff_gamma : nullptr, d, B, ndist, SeqMap{1, g.nseq, 0}, H, hp, s, e->err_flag));
-        else HIP_TRY(launch_final_diff(e->x + (int64_t)e->iqa_token * H, e->encw, e->encb, c.diff_scale ? e->diff_gamma : nullptr, d, B, ndist, g.sm, H, hp, s, e->err_flag));
+        const float* gamma = c.diff_scale ? e->diff_gamma : nullptr;
+        // the consumed token's residual row of sequence j: row j of the tail's output, or token row iqa_token of sequence j in x
+        const float* rows = prune ? e->xcls : e->x + (int64_t)e->iqa_token * H;
+        const int64_t stride = prune ? H : (int64_t)g.S_pad * H;
+        if (mode == REF_ENCODE) {
+            HIP_TRY(launch_export_rows(rows, stride, rg->rows, B, H, s, e->err_flag));
+            return 0;
+        }
+        if (mode == REF_GROUP) HIP_TRY(launch_group_diff(rows, stride, rows + B0 * stride, stride, e->vl_tab, B, e->encw, e->encb, gamma, d, H, hp, s, e->err_flag));
+        else if (mode == REF_CACHED) HIP_TRY(launch_group_diff(rg->rows, H, rows, stride, e->vl_tab, B, e->encw, e->encb, gamma, d, H, hp, s, e->err_flag));
+        else if (prune) HIP_TRY(launch_final_diff(e->xcls, e->encw, e->encb, gamma, d, B, ndist, SeqMap{1, g.nseq, 0}, H, hp, s, e->err_flag));
+        else HIP_TRY(launch_final_diff(e->x + (int64_t)e->iqa_token * H, e->encw, e->encb, gamma, d, B, ndist, g.sm, H, hp, s, e->err_flag));
         if (run_head(e, d, HB, q_out, s, true)) return 1;
     }
     if (e->calibrating) e->fp8_calibrated = true;
@@ -1253,6 +1301,77 @@ int vtq_forward_vit(vtq_handle e, const float* in, int32_t tokens_in, const floa
     e->vit_probs = probs;
     e->vit_rows = all_tokens ? N + e->T : e->T;
     return forward_impl(e, 1, p, ps, sc, B, N, nullptr, stream, tokens_in != 0, out);
+}
+
+// ---- one-to-many scoring: every reference encoded once (include/vtamiq_hip.h) ---------------------------------------------------------
+// The batch description first (it needs no handle), then the handle, then what the handle decides -- as vtq_forward_varlen
+static int check_group(const char* who, int32_t G, int32_t M, int32_t N, const int32_t* ref_index, bool need_index) {
+    if (need_index && !ref_index) return fail("%s: null ref_index", who);
+    if (G < 1 || M < 1 || N < 1) return fail("%s: G=%d M=%d N=%d", who, (int)G, (int)M, (int)N);
+    if (ref_index)
+        for (int m = 0; m < M; ++m)
+            if (ref_index[m] < 0 || ref_index[m] >= G) return fail("%s: ref_index[%d] = %d outside [0, %d)", who, m, (int)ref_index[m], (int)G);
+    return 0;
+}
+
+static int check_group_handle(const char* who, vtq_handle e) {
+    if (!e) return fail("%s: null handle", who);
+    if (e->fp8) return fail("%s: not available for the fp8 experiment's engine", who);
+    if (e->trace) return fail("%s: a token trace buffer is set (vtq_set_token_trace): the trace layout is per batch of pairs", who);
+    return 0;
+}
+
+static int forward_group(const char* who, vtq_handle e, bool tokens_in, const float* in_ref, const float* in_dist, const float* pos_ref,
+                         const float* pos_dist, const float* scales_ref, const float* scales_dist, int32_t G, int32_t M, int32_t N,
+                         const int32_t* ref_index, float* q_out, void* stream) {
+    if (check_group(who, G, M, N, ref_index, true) || check_group_handle(who, e)) return 1;
+    if (!in_ref || !in_dist || !pos_ref || !pos_dist) return fail("%s: null tensor", who);
+    if (!q_out) return fail("%s: null output", who);
+    const float* p[2] = {in_ref, in_dist};
+    const float* ps[2] = {pos_ref, pos_dist};
+    const float* sc[2] = {scales_ref, scales_dist};
+    const RefGroup rg{REF_GROUP, G, ref_index, nullptr, who};
+    return forward_impl(e, 2, p, ps, sc, M, N, q_out, stream, tokens_in, nullptr, &rg);
+}
+
+int vtq_forward_group(vtq_handle e, const float* patches_ref, const float* patches_dist, const float* pos_ref, const float* pos_dist,
+                      const float* scales_ref, const float* scales_dist, int32_t G, int32_t M, int32_t N, const int32_t* ref_index,
+                      float* q_out, void* stream) {
+    return forward_group("vtq_forward_group", e, false, patches_ref, patches_dist, pos_ref, pos_dist, scales_ref, scales_dist, G, M, N, ref_index,
+                         q_out, stream);
+}
+
+int vtq_forward_group_tokens(vtq_handle e, const float* feats_ref, const float* feats_dist, const float* pos_ref, const float* pos_dist,
+                             const float* scales_ref, const float* scales_dist, int32_t G, int32_t M, int32_t N, const int32_t* ref_index,
+                             float* q_out, void* stream) {
+    return forward_group("vtq_forward_group_tokens", e, true, feats_ref, feats_dist, pos_ref, pos_dist, scales_ref, scales_dist, G, M, N, ref_index,
+                         q_out, stream);
+}
+
+int vtq_encode_reference(vtq_handle e, const float* in, int32_t tokens_in, const float* pos, const float* scales, int32_t G, int32_t N,
+                         float* ref_rows, void* stream) {
+    const char* who = "vtq_encode_reference";
+    if (check_group(who, G, 1, N, nullptr, false) || check_group_handle(who, e)) return 1;
+    if (!in || !pos) return fail("%s: null tensor", who);
+    if (!ref_rows) return fail("%s: null output", who);
+    const float* p[2] = {in, nullptr};
+    const float* ps[2] = {pos, nullptr};
+    const float* sc[2] = {scales, nullptr};
+    const RefGroup rg{REF_ENCODE, G, nullptr, ref_rows, who};
+    return forward_impl(e, 1, p, ps, sc, G, N, nullptr, stream, tokens_in != 0, nullptr, &rg);
+}
+
+int vtq_forward_cached(vtq_handle e, const float* ref_rows, int32_t G, const float* in, int32_t tokens_in, const float* pos, const float* scales,
+                       int32_t M, int32_t N, const int32_t* ref_index, float* q_out, void* stream) {
+    const char* who = "vtq_forward_cached";
+    if (check_group(who, G, M, N, ref_index, true) || check_group_handle(who, e)) return 1;
+    if (!ref_rows || !in || !pos) return fail("%s: null tensor", who);
+    if (!q_out) return fail("%s: null output", who);
+    const float* p[2] = {in, nullptr};
+    const float* ps[2] = {pos, nullptr};
+    const float* sc[2] = {scales, nullptr};
+    const RefGroup rg{REF_CACHED, G, ref_index, const_cast<float*>(ref_rows), who};
+    return forward_impl(e, 1, p, ps, sc, M, N, q_out, stream, tokens_in != 0, nullptr, &rg);
 }
 
 int vtq_input_errors(vtq_handle e, int32_t* flags, void* stream) {

@@ -113,21 +113,23 @@ hipError_t launch_quant_rows_fp8(const float* src, void* dst, float* inv_scale, 
 hipError_t launch_split_rows_pad(const float* src, void* dst, int64_t plane, int rows, int K, int Kp, int f16, int planes, hipStream_t s);
 
 // nimg images (ref, dist[, dist2]) of fp32 patches [B*N, K] each -> 16-bit planes [rows_pad, K], rows >= nimg*B*N zero-filled
+// R0 != 0 (unequal groups, vtq_forward_group): image 0 holds R0 rows, every later image BN; rows >= R0 + (nimg - 1) * BN zero-filled
 hipError_t launch_pack_patches(const float* const* imgs, int nimg, void* dst, int64_t plane, int BN, int K, int rows_pad, int f16,
-                               int planes, hipStream_t s, float scale = 1.0f, int Kp = 0, Fp8Obs obs = Fp8Obs{nullptr, nullptr});
+                               int planes, hipStream_t s, float scale = 1.0f, int Kp = 0, Fp8Obs obs = Fp8Obs{nullptr, nullptr}, int R0 = 0);
 
 // per patch row r in [0, rows_pad): pos index, scale index (sc == nullptr: none), destination row in the residual stream (or -1);
 // positions outside [0, 1) are clamped into the table and flagged in *err (bit 0)
 hipError_t launch_embed_index(const float* const* pos, const float* const* sc, int nimg, int* pidx, int* sidx, int* row_map, int B, int N,
                               int rows_pad, SeqMap sm, int T, int grid, int num_scales, int* err, hipStream_t s,
-                              const int* vl_prefix = nullptr, const int* vl_row0 = nullptr);
+                              const int* vl_prefix = nullptr, const int* vl_row0 = nullptr, int B0 = 0);
+// B0 != 0 (unequal groups): image 0 holds B0 sequences (the first B0 of the batch), every later image B, N patches each
 // vl_prefix != NULL (variable length): vl_prefix[b] patches lie in front of pair b in each image, vl_prefix[B] = N = the patches of one
 // image (all pairs); patch row -> pair by search in the prefix, row_map = vl_row0[img * B + pair] + T + (row - vl_prefix[pair])
 
 // CLS (+pos row 0) and register tokens into the first T rows of every sequence
 // pre-embedded input (transformer.py:534-535): x[row_map[r]] = feats[r] + table1[pidx[r]] (+ table2[sidx[r]]); feats: nimg pointers to (B*N, H) fp32
 hipError_t launch_embed_rows(const float* const* feats, int nimg, int BN, const int* row_map, const int* pidx, const int* sidx,
-                             const float* table1, const float* table2, float* x, int H, hipStream_t s);
+                             const float* table1, const float* table2, float* x, int H, hipStream_t s, int R0 = 0);      // R0: as launch_pack_patches
 hipError_t launch_tokens(float* x, const float* cls, const float* pos_table, const float* extra, int nseq, SeqMap sm,
                          int T, int H, hipStream_t s, const int* vl_row0 = nullptr);     // vl_row0: sequence j starts at row vl_row0[j]
 
@@ -166,6 +168,14 @@ hipError_t launch_seq_rows_ln(const float* x, const float* ln_w, const float* ln
 // d[j*B + b] = gamma * (LN(x[row(b)]) - LN(x[row((j+1)*B + b)])), j < ndist  (final encoder_norm on the CLS rows only; vtamiq.py:104-111)
 hipError_t launch_final_diff(const float* x, const float* ln_w, const float* ln_b, const float* gamma, float* d, int B, int ndist,
                              SeqMap sm, int H, PlaneOut po, hipStream_t s, int* err = nullptr, const int* vl_row0 = nullptr);
+
+// The one-to-many difference: d[m] = gamma * (LN(xr + ref_index[m] * r_stride) - LN(xd + m * d_stride)), m < M, with launch_final_diff's
+// arithmetic, plane store and non-finite report.  ref_index: DEVICE table [M] of values the host has checked against the reference count;
+// strides in elements (% 4 == 0)
+hipError_t launch_group_diff(const float* xr, int64_t r_stride, const float* xd, int64_t d_stride, const int* ref_index, int M, const float* ln_w,
+                             const float* ln_b, const float* gamma, float* d, int H, PlaneOut po, hipStream_t s, int* err = nullptr);
+// out[r][H] = the fp32 row src + r * stride, r < rows (vtq_encode_reference); bit 1 of *err for a non-finite value
+hipError_t launch_export_rows(const float* src, int64_t stride, float* out, int rows, int H, hipStream_t s, int* err = nullptr);
 
 // one-time RCAB weight fold [Wc ; Wd Wc], bcat = [bc ; Wd bc + bd] (head.hip)
 hipError_t launch_fold_ca(const float* Wc, const float* bc, const float* Wd, const float* bd, float* Wcat, float* bcat, int H, int hid,

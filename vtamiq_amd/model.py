@@ -12,6 +12,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+import numbers
 import os
 import warnings
 from typing import Optional
@@ -41,6 +42,63 @@ _COUNT = {1: ("a", "tensor"), 2: ("two", "tensors"), 3: ("three", "tensors")}   
 
 def _ptr(t):
     return None if t is None else t.data_ptr()
+
+
+class StaleReferenceError(ValueError):
+    """A ReferenceFeatures object does not belong to the model state it is used with (precision, consumed token, engine options, weights):
+    its rows would be scored against sequences encoded differently.  Re-encode the references."""
+
+
+class ReferenceFeatures:
+    """What VTAMIQ.encode_reference keeps of G reference images, for VTAMIQ.forward_cached.
+      rows            (G, H) fp32: per image the consumed token's residual-stream row after the last layer, before encoder_norm.  An ordinary
+                      tensor of the caller's allocator: it outlives every later forward and any growth of the engine's workspace
+      precision       the engine's numerics mode that made the rows ("auto" resolved: "fp16x3" | "bf16x3")
+      token           the resolved index of the consumed token (VTAMIQ.token_num; 0 = CLS)
+      engine_options  the model's engine_options
+      signature       the model's weight signature (VTAMIQ._signature()) at encode time
+    The last four are what the rows are valid for; forward_cached raises StaleReferenceError when any of them has changed."""
+    __slots__ = ("rows", "precision", "token", "engine_options", "signature")
+
+    def __init__(self, rows, precision, token, engine_options, signature):
+        self.rows, self.precision, self.token, self.engine_options, self.signature = rows, precision, int(token), int(engine_options), signature
+
+    def __len__(self):
+        return int(self.rows.shape[0])
+
+    @staticmethod
+    def cat(refs):
+        """The references of several encode_reference calls as one object (rows concatenated in order); they must share what made them."""
+        refs = list(refs)
+        first = refs[0]
+        for r in refs[1:]:
+            if (r.precision, r.token, r.engine_options, r.signature) != (first.precision, first.token, first.engine_options, first.signature):
+                raise StaleReferenceError("ReferenceFeatures.cat: the references were encoded under different precisions, tokens, options or weights")
+        return ReferenceFeatures(torch.cat([r.rows for r in refs], 0), first.precision, first.token, first.engine_options, first.signature)
+
+
+def _ref_index(ref_index, G: int, M: int):
+    """`ref_index` of forward_group / forward_cached as a list of M ints in [0, G), checked on the host before any device work.  None: range(M),
+    which needs G == M."""
+    if ref_index is None:
+        if G != M:
+            raise ValueError(f"ref_index=None pairs distorted image m with reference m and needs as many references as distorted images, got G={G}, M={M}")
+        return list(range(M))
+    if isinstance(ref_index, torch.Tensor):
+        if ref_index.device.type != "cpu":
+            raise ValueError("ref_index must be a sequence of ints or a CPU integer tensor: a CUDA tensor would force a device synchronisation")
+        if ref_index.dtype.is_floating_point or ref_index.dtype.is_complex or ref_index.dtype == torch.bool or ref_index.dim() != 1:
+            raise ValueError("ref_index must be a 1-D integer tensor")
+        ref_index = ref_index.tolist()
+    ref_index = list(ref_index)
+    if any(isinstance(v, bool) or not isinstance(v, numbers.Integral) for v in ref_index):
+        raise ValueError(f"ref_index must hold integers only, got {ref_index}")
+    idx = [int(v) for v in ref_index]
+    if len(idx) != M:
+        raise ValueError(f"ref_index must hold one entry per distorted image ({M}), got {len(idx)}")
+    if any(v < 0 or v >= G for v in idx):
+        raise ValueError(f"ref_index must lie in [0, {G}) (the references), got {idx}")
+    return idx
 
 
 class _Params(nn.Module):
@@ -640,6 +698,99 @@ class VTAMIQ(nn.Module):
             stream = torch.cuda.current_stream(device).cuda_stream
             self._launch_checked(device, lambda lib: self._check(lib.vtq_forward_varlen(
                 self._engine, pr.data_ptr(), pd.data_ptr(), qr.data_ptr(), qd.data_ptr(), _ptr(sr), _ptr(sdist), B, n_arr, q.data_ptr(), stream)))
+        return q, None
+
+    # ---- one-to-many scoring: every reference encoded once ----------------------------------------------------------------
+    def _group_guard(self, what):
+        if self.training:
+            raise NotImplementedError(_TRAIN_MSG)
+        if self._FP8_EXPERIMENT:
+            raise NotImplementedError(f"{what} is not available for the fp8 experiment's model")
+
+    def _token(self) -> int:
+        t = int(self.token_num)
+        return t + self.spec.num_tokens if t < 0 else t
+
+    def forward_group(self, patches, pos, scales, ref_index):
+        """M distorted images over G references in ONE call, every reference encoded once: G + M sequences where forward() on the expanded
+        pairs encodes 2 M.
+          patches    (p_ref, p_dist): (G, N, 3, P, P) and (M, N, 3, P, P) -- or both pre-embedded, (G | M, N, H), as in forward()
+          pos        (pos_ref (G, N, 2), pos_dist (M, N, 2));  scales likewise (G | M, N), or (None, None)
+          ref_index  M integers in [0, G), a sequence or a CPU integer tensor (a CUDA tensor is refused: reading it would synchronise the
+                     stream); any order, repeats and unused references are allowed
+        Returns (q, None), q (M,) fp32: q[m] has the bits `self((p_ref[i:i+1], p_dist[m:m+1]), ...)[0]` gives, i = ref_index[m], in every
+        precision and model configuration.  The input / range policy ("auto", validate_inputs, check_inputs) is forward()'s."""
+        self._group_guard("forward_group")
+        if len(patches) != 2:
+            raise ValueError("forward_group expects patches = (p_ref, p_dist)")
+        G, M = int(patches[0].shape[0]), int(patches[1].shape[0])
+        idx = _ref_index(ref_index, G, M)
+        pos = pos if pos is not None else (None, None)
+        scales = scales if scales is not None else (None, None)
+        device, _, N, tokens_in, (pr,), (qr,), (sr,) = self._inputs((patches[0],), (pos[0],), (scales[0],))
+        device_d, _, N_d, tokens_d, (pd,), (qd,), (sdist,) = self._inputs((patches[1],), (pos[1],), (scales[1],))
+        if device_d != device or N_d != N or tokens_d != tokens_in:
+            raise ValueError(f"forward_group: references and distorted images must agree in device, patch count and input form, got "
+                             f"{tuple(patches[0].shape)} / {tuple(patches[1].shape)}")
+        with torch.cuda.device(device):
+            q = torch.empty(M, device=device, dtype=torch.float32)
+            arr = (C.c_int32 * M)(*idx)
+            stream = torch.cuda.current_stream(device).cuda_stream
+            self._launch_checked(device, lambda lib: self._check((lib.vtq_forward_group_tokens if tokens_in else lib.vtq_forward_group)(
+                self._engine, pr.data_ptr(), pd.data_ptr(), qr.data_ptr(), qd.data_ptr(), _ptr(sr), _ptr(sdist), G, M, N, arr, q.data_ptr(), stream)))
+        return q, None
+
+    def encode_reference(self, patches, pos, scales=None) -> ReferenceFeatures:
+        """Encode G reference images once, for forward_cached(): (G, N, 3, P, P) patches (or pre-embedded (G, N, H)), pos (G, N, 2), scales
+        (G, N) or None.  Returns a ReferenceFeatures whose `.rows` (G, H) are an ordinary tensor of the caller's.  The input / range policy is
+        forward()'s; check_inputs() raises FloatingPointError for a non-finite row."""
+        self._group_guard("encode_reference")
+        device, G, N, tokens_in, (pt,), (pp,), (ps,) = self._inputs((patches,), (pos,), (scales,))
+        with torch.cuda.device(device):
+            rows = torch.empty(G, self.spec.hidden_size, device=device, dtype=torch.float32)
+            stream = torch.cuda.current_stream(device).cuda_stream
+            self._launch_checked(device, lambda lib: self._check(lib.vtq_encode_reference(
+                self._engine, pt.data_ptr(), int(tokens_in), pp.data_ptr(), _ptr(ps), G, N, rows.data_ptr(), stream)))
+        # read AFTER the launch: "auto" may have switched the model to bf16x3 and repeated the call -- the rows are that run's
+        return ReferenceFeatures(rows, self.engine_precision, self._token(), self.engine_options, self._signature())
+
+    def _stale(self, ref: ReferenceFeatures):
+        now = (self.engine_precision, self._token(), self.engine_options)
+        if (ref.precision, ref.token, ref.engine_options) != now:
+            return f"encoded under (precision, token, engine_options) = {(ref.precision, ref.token, ref.engine_options)}, the model is now at {now}"
+        if ref.signature != self._signature():
+            return "the model's weights are not the ones that encoded them (another model, load_state_dict, .to(), an optimizer step)"
+        return None
+
+    def forward_cached(self, ref: ReferenceFeatures, patches_dist, pos_dist, scales_dist=None, ref_index=None):
+        """Score M distorted images against references encoded earlier (encode_reference): M sequences are encoded, nothing of the references.
+          ref           ReferenceFeatures of G references, made by THIS model in its present state (else StaleReferenceError, a ValueError)
+          patches_dist  (M, N, 3, P, P) or pre-embedded (M, N, H); pos_dist (M, N, 2); scales_dist (M, N) or None.  N need not be the
+                        references' N
+          ref_index     as forward_group(); None = range(M), which needs G == M
+        Returns (q, None) with forward_group()'s contract.  Under precision "auto" an fp16 overflow switches the model to bf16x3 as usual and
+        the call then raises StaleReferenceError: the cached rows are fp16x3 rows; encode the references again."""
+        self._group_guard("forward_cached")
+        if not isinstance(ref, ReferenceFeatures):
+            raise TypeError("forward_cached takes the ReferenceFeatures of encode_reference as its first argument")
+        G, M = len(ref), int(patches_dist.shape[0])
+        idx = _ref_index(ref_index, G, M)
+        why = self._stale(ref)
+        if why:
+            raise StaleReferenceError(f"forward_cached: the reference features are stale: {why}; encode_reference again")
+        device, _, N, tokens_in, (pt,), (pp,), (ps,) = self._inputs((patches_dist,), (pos_dist,), (scales_dist,))
+        rows = ref.rows
+        if rows.device != device or rows.dtype != torch.float32 or tuple(rows.shape) != (G, self.spec.hidden_size) or not rows.is_contiguous():
+            raise ValueError(f"forward_cached: ref.rows must be a contiguous fp32 (G, {self.spec.hidden_size}) tensor on {device}")
+        with torch.cuda.device(device):
+            q = torch.empty(M, device=device, dtype=torch.float32)
+            arr = (C.c_int32 * M)(*idx)
+            stream = torch.cuda.current_stream(device).cuda_stream
+            self._launch_checked(device, lambda lib: self._check(lib.vtq_forward_cached(
+                self._engine, rows.data_ptr(), G, pt.data_ptr(), int(tokens_in), pp.data_ptr(), _ptr(ps), M, N, arr, q.data_ptr(), stream)))
+        if self.engine_precision != ref.precision:
+            raise StaleReferenceError(f"forward_cached: an operand left the fp16 range and the model now runs {self.engine_precision!r}; the cached "
+                                      f"rows are {ref.precision!r} rows: encode_reference again")
         return q, None
 
     def forward_pairwise(self, patches, pos, scales):
