@@ -138,6 +138,32 @@ int  vtq_forward_varlen(vtq_handle h, const float* patches_ref, const float* pat
 int  vtq_forward_tokens(vtq_handle h, const float* feats_ref, const float* feats_dist, const float* pos_ref, const float* pos_dist,
                         const float* scales_ref, const float* scales_dist, int32_t B, int32_t N, float* q_out, void* stream);
 
+/* vtq_forward plus the ATTENTION ROLLOUT of the token the score is read from (Abnar & Zuidema): which patches each image's score looked at.
+ * With T = 1 + num_extra_tokens, S = T + N, L = num_layers, h = num_heads, t = the consumed token (vtq_set_iqa_token), and P_l[k][b][hd] the
+ * S x S matrix softmax(Q K^T / 8) of layer l, head hd, image k (0 = reference, 1 = distorted) of pair b -- exactly vtq_forward_vit's `probs`:
+ *     A_l = 1/2 (I + 1/h sum_hd P_l[hd])           rollout[k][b][:] = e_t^T A_L A_{L-1} ... A_1           last_attention[k][b][hd][:] = P_L[k][b][hd][t][:]
+ * evaluated as a row vector from the last layer to the first, r <- 1/2 r + 1/(2h) sum_hd r^T P_l[hd]; no S x S matrix is stored.  Tokens
+ * first, then the N patches in input order; every value > 0, each rollout row sums to 1.  Nothing else is applied (no renormalisation over
+ * patches, no discarding of heads).
+ *   rollout_out        : fp32, EXACTLY 2 * B * S floats ([2][B][S]); required
+ *   last_attention_out : fp32, EXACTLY 2 * B * h * S floats ([2][B][h][S]); may be NULL
+ *   every other argument as vtq_forward / vtq_forward_tokens; q_out has the bits vtq_forward gives.
+ * A pair's rollout and last_attention do not depend on the batch it is in.  Asynchronous on `stream`; vtq_input_errors as vtq_forward.
+ * The Q / K planes of every layer survive the forward in buffers of their own, reserved by these entries only and grown like the
+ * workspace: vtq_rollout_workspace_bytes(h, B, N) bytes on top of vtq_workspace_bytes (about num_layers times the QKV buffer);
+ * vtq_workspace_bytes and every other entry are unchanged.  The scores still come from the CLS-only last layer; its Q and K rows are
+ * projected in addition, because the probabilities vtq_forward_vit reports are those of the 16-bit Q / K planes, which the tail never forms.
+ * Refused with vtq_last_error text and no launch: a NULL handle or rollout_out; B or N < 1; the fp8 experiment's handle; a set token trace
+ * buffer (vtq_set_token_trace); a set vtq_debug_stop_after.  The varlen, group, cached and pairwise entries have no rollout form. */
+int  vtq_forward_rollout(vtq_handle h, const float* patches_ref, const float* patches_dist, const float* pos_ref, const float* pos_dist,
+                         const float* scales_ref, const float* scales_dist, int32_t B, int32_t N, float* q_out, float* rollout_out,
+                         float* last_attention_out, void* stream);
+int  vtq_forward_rollout_tokens(vtq_handle h, const float* feats_ref, const float* feats_dist, const float* pos_ref, const float* pos_dist,
+                                const float* scales_ref, const float* scales_dist, int32_t B, int32_t N, float* q_out, float* rollout_out,
+                                float* last_attention_out, void* stream);
+/* Bytes of the extra device workspace a vtq_forward_rollout call of (B pairs, N patches) holds beside vtq_workspace_bytes(h, B, N). */
+size_t vtq_rollout_workspace_bytes(vtq_handle h, int32_t B, int32_t N);
+
 /* Pairwise items (train.predict, train.py:281-301: two model calls sharing the reference image): patches/pos/scales are HOST
  * arrays of 3 DEVICE pointers {ref, dist1, dist2}, each as in vtq_forward (scales may be NULL); the reference image is
  * encoded ONCE (3B sequences instead of 4B).  q_out[2B]: q_out[b] = score(ref_b, dist1_b), q_out[B + b] = score(ref_b, dist2_b);

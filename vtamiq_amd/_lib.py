@@ -54,6 +54,9 @@ SIGNATURES = {
     "vtq_forward": (C.c_int, [C.c_void_p] + [C.c_void_p] * 6 + [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "vtq_forward_varlen": (C.c_int, [C.c_void_p] + [C.c_void_p] * 6 + [C.c_int32, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]),
     "vtq_forward_tokens": (C.c_int, [C.c_void_p] + [C.c_void_p] * 6 + [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "vtq_forward_rollout": (C.c_int, [C.c_void_p] + [C.c_void_p] * 6 + [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vtq_forward_rollout_tokens": (C.c_int, [C.c_void_p] + [C.c_void_p] * 6 + [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vtq_rollout_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int32, C.c_int32]),
     "vtq_forward_pairwise": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int32,
                                        C.c_int32, C.c_void_p, C.c_void_p]),
     "vtq_forward_pairwise_tokens": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int32,
@@ -115,6 +118,12 @@ SIGNATURES = {
                                         C.c_int32, C.c_void_p]),
 }
 
+# include/vtamiq_hip_rollout.h: the unit entry of the attention-rollout step (the scoring entries vtq_forward_rollout* are in SIGNATURES)
+ROLLOUT_SIGNATURES = {
+    "vtq_k_rollout_step": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                     C.c_int32, C.c_int32, C.c_void_p]),
+}
+
 # the fp8 experiment (include/vtamiq_hip_fp8.h): exported only by a library built with -DVTQ_WITH_FP8 (python -m vtamiq_amd.build --fp8 ->
 # LIB_PATH_FP8, load_fp8()); bound when present
 FP8_SIGNATURES = {
@@ -149,7 +158,7 @@ def load(path: str | None = None) -> C.CDLL:
     # VTQ_LIB_PATH selects WHICH build is loaded (e.g. a build of another tree, for an A/B); it does not relax any check.  An A/B
     # build of an OLDER tree (different ABI: argument layouts may differ) loads only with VTQ_ALLOW_ABI_MISMATCH=1, with a warning.
     relaxed = os.environ.get("VTQ_ALLOW_ABI_MISMATCH") == "1"
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(ROLLOUT_SIGNATURES.items()):
         if relaxed and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)          # AttributeError if a declared symbol is not exported

@@ -18,6 +18,7 @@
 
 #include "../../include/vtamiq_hip.h"
 #include "../../include/vtamiq_hip_fp8.h"
+#include "../../include/vtamiq_hip_rollout.h"
 #include "kernels.h"
 
 using namespace vtq;
@@ -174,6 +175,16 @@ struct vtq_engine {
     float* vit_states = nullptr;
     float* vit_probs = nullptr;
     int vit_rows = 0;
+    // vtq_forward_rollout: the caller's outputs (one call's worth; NULL otherwise) and the workspace only such a call reserves: one QKV
+    // buffer per layer, in which its Q / K planes survive the forward, the row vector (ping-pong), the step's partials
+    float* ro_out = nullptr;
+    float* ro_last = nullptr;
+    bool ro_on = false;
+    int ro_capB = 0, ro_capN = 0;
+    std::vector<void*> ro_qkv;
+    int64_t ro_plane = 0;
+    float *ro_r[2] = {nullptr, nullptr}, *ro_part = nullptr;
+    std::vector<void*> ro_allocs;
     int iqa_token = 0;                          // vtamiq.py:57, 107-108: the token row the head consumes (0 = CLS, 1 .. = register tokens)
     // profiling
     uint32_t prof_mask = 0;
@@ -429,6 +440,50 @@ int reserve(vtq_engine* e, int B, int N) {
     return 0;
 }
 
+// ---- vtq_forward_rollout's extra workspace (include/vtamiq_hip.h): held beside workspace(), reserved by such a call only -------------
+// One QKV buffer per layer.  The last layer's too: the CLS tail never forms K, and its folded scores (fp32 rows against W_k^T q) are not
+// the ones forward_vit reports -- they differ from them by the operand rounding of the mode, 2e-2 in bf16 on peaked attention -- so a
+// rollout call projects the last layer's Q and K as well (run_encoder), and every layer's row comes from the same step kernel.
+struct RolloutWs { int64_t qkv_elems, r_floats, part_floats; };
+RolloutWs rollout_ws(const vtq_engine* e, int B, int N) {
+    const Geometry g = geometry(e, B, N);
+    const int64_t nh = e->H / 64;
+    return RolloutWs{g.rows_alloc * 3 * e->H, (int64_t)g.nseq * g.S, (int64_t)g.nseq * nh * ((g.S + 127) / 128) * g.S};
+}
+size_t rollout_bytes(const vtq_engine* e, int B, int N) {
+    const RolloutWs w = rollout_ws(e, B, N);
+    return (size_t)e->cfg.num_layers * w.qkv_elems * 2 * e->apl + (size_t)(2 * w.r_floats + w.part_floats) * 4;
+}
+
+// grows like reserve(): to the largest (B, N) seen, everything freed and allocated again.  The QKV buffers are zero-filled as `big` is
+int reserve_rollout(vtq_engine* e, int B, int N) {
+    if (B <= e->ro_capB && N <= e->ro_capN && e->ro_part) return 0;
+    const int nB = B > e->ro_capB ? B : e->ro_capB, nN = N > e->ro_capN ? N : e->ro_capN;
+    HIP_TRY(hipDeviceSynchronize());
+    for (void* p : e->ro_allocs) (void)hipFree(p);
+    e->ro_allocs.clear();
+    e->ro_part = nullptr;
+    e->ro_capB = e->ro_capN = 0;
+    const RolloutWs w = rollout_ws(e, nB, nN);
+    auto alloc = [&](void** p, size_t bytes, bool zero) {
+        HIP_TRY(hipMalloc(p, bytes ? bytes : 16));
+        e->ro_allocs.push_back(*p);
+        if (zero) HIP_TRY(hipMemset(*p, 0, bytes));
+        return 0;
+    };
+    e->ro_qkv.assign(e->cfg.num_layers, nullptr);
+    for (void*& q : e->ro_qkv)
+        if (alloc(&q, (size_t)w.qkv_elems * 2 * e->apl, true)) return 1;
+    e->ro_plane = w.qkv_elems;
+    if (alloc((void**)&e->ro_r[0], w.r_floats * 4, false) || alloc((void**)&e->ro_r[1], w.r_floats * 4, false) ||
+        alloc((void**)&e->ro_part, w.part_floats * 4, false))
+        return 1;
+    HIP_TRY(hipDeviceSynchronize());
+    e->ro_capB = nB;
+    e->ro_capN = nN;
+    return 0;
+}
+
 struct Prof {
     vtq_engine* e; hipStream_t s; int cls; bool on; hipEvent_t a, b;
     Prof(vtq_engine* e_, hipStream_t s_, int cls_) : e(e_), s(s_), cls(cls_), on((e_->prof_mask >> cls_) & 1u) {
@@ -508,6 +563,8 @@ int run_encoder(vtq_engine* e, const Geometry& g, hipStream_t s, bool prune, con
     // the two activation buffers, as planes of row length ld.  QKV (ld 3H) and the MLP hidden (ld M) alias in `big`: never live together
     auto lnv = [&](int ld) { return View{e->lnbuf, e->ln_plane, ld}; };
     auto bigv = [&](int ld) { return View{e->big, e->big_plane, ld}; };
+    // layer i's QKV planes: in `big`, or (vtq_forward_rollout) in a buffer of the layer's own, where Q and K survive the forward
+    auto qkvv = [&](int i) { return (e->ro_on && i < (int)e->ro_qkv.size()) ? View{e->ro_qkv[i], e->ro_plane, 3 * H} : bigv(3 * H); };
     float *xcls = e->xcls, *lncls = e->lncls, *qcls = e->qcls;
     const int64_t trace_stride = (int64_t)g.nseq * T * H;
     // LayerNorm inside the residual GEMMs (gemm_rowln.hip): the out-proj launch also writes LayerNorm 2's planes, the fc2 launch the
@@ -561,6 +618,13 @@ int run_encoder(vtq_engine* e, const Geometry& g, hipStream_t s, bool prune, con
         const Layer& Ly = e->layers[i];
         const bool tail = prune && i == L - 1;
         if (!(fused && i > 0) && !tail && layernorm(Ly.ln1w, Ly.ln1b, e->s_ln1[i])) return 1;
+        if (tail && e->ro_on) {
+            // vtq_forward_rollout: the rollout needs this layer's Q and K planes of every row, which the tail below never forms (see
+            // RolloutWs).  LayerNorm 1 into lnbuf (free here: the tail reads x) and the query | key rows of the QKV GEMM; x is not touched
+            if (layernorm(Ly.ln1w, Ly.ln1b, e->s_ln1[i])) return 1;
+            Prof p(e, s, VTQ_K_QKV);
+            HIP_TRY(launch_gemm(gemm_args(lnv(H), lin_rows(Ly.qkv, 0, 2 * H), M, qkvv(i)), lin, EPI_BIAS, s));
+        }
         if (tail) {
             // ---- last layer: the R consumed rows only (cls_tail.hip).  Their one query per head is folded into the key and value
             // projections, so no other row is normalised or projected: the attention streams the fp32 residual rows themselves
@@ -609,18 +673,19 @@ int run_encoder(vtq_engine* e, const Geometry& g, hipStream_t s, bool prune, con
         if (e->dbg_stop == i * 7 + 0) return 0;
         {
             Prof p(e, s, VTQ_K_QKV);
-            HIP_TRY(launch_gemm(gemm_args(lnv(H), Ly.qkv, M, bigv(3 * H), 1.0f / e->s_ln1[i]), lin, EPI_BIAS, s));
+            HIP_TRY(launch_gemm(gemm_args(lnv(H), Ly.qkv, M, qkvv(i), 1.0f / e->s_ln1[i]), lin, EPI_BIAS, s));
         }
         if (e->dbg_stop == i * 7 + 1) return 0;
         {
             Prof p(e, s, VTQ_K_ATTN);
+            const View qv = qkvv(i);
             if (f8m) {
                 if (fp8_stage(e, s, e->s_att[i], [&](float sc, Fp8Obs ob) { HIP_TRY(launch_attention(e->big, e->big_plane, e->lnbuf, e->ln_plane, g.nseq, g.S, g.S_pad, H, e->att, s, sc, ob, e->att.terms == 3)); return 0; })) return 1;
-            } else if (vl) HIP_TRY(launch_attention_varlen(e->big, e->big_plane, e->lnbuf, e->ln_plane, vl->blocks, vl->nblocks, H, e->att, s, e->att.terms == 3));
-            else HIP_TRY(launch_attention(e->big, e->big_plane, e->lnbuf, e->ln_plane, g.nseq, g.S, g.S_pad, H, e->att, s, 0.0f, Fp8Obs{nullptr, nullptr}, e->att.terms == 3));
+            } else if (vl) HIP_TRY(launch_attention_varlen(qv.p, qv.plane, e->lnbuf, e->ln_plane, vl->blocks, vl->nblocks, H, e->att, s, e->att.terms == 3));
+            else HIP_TRY(launch_attention(qv.p, qv.plane, e->lnbuf, e->ln_plane, g.nseq, g.S, g.S_pad, H, e->att, s, 0.0f, Fp8Obs{nullptr, nullptr}, e->att.terms == 3));
             // forward_vit's attention maps: from the same QKV planes, before the out-proj (with adapters it reuses `big`)
             if (e->vit_probs)
-                HIP_TRY(launch_attention_probs(e->big, e->big_plane, e->vit_probs + (int64_t)i * g.nseq * (H / 64) * g.S * g.S, g.nseq, g.S, g.S_pad, H,
+                HIP_TRY(launch_attention_probs(qv.p, qv.plane, e->vit_probs + (int64_t)i * g.nseq * (H / 64) * g.S * g.S, g.nseq, g.S, g.S_pad, H,
                                                e->att, s, e->att.terms == 3));
         }
         if (e->dbg_stop == i * 7 + 2) return 0;
@@ -809,6 +874,7 @@ void vtq_destroy(vtq_handle e) {
     if (e->vl_host) (void)hipHostFree(e->vl_host);
     if (e->vl_uploaded) (void)hipEventDestroy(e->vl_uploaded);
     for (void* p : e->ws_allocs) (void)hipFree(p);
+    for (void* p : e->ro_allocs) (void)hipFree(p);
     for (auto& ev : e->ev_used) { (void)hipEventDestroy(ev.a); (void)hipEventDestroy(ev.b); }
     for (auto& ev : e->ev_free) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
     delete e;
@@ -969,6 +1035,20 @@ int vtq_profile_collect(vtq_handle e, double* ms_sum, int64_t* launches) {
     return 0;
 }
 
+// Attention rollout of the consumed token behind a forward that kept every layer's Q / K planes (e->ro_qkv): one step per layer, last to
+// first, every launch on s.  The walk starts at r = e_token, so the first step's per-head sums are the last layer's attention row of the
+// token: last_attention.  The row vector ping-pongs between the two workspace vectors; the LAST step writes the caller's rollout_out itself
+// ([nseq][S] is its layout), so there is no copy.
+static int run_rollout(vtq_engine* e, const Geometry& g, hipStream_t s) {
+    const int H = e->H, L = e->cfg.num_layers, t = e->iqa_token;
+    const bool ql = e->att.terms == 3;
+    auto dst = [&](int op) { return op == L - 1 ? e->ro_out : e->ro_r[op & 1]; };      // op 0 = the last layer ... op L - 1 = layer 0
+    for (int op = 0; op < L; ++op)
+        HIP_TRY(launch_rollout_step(e->ro_qkv[L - 1 - op], e->ro_plane, op ? dst(op - 1) : nullptr, t, e->ro_part, dst(op), op ? nullptr : e->ro_last,
+                                    g.nseq, g.S, g.S_pad, H, e->att, s, ql));
+    return 0;
+}
+
 // nimg = 2: q_out[B] for (ref, dist); nimg = 3: q_out[2B] = scores of (ref, dist1) then (ref, dist2) with ref encoded once;
 // nimg = 1 (vtq_forward_vit): no head -- vit_out receives encoder_norm of `vit_rows` rows per image (e->vit_states / vit_probs set by the caller)
 // rg (vtq_forward_group / vtq_encode_reference / vtq_forward_cached): image 0 holds rg->G sequences instead of B (REF_GROUP), or the one image
@@ -992,6 +1072,7 @@ static int forward_impl(vtq_handle e, int nimg, const float* const* patches, con
             if (!scales[k]) return fail("Model uses scale embedding but scales is passed as None.");   // transformer.py:547-548
     if (all_loaded(e, "vtq_forward")) return 1;
     if (reserve(e, (nseq + 1) / 2, N)) return 1;           // capacity is kept in units of sequence pairs
+    if (e->ro_on && reserve_rollout(e, (nseq + 1) / 2, N)) return 1;
     // fp8 mode: the first forward of an engine calibrates the activation scales on its own batch (see kSPatch); it synchronises
     // the stream once per quantisation point and returns this batch's scores computed with the final scales
     struct CalibGuard { vtq_engine* e; ~CalibGuard() { e->calibrating = false; } } calib_guard{e};
@@ -1046,6 +1127,12 @@ static int forward_impl(vtq_handle e, int nimg, const float* const* patches, con
     // them reaches an output, for zeros and for NaNs alike).
     for (int pl = 0; pl < e->apl; ++pl)
         HIP_TRY(hipMemsetAsync((char*)e->big + ((size_t)pl * e->big_plane + (size_t)g.M_pad * 3 * H) * 2, 0, (size_t)128 * 3 * H * 2, s));
+    // (vtq_forward_rollout: the same rows of every retained QKV buffer -- no later stage of this forward writes them, and an earlier,
+    // larger call may have)
+    if (e->ro_on)
+        for (void* q : e->ro_qkv)
+            for (int pl = 0; pl < e->apl; ++pl)
+                HIP_TRY(hipMemsetAsync((char*)q + ((size_t)pl * e->ro_plane + (size_t)g.M_pad * 3 * H) * 2, 0, (size_t)128 * 3 * H * 2, s));
 
     // ---- encoder (transformer.py:363-378, 275-285) -------------------------------------------------------------
     // the trace tap needs every token row of the last layer (the CLS-only tail itself takes any sequence length)
@@ -1079,6 +1166,7 @@ static int forward_impl(vtq_handle e, int nimg, const float* const* patches, con
         else HIP_TRY(launch_final_diff(e->x + (int64_t)e->iqa_token * H, e->encw, e->encb, gamma, d, B, ndist, g.sm, H, hp, s, e->err_flag));
         if (run_head(e, d, HB, q_out, s, true)) return 1;
     }
+    if (e->ro_on && run_rollout(e, g, s)) return 1;
     if (e->calibrating) e->fp8_calibrated = true;
     return 0;
 }
@@ -1148,6 +1236,39 @@ int vtq_forward_tokens(vtq_handle e, const float* feats_ref, const float* feats_
                        const float* scales_ref, const float* scales_dist, int32_t B, int32_t N, float* q_out, void* stream) {
     return forward_pair(e, true, feats_ref, feats_dist, pos_ref, pos_dist, scales_ref, scales_dist, B, N, q_out, stream);
 }
+
+// vtq_forward with the attention rollout of the consumed token (include/vtamiq_hip.h).  What it does not offer is refused before any launch
+static int forward_rollout(const char* who, vtq_handle e, bool tokens_in, const float* in_ref, const float* in_dist, const float* pos_ref,
+                           const float* pos_dist, const float* scales_ref, const float* scales_dist, int32_t B, int32_t N, float* q_out,
+                           float* rollout_out, float* last_attention_out, void* stream) {
+    if (!e) return fail("%s: null handle", who);
+    if (e->fp8) return fail("%s: not available for the fp8 experiment's engine", who);
+    if (e->trace) return fail("%s: a token trace buffer is set (vtq_set_token_trace): the trace tap runs the last layer in another form", who);
+    if (!rollout_out) return fail("%s: null rollout_out", who);
+    if (B < 1 || N < 1 || B > 32767) return fail("%s: B=%d N=%d", who, (int)B, (int)N);
+    if (e->dbg_stop >= 0) return fail("%s: vtq_debug_stop_after is set", who);
+    struct Reset { vtq_engine* e; ~Reset() { e->ro_on = false; e->ro_out = nullptr; e->ro_last = nullptr; } } reset{e};
+    e->ro_on = true;
+    e->ro_out = rollout_out;
+    e->ro_last = last_attention_out;
+    return forward_pair(e, tokens_in, in_ref, in_dist, pos_ref, pos_dist, scales_ref, scales_dist, B, N, q_out, stream);
+}
+
+int vtq_forward_rollout(vtq_handle e, const float* patches_ref, const float* patches_dist, const float* pos_ref, const float* pos_dist,
+                        const float* scales_ref, const float* scales_dist, int32_t B, int32_t N, float* q_out, float* rollout_out,
+                        float* last_attention_out, void* stream) {
+    return forward_rollout("vtq_forward_rollout", e, false, patches_ref, patches_dist, pos_ref, pos_dist, scales_ref, scales_dist, B, N, q_out,
+                           rollout_out, last_attention_out, stream);
+}
+
+int vtq_forward_rollout_tokens(vtq_handle e, const float* feats_ref, const float* feats_dist, const float* pos_ref, const float* pos_dist,
+                               const float* scales_ref, const float* scales_dist, int32_t B, int32_t N, float* q_out, float* rollout_out,
+                               float* last_attention_out, void* stream) {
+    return forward_rollout("vtq_forward_rollout_tokens", e, true, feats_ref, feats_dist, pos_ref, pos_dist, scales_ref, scales_dist, B, N, q_out,
+                           rollout_out, last_attention_out, stream);
+}
+
+size_t vtq_rollout_workspace_bytes(vtq_handle e, int32_t B, int32_t N) { return (e && B >= 1 && N >= 1) ? rollout_bytes(e, B, N) : 0; }
 
 // B pairs of different patch counts through one launch sequence (include/vtamiq_hip.h).  Layout: sequences packed back to back at their
 // own length, all reference sequences, then all distorted ones; the packed patch rows likewise (image, pair, patch).  Every kernel is
@@ -1501,6 +1622,16 @@ int vtq_k_attention_probs(const void* qkv, int64_t plane, float* probs, int32_t 
     if (!qkv || !probs || nseq < 1 || S < 1 || S_pad < S || H < 64 || H % 64) return fail("vtq_k_attention_probs: bad argument");
     if (q_log2 && nm.terms != 3) return fail("vtq_k_attention_probs: q_log2 applies to the 3-term formats only");
     HIP_TRY(launch_attention_probs(qkv, plane, probs, nseq, S, S_pad, H, nm, (hipStream_t)stream, q_log2 != 0));
+    return 0;
+}
+
+int vtq_k_rollout_step(const void* qkv, int64_t plane, const float* r_in, float* r_out, float* part, int32_t nseq, int32_t S, int32_t S_pad,
+                       int32_t H, int32_t num, int32_t q_log2, void* stream) {
+    const Num nm = num_from_code(num);
+    if (!num_valid(nm) || nm.terms == 2 || nm.f16 > 1) return fail("vtq_k_rollout_step: operand format code %d", num);
+    if (!qkv || !r_in || !r_out || !part || nseq < 1 || nseq > 65535 || S < 1 || S_pad < S || H < 64 || H % 64) return fail("vtq_k_rollout_step: bad argument");
+    if (q_log2 && nm.terms != 3) return fail("vtq_k_rollout_step: q_log2 applies to the 3-term formats only");
+    HIP_TRY(launch_rollout_step(qkv, plane, r_in, 0, part, r_out, nullptr, nseq, S, S_pad, H, nm, (hipStream_t)stream, q_log2 != 0));
     return 0;
 }
 

@@ -154,6 +154,13 @@ std::vector<int> attention_varlen_blocks(const int* seq_len, int nseq, int H);  
 hipError_t launch_attention_probs(const void* qkv, int64_t plane, float* probs, int nseq, int S, int S_pad, int H, Num num, hipStream_t s,
                                   bool q_log2 = false);
 
+// One attention-rollout step on the same QKV planes (attention_rollout.hip): out[seq][j] = 1/2 r[seq][j] + 1/(2 h) sum_head (r^T P_head)[j],
+// P = the probabilities launch_attention_probs would store.  r, out: fp32 [nseq][S] (r == NULL: r = e_token); heads_out (may be NULL):
+// fp32 [nseq][H / 64][S] = r^T P_head; part: workspace fp32 [nseq][H / 64][ceil(S / 128)][S].  Two launches (step, combine); reads rows
+// [seq * S_pad, seq * S_pad + S) of each sequence only.  A sequence's result depends on its own rows and S alone.
+hipError_t launch_rollout_step(const void* qkv, int64_t plane, const float* r, int token, float* part, float* out, float* heads_out, int nseq,
+                               int S, int S_pad, int H, Num num, hipStream_t s, bool q_log2 = false);
+
 // zero the rows of the residual stream that belong to no token: per-sequence pads, per-part tails, and everything up to rows_total
 hipError_t launch_zero_pad_rows(float* x, int nseq, int S, SeqMap sm, int H, int rows_total, hipStream_t s);
 

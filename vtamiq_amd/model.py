@@ -15,7 +15,7 @@ import math
 import numbers
 import os
 import warnings
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 from torch import nn
@@ -42,6 +42,15 @@ _COUNT = {1: ("a", "tensor"), 2: ("two", "tensors"), 3: ("three", "tensors")}   
 
 def _ptr(t):
     return None if t is None else t.data_ptr()
+
+
+class Rollout(NamedTuple):
+    """What VTAMIQ.forward_rollout returns beside the scores (index 0 = reference image, 1 = distorted image of each pair):
+      rollout         (2, B, S) fp32: attention rollout of the token the score is read from, over the S = T + N tokens of each image
+                      (the T = 1 + num_extra_tokens tokens first, then the N patches in input order); > 0, each row sums to 1
+      last_attention  (2, B, num_heads, S) fp32: the last layer's attention row of that token, per head"""
+    rollout: torch.Tensor
+    last_attention: torch.Tensor
 
 
 class StaleReferenceError(ValueError):
@@ -642,6 +651,42 @@ class VTAMIQ(nn.Module):
                         lib.vtq_set_token_trace(self._engine, None)
             self._launch_checked(device, launch)
         return q, None
+
+    def forward_rollout(self, patches, pos, scales):
+        """forward() plus, in the same call, which patches each score looked at: attention rollout (Abnar & Zuidema) of the token the score
+        is read from (`token_num`), and that token's last-layer attention row per head.  With P_l the (S, S) attention matrices
+        forward_vit(return_attention) reports, A_l = (I + mean over heads of P_l) / 2:
+            rollout[k, b] = e_t^T A_L A_(L-1) ... A_1          last_attention[k, b, hd] = P_L[k, b, hd, t, :]
+        and nothing else (no renormalisation over patches, no discarding of heads).  The engine walks it as a row vector from the last layer
+        to the first on the Q / K planes the forward leaves behind; no (S, S) matrix is stored.  The score still comes from the last layer
+        pruned to its one row; that layer's Q / K rows are projected in addition, for the walk alone.
+          patches, pos, scales  as forward(): (ref, dist) of 5-D patches or pre-embedded (B, N, H) rows; scales (ref, dist) or None
+        Returns (q, Rollout): q (B,) fp32 with the bits of forward(); Rollout.rollout (2, B, S), Rollout.last_attention (2, B, num_heads, S),
+        fp32 on the input device.  A pair's values do not depend on the batch it is in.  The input / range policy ("auto", validate_inputs,
+        check_inputs) is forward()'s: a position outside [0, 1) raises IndexError, an fp16 overflow switches to bf16x3 and repeats the whole call.
+        The call keeps num_layers extra QKV buffers in the engine (rollout_workspace_bytes).  forward_varlen, forward_group,
+        forward_cached and forward_pairwise have no rollout variant."""
+        if self.training:
+            raise NotImplementedError(_TRAIN_MSG)
+        if self._FP8_EXPERIMENT:
+            raise NotImplementedError("forward_rollout is not available for the fp8 experiment's model")
+        if len(patches) != 2:
+            raise ValueError("forward_rollout expects patches = (p_ref, p_dist)")
+        device, B, N, tokens_in, (pr, pd), (qr, qd), (sr, sdist) = self._inputs(tuple(patches), pos, scales)
+        S, nh = N + self.spec.num_tokens, self.spec.num_heads
+        with torch.cuda.device(device):
+            q = torch.empty(B, device=device, dtype=torch.float32)
+            roll = torch.empty(2, B, S, device=device, dtype=torch.float32)
+            last = torch.empty(2, B, nh, S, device=device, dtype=torch.float32)
+            stream = torch.cuda.current_stream(device).cuda_stream
+            self._launch_checked(device, lambda lib: self._check((lib.vtq_forward_rollout_tokens if tokens_in else lib.vtq_forward_rollout)(
+                self._engine, pr.data_ptr(), pd.data_ptr(), qr.data_ptr(), qd.data_ptr(), _ptr(sr), _ptr(sdist), B, N, q.data_ptr(),
+                roll.data_ptr(), last.data_ptr(), stream)))
+        return q, Rollout(roll, last)
+
+    def rollout_workspace_bytes(self, B, N):
+        """Bytes of engine workspace a forward_rollout call of (B pairs, N patches) holds beside workspace_bytes(B, N)."""
+        return int(self._engine_lib().vtq_rollout_workspace_bytes(self._engine, B, N)) if self._engine is not None else 0
 
     def forward_varlen(self, patches, pos, scales, lengths):
         """forward() on B pairs with DIFFERENT patch counts in one launch sequence: pair b has lengths[b] >= 1 patches in both images.
