@@ -21,6 +21,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests import interleave as il
 from tests.gpu_util import FORMATS, elt_dtype, num_code, planes_value, to_planes
 from tests.helpers import gate_error, load_case, split_inputs
 from vtamiq_amd import VTAMIQ, _lib, synth
@@ -299,6 +300,103 @@ def child_threads(rounds=3):
             assert same_bits(q, want[i]), (i, r)
 
 
+# ---- the entries added since: rollout, varlen, group / cached, forward_vit with maps -------------------------------------------------
+# four models, each with its own weight seed, each running a short fixed list of calls of tests/interleave.py's catalogue: the rollout
+# workspace regrows (small, then large), varlen's tables and the group / cached ref_index go through each engine's own vl_tab and pinned
+# image, forward_vit's per-call switches sit in front of a plain forward
+ENTRIES = [["rollout_small", "rollout_large"], ["varlen_small", "varlen_large"], ["group_small", "cached_small"], ["vit_large", "forward_small"]]
+
+
+def entry_models():
+    """One fp16x3 model per list of ENTRIES (weight seeds 90 ..); every input of the lists on the device before anything runs."""
+    for names in ENTRIES:
+        for n in names:
+            il.CATALOGUE[n].inputs()
+    return [il.build_model("fp16x3", wseed=90 + i) for i in range(len(ENTRIES))]
+
+
+def serial_entries(models):
+    """Every model's list on the default stream, one call after the other, cloned -- finite, and different from model to model."""
+    torch.cuda.synchronize()
+    want = []
+    for m, names in zip(models, ENTRIES):
+        outs = []
+        for n in names:
+            outs.append(tuple(t.clone() for t in il.CATALOGUE[n].run(m)))
+            torch.cuda.synchronize()
+        want.append(outs)
+    assert all(bool(torch.isfinite(t).all()) for outs in want for o in outs for t in o)
+    firsts = [outs[-1][0].flatten()[0].item() for outs in want]
+    assert len(set(firsts)) == len(firsts), firsts
+    return want
+
+
+def same_entries(got, want, who):
+    """got: one run of a model's list (a tuple of tensors per call) against the serial run's."""
+    assert len(got) == len(want), who
+    for c, (a, b) in enumerate(zip(got, want)):
+        assert len(a) == len(b), (who, c)
+        for k, (x, y) in enumerate(zip(a, b)):
+            assert il.same_bits(x, y), (who, c, k)
+
+
+def test_new_entries_on_their_own_streams_round_robin():
+    """ENTRIES on 4 streams, 3 rounds enqueued round-robin with no host synchronisation in between, the first round each engine's cold
+    start: every output of every call of every round has the bits of the serial default-stream run."""
+    models = entry_models()
+    streams = [torch.cuda.Stream() for _ in models]
+    torch.cuda.synchronize()
+    rounds = 3
+    got = [[] for _ in models]
+    for _ in range(rounds):
+        for i, (m, names) in enumerate(zip(models, ENTRIES)):
+            with torch.cuda.stream(streams[i]):
+                got[i].append([il.CATALOGUE[n].run(m) for n in names])
+    torch.cuda.synchronize()
+    want = serial_entries(models)
+    for i, runs in enumerate(got):
+        for r, run in enumerate(runs):
+            same_entries(run, want[i], (i, r))
+
+
+def test_new_entries_on_their_own_threads():
+    """child_entries below, in a fresh process."""
+    child("entries", timeout=900)
+
+
+def child_entries(rounds=3):
+    """ENTRIES from 4 Python threads, one model and one stream each, released together by a barrier, as child_threads: each thread's
+    outputs, every round, are its model's serial outputs."""
+    models = entry_models()
+    streams = [torch.cuda.Stream() for _ in models]
+    torch.cuda.synchronize()
+    got, errors = [[] for _ in models], []
+    start = threading.Barrier(len(models))
+
+    def work(i):
+        try:
+            start.wait(timeout=60)
+            with torch.cuda.stream(streams[i]):
+                for _ in range(rounds):
+                    got[i].append([il.CATALOGUE[n].run(models[i]) for n in ENTRIES[i]])
+            streams[i].synchronize()
+        except BaseException as e:                                        # reported by the main thread
+            errors.append((i, repr(e)))
+
+    threads = [threading.Thread(target=work, args=(i,)) for i in range(len(models))]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join(timeout=600)
+    assert not errors and not any(t.is_alive() for t in threads), errors
+    torch.cuda.synchronize()
+    want = serial_entries(models)
+    for i, runs in enumerate(got):
+        assert len(runs) == rounds
+        for r, run in enumerate(runs):
+            same_entries(run, want[i], (i, r))
+
+
 # ---- one engine, several streams, ordered by the caller ---------------------------------------------------------------------------------
 def test_one_engine_alternating_streams_ordered_by_events(busy):
     """One handle is used by one stream at a time, and the caller's events say which: forward on A; B waits for A's event and runs a
@@ -393,7 +491,7 @@ def test_image_pair_pipeline_under_a_side_stream(busy):
 
 def main(argv):
     case, rest = argv[0], argv[1:]
-    {"schedule": child_schedule, "threads": child_threads}[case](*rest)
+    {"schedule": child_schedule, "threads": child_threads, "entries": child_entries}[case](*rest)
     print("child ok")
 
 
