@@ -450,7 +450,9 @@ int  vtq_k_gather_patches(const float* const* levels, const int32_t* hs, const i
 
 /* ---- validation-loop reductions; fp64 like the reference's numpy arrays ------------------------------------ */
 /* average_over_repeats (train.py:398-400): q fp32 [R, N] (repeat-major, as the concatenated passes of do_validation) ->
- * out fp64 [N] = mean over the R repeats, summed in repeat order.  R, N >= 1. */
+ * out fp64 [N] = mean over the R repeats, summed in repeat order from +0 (numpy's axis-0 reduction: a column of -0.0 alone gives +0.0).
+ * Non-finite scores follow IEEE arithmetic as in numpy: a NaN, or +inf and -inf in one column, gives NaN; otherwise an infinity stays.
+ * R, N >= 1. */
 int  vtq_k_repeat_mean(const float* q, double* out, int32_t R, int32_t N, void* stream);
 /* The fit-free part of compute_correlations (utils/misc/correlations.py:21-33) on two fp64 score vectors a, b [N]:
  *   work[0:N], work[N:2N]  = normalize_array(a), normalize_array(b) (image_tools.py:17-21; plain copies when normalize == 0)
@@ -458,7 +460,15 @@ int  vtq_k_repeat_mean(const float* q, double* out, int32_t R, int32_t N, void* 
  *   counts[0] = 2 (concordant - discordant pairs), counts[1] = 2 (pairs tied in a), counts[2] = 2 (pairs tied in b)   (exact)
  *   out[0] = Spearman (Pearson of the ranks), out[1] = Pearson, out[2] = RMSE of the normalised vectors.
  * work: DEVICE fp64 [4N]; counts: DEVICE int64 [3]; out: DEVICE fp64 [3] (exactly; none needs an initial value).  N >= 2.  The host
- * finishes Kendall's tau-b from the counts. */
+ * finishes Kendall's tau-b from the counts.
+ * Degenerate input follows numpy / scipy.stats, never a value that reads as a good model:
+ *   - a NaN anywhere in a or b gives NaN for out[0], out[1] and out[2].  With normalize != 0 the vector's whole normalised copy is NaN
+ *     (ndarray.min / max propagate), with normalize == 0 the NaN element alone; a NaN element has a NaN rank.  The pair kernel counts a NaN
+ *     as tied with everything, so the counts stay finite: the caller reports Kendall as NaN when work[0:2N] holds a NaN.
+ *   - a constant a or b gives NaN for out[0] and out[1] (scipy.stats.pearsonr's constant-input rule, also where the mean of N equal values
+ *     rounds away from that value); out[2] stays finite; counts[1] or counts[2] equals N (N - 1), the "no tau" condition.
+ *   - infinities behave as in numpy: they rank and count like any other value; inf - inf is NaN in the normalised copy (-inf with
+ *     normalize != 0) and in Pearson's centring, so out[1] is NaN and out[2] is inf or NaN. */
 int  vtq_k_rank_metrics(const double* a, const double* b, int32_t N, int32_t normalize, double* work, int64_t* counts, double* out,
                         void* stream);
 

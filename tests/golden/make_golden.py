@@ -340,6 +340,84 @@ def run_validation_metrics():
     np.savez(os.path.join(HERE, "validation_metrics.npz"), **out)
 
 
+EDGE_FIELDS = ["SROCC", "KROCC", "PLCC", "RMSE", "PLCC_NOFIT", "RMSE_NOFIT"]
+
+
+def edge_case_inputs():
+    """name -> (targets, predictions pass-major [reps * n], reps, bs): the degenerate score vectors of validation_metrics_edges.npz.  fp32, as
+    the loop produces them; the two range cases are fp64 (fp32 cannot hold 1 + 5e-7) and go through compute_correlations directly."""
+    rng = np.random.default_rng(4040)
+    n = 40
+    f32 = np.float32
+
+    def targets(m=n):
+        return rng.uniform(0.0, 5.0, m).astype(f32)
+
+    def preds(a):
+        return (0.6 * a + 0.3 * rng.standard_normal(a.size)).astype(f32)
+
+    def put(p, i, v):
+        p = p.copy()
+        p[i] = v
+        return p
+
+    c = {}
+    a = targets(); c["const_pred"] = (a, np.full(n, 2.5, f32), 1, 16)
+    a = targets(); c["const_target"] = (np.full(n, 3.0, f32), preds(a), 1, 16)
+    c["const_both"] = (np.full(n, 3.0, f32), np.full(n, 2.5, f32), 1, 16)
+    a = targets(); c["all_but_one_equal"] = (a, put(np.zeros(n, f32), 17, 1.0), 1, 16)
+    a = targets(); c["range_below_eps"] = (a.astype(np.float64), 1.0 + 5e-7 * rng.uniform(0.0, 1.0, n), 1, n)
+    a = targets(); c["range_above_eps"] = (a.astype(np.float64), 1.0 + 2e-6 * np.linspace(0.0, 1.0, n)[rng.permutation(n)], 1, n)
+    a = targets(); c["nan_first"] = (a, put(preds(a), 0, np.nan), 1, 16)
+    a = targets(); c["nan_last"] = (a, put(preds(a), n - 1, np.nan), 1, 16)
+    a = targets(); c["nan_in_target"] = (put(a, 11, np.nan), preds(a), 1, 16)
+    a = targets(); c["nan_one_repeat"] = (a, put(np.concatenate([preds(a) for _ in range(3)]), 1 * n + 23, np.nan), 3, 16)
+    a = targets(); c["neg_inf"] = (a, put(preds(a), 9, -np.inf), 1, 16)
+    a = targets(); c["pos_inf"] = (a, put(preds(a), 30, np.inf), 1, 16)
+    a = targets(); c["all_nan"] = (a, np.full(n, np.nan, f32), 1, 16)
+    a = np.sort(targets()); c["monotone"] = (a, (0.6 * a + 0.01 * np.arange(n)).astype(f32), 1, 16)
+    a = np.sort(targets()); c["antitone"] = (a, (3.0 - 0.6 * a - 0.01 * np.arange(n)).astype(f32), 1, 16)
+    a = targets()
+    z = preds(a) - f32(1.5)                                                      # sign changes
+    z[[3, 8, 21]] = 0.0
+    z[[5, 13, 34]] = -0.0
+    c["signed_zero"] = (a, z.astype(f32), 1, 16)
+    a = targets(5); c["n5"] = (a, preds(a), 1, 2)
+    return c
+
+
+def run_validation_metrics_edges():
+    """train.py:398-409 + utils/misc/correlations.py:21-52 where a validation set degenerates: constant vectors, NaN, +-inf, ranges around
+    the 1e-6 no-divide branch of normalize_array, +-0.0, exact monotone orders, n = 5.  Written to validation_metrics_edges.npz (NaN and inf
+    fields stored as they come); validation_metrics.npz is not regenerated.  <case>_nonorm_fields: compute_correlations(a, b, normalize=False)."""
+    import warnings
+    _install_train_stubs()
+    import train as ref_train
+    import utils.misc.correlations as ref_corr
+    ref_corr.log_warn = lambda *a, **k: None                                    # "Overflow during logistic fit": expected for the non-finite cases
+    ref_compute_correlations = ref_corr.compute_correlations
+    out = {"field_names": np.array(EDGE_FIELDS)}                                # <case>_fields / <case>_nonorm_fields: [6] in this order
+    for name, (q, flat_p, reps, bs) in edge_case_inputs().items():
+        n = q.size
+        with warnings.catch_warnings(), np.errstate(all="ignore"):
+            warnings.simplefilter("ignore")
+            if q.dtype == np.float64:                                           # the range cases: fp64 vectors, no cat / fp32 path
+                corr = ref_compute_correlations(q.copy(), flat_p.copy())
+            else:
+                ys = [torch.from_numpy(q[i:i + bs].copy()) for _ in range(reps) for i in range(0, n, bs)]
+                yp = [torch.from_numpy(flat_p[r * n + i:r * n + min(i + bs, n)].copy()) for r in range(reps) for i in range(0, n, bs)]
+                corr = ref_train.compute_correlations_cat_flat(ys, yp, reps)
+            if name in ("pos_inf", "nan_first"):
+                raw = ref_compute_correlations(np.array(q, dtype=float), np.array(flat_p, dtype=float), normalize=False)
+                out[name + "_nonorm_fields"] = np.array([raw[k] for k in EDGE_FIELDS], dtype=np.float64)
+            if reps > 1:
+                out[name + "_mean"] = ref_train.average_over_repeats(np.array(flat_p, dtype=float), reps)
+        out[name + "_q"], out[name + "_pred"], out[name + "_reps"], out[name + "_bs"] = q, flat_p, reps, bs
+        out[name + "_fields"] = np.array([corr[k] for k in EDGE_FIELDS], dtype=np.float64)
+        print("validation_metrics_edges", name, {k: float(corr[k]) for k in EDGE_FIELDS})
+    np.savez(os.path.join(HERE, "validation_metrics_edges.npz"), **out)
+
+
 def run_ladder_case(name, vtamiq_kwargs, images, N, wseed, iseed, stress_qk, chunk=8, stress_head=False):
     """SCORES ONLY, at the BASELINE patch count: the reference in fp32 and in float64 on stress_state weights over a distortion
     ladder of images * 8 pairs (synth.make_ladder_inputs) -- the trained-like parity tail pinned by the reference itself at
@@ -456,7 +534,10 @@ def main():
     if len(sys.argv) > 1 and sys.argv[1] == "--long":           # only the N = 5000 cases (added in round 6)
         run_long()
         return
-    if len(sys.argv) > 1 and sys.argv[1] == "--stress":         # only the trained-like-statistics cases (added in round 3)
+    if len(sys.argv) > 1 and sys.argv[1] == "--metrics-edges":  # only the degenerate validation sets (the other fixtures are unchanged)
+        run_validation_metrics_edges()
+        return
+    if len(sys.argv) > 1 and sys.argv[1] == "--stress":       # only the trained-like-statistics cases (added in round 3)
         run_stress()
         return
     run_case("c1_b2_n50", dict(vit_config=dict(variant=B16)), B=2, N=50, wseed=1, iseed=11, trace=True)
@@ -493,6 +574,7 @@ def main():
     run_patches()
     run_patches(P=8, fname="patches_gather_p8.npz", seed=12)
     run_validation_metrics()
+    run_validation_metrics_edges()
 
 
 if __name__ == "__main__":

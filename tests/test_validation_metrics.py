@@ -80,7 +80,7 @@ def test_hip_metrics_large_random_vs_oracle():
     assert abs(got["SROCC"] - scipy.stats.spearmanr(a, b).correlation) <= 1e-12
     assert abs(got["PLCC_NOFIT"] - scipy.stats.pearsonr(a, b)[0]) <= 1e-12
     const = validate.compute_correlations(torch.ones(16).cuda(), torch.arange(16.).cuda())
-    assert np.isnan(const["KROCC"])
+    assert np.isnan(const["KROCC"]) and np.isnan(const["SROCC"]) and np.isnan(const["PLCC_NOFIT"])     # no correlation, not a perfect one
 
 
 @pytest.mark.gpu

@@ -4,6 +4,9 @@
 // pair counts of Kendall's tau-b, Pearson and RMSE -- so a validation pass keeps its scores on the GPU and brings back
 // eight numbers instead of synchronising on q.cpu() after every batch (train.py:617-618).
 // fp64 throughout, like the reference's numpy arrays; the pair counts are exact integers.
+// Non-finite and constant scores follow numpy / scipy.stats, so a collapsed model cannot read as a perfect one: a NaN makes min / max,
+// hence the whole normalised vector, NaN (ndarray.min propagates); a NaN element has a NaN rank; Pearson of a constant vector is NaN
+// (scipy.stats.pearsonr's constant-input rule) and is never clamped into [-1, 1] from NaN; infinities take IEEE arithmetic as in numpy.
 // Bound: the O(N^2) pair kernel is VALU/LDS work on N <= 1e5 scores (1e10 compares ~ 10 ms); nothing here is on the
 // forward's critical path.
 #include "dev_common.h"
@@ -27,12 +30,15 @@ __device__ __forceinline__ double block_sum(double v, double* sh) {      // all 
     __syncthreads();
     return r;
 }
+// ndarray.min / ndarray.max: a NaN operand wins (fmin / fmax would skip it); the same value as fmin / fmax otherwise
+__device__ __forceinline__ double nan_min(double x, double y) { return x != x ? x : (y != y ? y : fmin(x, y)); }
+__device__ __forceinline__ double nan_max(double x, double y) { return x != x ? x : (y != y ? y : fmax(x, y)); }
 __device__ __forceinline__ double block_minmax(double v, double* sh, bool want_max) {
     const int t = threadIdx.x;
     sh[t] = v;
     __syncthreads();
     for (int o = blockDim.x >> 1; o > 0; o >>= 1) {
-        if (t < o) sh[t] = want_max ? fmax(sh[t], sh[t + o]) : fmin(sh[t], sh[t + o]);
+        if (t < o) sh[t] = want_max ? nan_max(sh[t], sh[t + o]) : nan_min(sh[t], sh[t + o]);
         __syncthreads();
     }
     const double r = sh[0];
@@ -40,16 +46,18 @@ __device__ __forceinline__ double block_minmax(double v, double* sh, bool want_m
     return r;
 }
 
-// numpy reduces axis 0 of the (R, N) view row by row: ((x0 + x1) + x2) + ... then one true-divide
+// numpy reduces axis 0 of the (R, N) view row by row from its additive identity: (((+0 + x0) + x1) + x2) + ... then one true-divide
+// (the leading +0 changes one result only: a column of -0.0 alone averages to +0.0, as numpy's does)
 __global__ void repeat_mean_kernel(const float* __restrict__ q, double* __restrict__ out, int R, int N) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= N) return;
-    double s = (double)q[i];
-    for (int r = 1; r < R; ++r) s += (double)q[(int64_t)r * N + i];
+    double s = 0.0;
+    for (int r = 0; r < R; ++r) s += (double)q[(int64_t)r * N + i];
     out[i] = s / (double)R;
 }
 
-// one block: b = a - min(a); if |max(b)| > 1e-6: b /= max(b)   (normalize == 0: plain copy)
+// one block: b = a - min(a); if |max(b)| > 1e-6: b /= max(b)   (normalize == 0: plain copy).  min / max propagate NaN, and |NaN| > 1e-6 is
+// false: one NaN in a leaves b all NaN, undivided, as numpy does
 __global__ void normalize_kernel(const double* __restrict__ a, double* __restrict__ b, int N, int normalize) {
     __shared__ double sh[1024];
     const int t = threadIdx.x;
@@ -58,10 +66,10 @@ __global__ void normalize_kernel(const double* __restrict__ a, double* __restric
         return;
     }
     double mn = INFINITY;
-    for (int i = t; i < N; i += blockDim.x) mn = fmin(mn, a[i]);
+    for (int i = t; i < N; i += blockDim.x) mn = nan_min(mn, a[i]);
     mn = block_minmax(mn, sh, false);
     double mx = -INFINITY;
-    for (int i = t; i < N; i += blockDim.x) { const double v = a[i] - mn; b[i] = v; mx = fmax(mx, v); }
+    for (int i = t; i < N; i += blockDim.x) { const double v = a[i] - mn; b[i] = v; mx = nan_max(mx, v); }
     mx = block_minmax(mx, sh, true);
     if (fabs(mx) > 1e-6)
         for (int i = t; i < N; i += blockDim.x) b[i] = b[i] / mx;
@@ -93,9 +101,9 @@ __global__ __launch_bounds__(kT) void pair_kernel(const double* __restrict__ a, 
         }
         __syncthreads();
     }
-    if (live) {                                              // eq counts include j == i
-        ra[i] = (double)less_a + 0.5 * (double)(eq_a + 1);
-        rb[i] = (double)less_b + 0.5 * (double)(eq_b + 1);
+    if (live) {                                              // eq counts include j == i; a NaN compares as tied with everything: it has no rank
+        ra[i] = ai != ai ? ai : (double)less_a + 0.5 * (double)(eq_a + 1);
+        rb[i] = bi != bi ? bi : (double)less_b + 0.5 * (double)(eq_b + 1);
     }
     red[0][t] = live ? sgn : 0;
     red[1][t] = live ? eq_a - 1 : 0;
@@ -108,13 +116,17 @@ __global__ __launch_bounds__(kT) void pair_kernel(const double* __restrict__ a, 
     if (t < 3) atomicAdd((unsigned long long*)&counts[t], (unsigned long long)red[t][0]);
 }
 
-// one block: Pearson r of (x, y) the scipy.stats.pearsonr way (centre, normalise, dot, clamp) and sqrt(mean((x - y)^2))
+// one block: Pearson r of (x, y) the scipy.stats.pearsonr way (constant input: NaN; centre, normalise, dot, clamp) and sqrt(mean((x - y)^2))
 __global__ void pearson_rmse_kernel(const double* __restrict__ x, const double* __restrict__ y, int N, double* __restrict__ r_out,
                                     double* __restrict__ rmse_out) {
     __shared__ double sh[1024];
     const int t = threadIdx.x;
     double sx = 0, sy = 0;
-    for (int i = t; i < N; i += blockDim.x) { sx += x[i]; sy += y[i]; }
+    const double x0 = x[0], y0 = y[0];
+    int varies = 0;                                          // bit 0: some x[i] != x[0], bit 1: same for y (a NaN differs from everything)
+    for (int i = t; i < N; i += blockDim.x) { sx += x[i]; sy += y[i]; varies |= (x[i] != x0 ? 1 : 0) | (y[i] != y0 ? 2 : 0); }
+    const int x_varies = __syncthreads_or(varies & 1), y_varies = __syncthreads_or(varies & 2);
+    const bool constant = !x_varies || !y_varies;
     const double mx = block_sum(sx, sh) / N, my = block_sum(sy, sh) / N;
     double xx = 0, yy = 0, xy = 0, dd = 0;
     for (int i = t; i < N; i += blockDim.x) {
@@ -124,7 +136,8 @@ __global__ void pearson_rmse_kernel(const double* __restrict__ x, const double* 
     xx = block_sum(xx, sh); yy = block_sum(yy, sh); xy = block_sum(xy, sh); dd = block_sum(dd, sh);
     if (t == 0) {
         double r = xy / (sqrt(xx) * sqrt(yy));
-        r = fmax(fmin(r, 1.0), -1.0);
+        r = r > 1.0 ? 1.0 : (r < -1.0 ? -1.0 : r);           // fmin / fmax would turn a 0 / 0 into a perfect correlation
+        if (constant) r = NAN;                               // the mean of N equal values need not be that value: xx may round to > 0
         if (r_out) *r_out = r;
         if (rmse_out) *rmse_out = sqrt(dd / N);
     }

@@ -84,7 +84,9 @@ def _finish_correlations(host: np.ndarray, n: int) -> dict:
     con_minus_dis, xtie, ytie = (int(round(v)) // 2 for v in host[3:6])
     aa, bb = host[6:6 + n], host[6 + n:6 + 2 * n]
     tot = n * (n - 1) // 2
-    if xtie == tot or ytie == tot:                                    # scipy.stats.kendalltau: a constant input has no tau
+    if np.isnan(aa).any() or np.isnan(bb).any():                      # the pair kernel counts a NaN as tied with everything; scipy: nan
+        kendall = float("nan")
+    elif xtie == tot or ytie == tot:                                  # scipy.stats.kendalltau: a constant input has no tau
         kendall = float("nan")
     else:
         kendall = min(1.0, max(-1.0, con_minus_dis / np.sqrt(tot - xtie) / np.sqrt(tot - ytie)))       # tau-b
@@ -100,6 +102,8 @@ def _finish_correlations(host: np.ndarray, n: int) -> dict:
     xm, ym = aa - aa.mean(), fitted - fitted.mean()
     with np.errstate(divide="ignore", invalid="ignore"):              # a constant input has no correlation: nan, as scipy.stats.pearsonr
         pearson = float(np.clip(np.dot(xm / np.linalg.norm(xm), ym / np.linalg.norm(ym)), -1.0, 1.0))
+    if (aa == aa[0]).all() or (fitted == fitted[0]).all():            # pearsonr's constant-input rule: the mean of n equal values need not
+        pearson = float("nan")                                        # be that value, so xm / ym may be a rounding remainder instead of 0
     rmse = float(np.sqrt(np.mean((aa - fitted) ** 2)))
     return {SROCC_FIELD: spearman, KROCC_FIELD: kendall, PLCC_FIELD: pearson, RMSE_FIELD: rmse,
             PLCC_NOFIT_FIELD: pearson_nofit, RMSE_NOFIT_FIELD: rmse_nofit}
