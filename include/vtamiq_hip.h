@@ -233,6 +233,9 @@ int  vtq_forward_cached(vtq_handle h, const float* ref_rows, int32_t G, const fl
 
 /* Input check.  The reference raises (IndexError / device assert) when a position lies outside [0, 1)
  * (transformer.py:417-421); vtq_forward clamps such an index into the table instead of gathering out of bounds and records it.
+ * Bit 0: a position coordinate with floor(pos * pos_grid) outside [0, pos_grid) or NaN (each coordinate is clamped to cell 0 or
+ * pos_grid - 1 on its own), or a NaN scale id (the reference's clamp(scale, 0, num_scales - 1) keeps a NaN, whose index then raises;
+ * here it takes scale-table row 1).  Every other scale id, +-inf included, is clamped as the reference clamps it and is no error.
  * Bit 1: the CLS difference of some pair was not finite -- an operand left its format's range upstream (the fp16 operand modes
  * carry |v| <= 65504; VTQ_PREC_BF16X3 has the fp32 range), or the inputs / weights held inf / NaN.
  * (Bit 2 is raised by the fp8 experiment only: include/vtamiq_hip_fp8.h.)
@@ -276,8 +279,8 @@ int  vtq_debug_gemm_diag(void* buf, int32_t shadow);
  * computes the same arithmetic in the same order per query row: outputs are bit-identical. */
 int  vtq_debug_attention_variant(int32_t variant);
 /* Which tile shape vtq_k_gemm and the engine's GEMM launches use (process-wide; tests and measurement): -1 = the library's rule
- * (vtq_k_gemm_tile_rule), 0 = the persistent 256x256 kernel, 1 = 64x64 tiles, 2 = 128x128 tiles (one workgroup per tile,
- * csrc/gemm_st.hip).  Every shape gives every output element the same MFMA sequence and epilogue arithmetic: outputs are bit-identical. */
+ * (vtq_k_gemm_tile_rule), 0 = the persistent 256x256 kernel; one workgroup per tile (csrc/gemm_st.hip): 1 = 64x64 tiles with an operand
+ * ring of 3, 2 = 64x64 tiles with a ring of 2 (two workgroups per CU), 3 = 128x128 tiles.  Every shape gives every output element the same MFMA sequence and epilogue arithmetic: outputs are bit-identical. */
 int  vtq_debug_gemm_variant(int32_t variant);
 /* Host-only: the tile shape the library's rule gives an (M, N, K) launch in operand format num (VTQ_NUM_*); -1 = bad format code. */
 int  vtq_k_gemm_tile_rule(int32_t M, int32_t N, int32_t K, int32_t num);

@@ -91,12 +91,15 @@ class StageLog:
 
 class StageProbe:
     """The product library's workspace after a given encoder stage.  `args` = the model's forward arguments (kept: every grab
-    re-runs the same forward -- forwards are bit-deterministic, so the stage outputs of separate grabs belong to one computation)."""
+    re-runs the same forward -- forwards are bit-deterministic, so the stage outputs of separate grabs belong to one computation).
+    `call` (tests/test_gpu_embed.py): a callable that makes another entry call on `model` instead of model(*args); B, N, nimg then only
+    say how many rows the call packs (nimg * B sequences of N + T rows)."""
 
-    def __init__(self, model, args, B: int, N: int, nimg: int = 2):
+    def __init__(self, model, args, B: int, N: int, nimg: int = 2, call=None):
         if model.precision not in ACT_PLANES:
             raise ValueError(f"StageProbe needs an explicit precision (one of {sorted(ACT_PLANES)}), not {model.precision!r}")
         self.m, self.args, self.spec = model, args, model.spec
+        self.call = call if call is not None else (lambda: model(*args))
         self.mode = model.precision
         self.H, self.Md = self.spec.hidden_size, self.spec.mlp_dim
         self.W = max(3 * self.H, self.Md)                            # `big` row width (DESIGN.md section 3)
@@ -107,7 +110,7 @@ class StageProbe:
         self.dtype = torch.float16 if self.mode.startswith("fp16") else torch.bfloat16
         self.lib, self.hip = _lib.load(), C.CDLL("libamdhip64.so")
         with torch.no_grad():
-            model(*args)                                             # creates the engine and its workspace
+            self.call()                                              # creates the engine and its workspace
         torch.cuda.synchronize()
 
     def _copy(self, ptr: int, nbytes: int) -> torch.Tensor:
@@ -126,7 +129,7 @@ class StageProbe:
         try:
             _lib.check(self.lib.vtq_debug_stop_after(m._engine, stop))
             with torch.no_grad():
-                m(*self.args)                                        # (the head still runs, on stale rows: its scores are ignored)
+                self.call()                                          # (the head still runs, on stale rows: its scores are ignored)
             torch.cuda.synchronize()
         finally:
             _lib.check(self.lib.vtq_debug_stop_after(m._engine, -1))

@@ -120,7 +120,10 @@ __global__ __launch_bounds__(256) void pack_patches_kernel(ImgPtrs src, int nimg
 // ScaleEmbedding.forward index (transformer.py:396-398): clamp(scale, 0, num_scales-1) + 1.
 // The reference indexes its table with whatever comes out (transformer.py:417-421) and raises IndexError / a device assert for
 // pos outside [0, 1); here an out-of-range index (pos < 0, pos >= 1, NaN) is clamped into the table and reported through
-// *err (bit 0), which vtq_input_errors() reads back: never an out-of-bounds gather.
+// *err (bit 0), which vtq_input_errors() reads back: never an out-of-bounds gather.  Each coordinate is clamped on its own:
+// floor(pos * G) < 0 or NaN -> cell 0, >= G -> cell G - 1, the other coordinate keeps its cell.
+// A scale id is clamped by the reference itself, so no finite or infinite value is an error; a NaN scale id survives the
+// reference's clamp, becomes INT64_MIN as an index and raises there: here it takes table row 1 and is reported through bit 0 too.
 __global__ void embed_index_kernel(ImgPtrs pos, ImgPtrs sc, int nimg, int* __restrict__ pidx, int* __restrict__ sidx,
                                    int* __restrict__ row_map, int B0, int B, int N, int rows_pad, SeqMap sm, int T, int grid, int num_scales,
                                    int* __restrict__ err, const int* __restrict__ vl_prefix, const int* __restrict__ vl_row0) {
@@ -145,6 +148,7 @@ __global__ void embed_index_kernel(ImgPtrs pos, ImgPtrs sc, int nimg, int* __res
     if (sc.p[0]) {
         const float* sb = img == 0 ? sc.p[0] : (img == 1 ? sc.p[1] : sc.p[2]);
         float sv = sb[rr];
+        if (sv != sv) atomicOr(err, 1);                   // NaN: fmaxf(NaN, 0) = 0 below, table row 1
         sv = fminf(fmaxf(sv, 0.0f), (float)(num_scales - 1)) + 1.0f;
         si = (int)sv;
     }

@@ -26,7 +26,7 @@ from .spec import ModelSpec, make_spec
 _PRECISIONS = _lib.PRECISIONS
 # "auto" (the default of the drop-in model): run the parity mode fp16x3, read the engine's error word after every forward (one
 # 4-byte D2H + stream sync: the caller's q.cpu() / loss pays the same sync a moment later) and
-#   * raise IndexError for a position outside [0, 1), as the reference's table lookup does (transformer.py:417-421);
+#   * raise IndexError for a position outside [0, 1) or a NaN scale id, as the reference's table lookups do (transformer.py:417-421, 396-400);
 #   * when an operand left the fp16 range (|v| > 65504: non-finite CLS difference) switch THIS model to "bf16x3" (fp32 range,
 #     same 3-MFMA split) with a warning and re-run the call -- the fp32 reference returns finite scores there (train.py:602-607),
 #     so must a drop-in.  The switch is sticky: the overflow comes from the checkpoint's activation scale.
@@ -36,7 +36,8 @@ AUTO_FIRST, AUTO_FALLBACK = "fp16x3", "bf16x3"
 
 _TRAIN_MSG = ("the MI355X engine implements the eval/no-grad forward only (Dropout/DropPath of vtamiq.py:72-75 and "
               "channel_attention.py:26-29 are train-time stochastic; backward is out of scope): call model.eval()")
-_POS_RANGE_MSG = "pos outside [0, 1): index out of range in the positional-embedding table (transformer.py:417-421)"
+_POS_RANGE_MSG = ("pos outside [0, 1) or a NaN scale id: index out of range in the positional- / scale-embedding table "
+                  "(transformer.py:417-421, 396-400)")
 _COUNT = {1: ("a", "tensor"), 2: ("two", "tensors"), 3: ("three", "tensors")}      # images per item, as the shape errors word it
 
 
@@ -425,7 +426,7 @@ class VTAMIQ(nn.Module):
         self._forget_packed_weights()
 
     def check_inputs(self):
-        """Synchronise and raise IndexError if any forward since the last check saw a position outside [0, 1), FloatingPointError
+        """Synchronise and raise IndexError if any forward since the last check saw a position outside [0, 1) or a NaN scale id, FloatingPointError
         if one produced a non-finite CLS difference (operand range overflow, fp16 modes)."""
         if self._engine is None:
             return
