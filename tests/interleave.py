@@ -1,8 +1,8 @@
 """Every public forward entry as a named call, a plan that runs them in every order, and the comparison with a fresh engine.
 
 The engine (vtamiq_amd/csrc/engine.hip) is state shared by all calls on one handle: a workspace that only grows and is zero-filled only
-when it is allocated, a second one for forward_rollout, per-call switches reset by destructors (ro_on, vit_states, trace, iqa_token), one
-device table (vl_tab) used by forward_varlen and by the group / cached entries.  tests/test_gpu_interleave.py and tests/test_gpu_streams.py
+when it is allocated, a second one for forward_rollout, the settings the ABI keeps between calls (trace, iqa_token), one device table
+(vl_tab) used by forward_varlen and by the group / cached entries.  tests/test_gpu_interleave.py and tests/test_gpu_streams.py
 run the calls of this catalogue back to back on one model and compare every output, bit for bit, with the same call on a model that has
 run nothing else (`reference`).  tests/test_interleave_plan.py checks, without a GPU, what those tests rely on: that the plan holds every
 ordered pair of kinds, and that a poisoned carrier call covers the slack rows of every clean call that follows it.
@@ -216,7 +216,7 @@ KINDS = tuple(dict.fromkeys(e.kind for e in _ENTRIES))                      # in
 SMALL = [e.name for e in _ENTRIES if e.size == "small"]                     # one call of every kind
 # part b of tests/test_gpu_interleave.py: every image of a carrier holds one non-finite sample, then every SMALL call runs on that engine
 CARRIERS = ["forward_large", "rollout_large", "varlen_large", "group_large", "vit_large"]
-SLACK_ROWS = 128                                                            # rows behind M_pad that forward_impl / vtq_forward_varlen clear by hand
+SLACK_ROWS = 128                                                            # rows behind M_pad that every forward clears by hand
 
 
 # ---- the plan --------------------------------------------------------------------------------------------------------------------------

@@ -4,21 +4,23 @@ The catalogue of calls, the plan and the comparison are tests/interleave.py.  Ev
 the reference of a call is the same call on a freshly constructed model that runs nothing else.  That each kind is right on its own is
 pinned by its own file (test_gpu_parity, _varlen, _group, _rollout, _forward_vit) and not repeated here.
 
-Which engine member (vtamiq_amd/csrc/engine.hip) or model path (vtamiq_amd/model.py) each test is aimed at:
+What of the engine (vtamiq_amd/csrc/engine.hip) or of the model (vtamiq_amd/model.py) each test pins:
   test_any_order                          every ordered pair of kinds, geometries small -> large -> small: stale rows of x / lnbuf / big and of the
-                                          rollout buffers ro_qkv behind a smaller call, ro_on / ro_out, vit_states / vit_probs / vit_rows, vl_tab shared
-                                          by varlen's tables and the group / cached ref_index; returned tensors that alias engine memory
+                                          rollout buffers ro_qkv behind a smaller call reach no output; no call writes a rollout, layer states or
+                                          attention maps it was not asked for; vl_tab shared by varlen's tables and the group / cached ref_index;
+                                          returned tensors that alias engine memory
   test_after_a_poisoned_call              stale non-finite rows of x / lnbuf / big and of the ro_qkv buffers behind a smaller call, the error word.
                                           pairwise_small (run first), rollout_small and varlen_small are shaped so that their last 64-key tile reads the
-                                          128 slack rows behind M_pad that forward_impl / vtq_forward_varlen clear by hand.  The test does NOT tell those
+                                          128 slack rows behind M_pad that every forward clears by hand.  The test does NOT tell those
                                           memsets' presence from their absence: with the ro_qkv memset taken out it still passes, because the attention
                                           and rollout-step kernels replace masked scores and zero masked V rows themselves (tests/test_gpu_footprint.py
                                           test_attention pins that for NaN rows).  It pins the outcome -- NaN behind M_pad reaches no output -- not a line
   test_one_poisoned_pair                  masked keys of a NaN neighbour sequence: healthy pairs of the same call keep their bits in every output
-  test_after_a_refused_call               ro_on / ro_out / ro_last left set by a rollout call refused inside forward_impl (Reset's destructor), trace.
+  test_after_a_refused_call               a rollout call refused by the shared path's checks, or behind a trace: the calls behind it never write into
+                                          the refused call's output buffers (the outputs belong to the call, not to the handle), trace.
                                           The varlen refusal is the model's ValueError and never enters the engine; the group refusal is check_group's,
                                           ahead of upload_table: both show that a refusal leaves nothing behind, neither reaches vl_tab / vl_host
-  test_a_vit_call_refused_behind_its_switches   vit_states / vit_probs / vit_rows left set by a vtq_forward_vit refused inside forward_impl
+  test_a_vit_call_refused_behind_its_switches   the same for a vtq_forward_vit call refused by the shared path's checks: its `out` and `states`
   test_after_an_out_of_range_position_under_auto   the error word and _launch_checked behind an IndexError, for rollout, group and varlen
   test_token_num_between_calls            iqa_token set per call by _enqueue; ReferenceFeatures.token
   test_auto_nan_input_*                   _launch_checked's three runs into the same output tensors, the parked fp16x3 engine
@@ -150,8 +152,8 @@ def _untouched(*ts):
 @pytest.mark.parametrize("precision,options", MODES, ids=MODE_IDS)
 def test_after_a_refused_call(precision, options):
     """Calls that include/vtamiq_hip.h says are refused (non-zero, no launch), each between valid calls of other kinds and followed by the
-    small call of every kind.  The rollout refusals happen AFTER the entry has set ro_on / ro_out: a plain forward behind them must
-    leave the refused call's canary-filled output buffers alone."""
+    small call of every kind.  The rollout refusals happen AFTER the entry has taken the call's output pointers: a plain forward behind
+    them must leave the refused call's canary-filled output buffers alone."""
     m = il.build_model(precision, options)
     refs = refs_for(["rollout_large", "varlen_large", "group_large", "forward_large"], precision, options)
     lib = m._engine_lib()
@@ -173,7 +175,7 @@ def test_after_a_refused_call(precision, options):
     q, roll, last = _rollout_buffers()
     rc = lib.vtq_forward_rollout(eng, p[0], p[1], ps[0], None, None, None, 3, 40, q.data_ptr(), roll.data_ptr(), last.data_ptr(), stream())
     assert rc != 0 and b"null tensor" in lib.vtq_last_error()
-    valid("forward_large")                                                  # with ro_on left set it would walk a rollout into `roll`
+    valid("forward_large")                                                  # were the refused call's outputs kept, it would walk a rollout into `roll`
     assert _untouched(q, roll, last)
     check_small_calls(m, precision, options)
     assert _untouched(q, roll, last)
@@ -218,8 +220,8 @@ SCALES_KW["vit_config"]["num_scales"] = 2
 
 @pytest.mark.parametrize("precision,options", MODES, ids=MODE_IDS)
 def test_a_vit_call_refused_behind_its_switches(precision, options):
-    """vtq_forward_vit sets vit_states / vit_probs / vit_rows and is then refused inside the shared forward path.  With the catalogue's
-    model nothing forward_impl refuses gets past vtq_forward_vit's own checks, so this case runs on the same model WITH a scale
+    """vtq_forward_vit takes the call's `out` / `states` pointers and is then refused by the shared forward path's checks.  With the catalogue's
+    model nothing the shared checks refuse gets past vtq_forward_vit's own, so this case runs on the same model WITH a scale
     embedding: a NULL `scales` is refused there ("required when num_scales > 1").  The pair forward behind it must not copy token rows
     into the refused call's states buffer, and it and a rollout, varlen, group and forward_vit call have the fresh engine's bits."""
     def model():
@@ -256,7 +258,7 @@ def test_a_vit_call_refused_behind_its_switches(precision, options):
     states = torch.full((2, 4, il.T, 768), 7.0, device=DEV)                 # room for the 4 sequences of the calls behind the refusal
     rc = lib.vtq_forward_vit(eng, p[0].data_ptr(), 0, ps[0].data_ptr(), None, 2, 40, 0, out.data_ptr(), states.data_ptr(), None, stream())
     assert rc != 0 and b"scale embedding" in lib.vtq_last_error()
-    q = forward(m)                                                          # the pair forward first: forward_vit sets the switches itself
+    q = forward(m)                                                          # the pair forward first: it has no such outputs of its own
     torch.cuda.synchronize()
     assert _untouched(out, states)
     got = (q, *others(m))

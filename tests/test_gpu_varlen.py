@@ -109,6 +109,7 @@ CONFIGS = {
     "scales3": (dict(variant="ViT-B16", num_scales=3), 0, E2E_LENGTHS),
     "full_last_layer": (dict(variant="ViT-B16"), _lib.OPT_FULL_LAST_LAYER, E2E_LENGTHS),
     "vit_l16": (dict(variant="ViT-L16"), 0, [8, 130, 63]),
+    "adapters": (dict(variant="ViT-B16", num_adapters=1), 0, E2E_LENGTHS),
 }
 
 
@@ -176,6 +177,11 @@ def test_scores_have_the_bits_of_the_pair_alone(name, precision):
 
 def test_scores_have_the_bits_of_the_pair_alone_vit_l16():
     _e2e("vit_l16", "fp16x3")
+
+
+def test_scores_have_the_bits_of_the_pair_alone_adapters():
+    """Adapters: the full last layer (no CLS-only tail) and two more GEMMs per residual branch, on rows addressed by the tables."""
+    _e2e("adapters", "fp16x3")
 
 
 # ---- 4: uniform lengths --------------------------------------------------------------------------------------------------

@@ -123,7 +123,7 @@ struct vtq_engine {
     bool fp8 = false;                  // linear layers on e4m3 operands (MX-scaled MFMA, unit block scales): VTQ_PREC_FP8
     float s_patch = kSPatch;           //   activation scales (see kSPatch ...): patches, then per layer {LN1, attention, LN2, GELU}
     std::vector<float> s_ln1, s_att, s_ln2, s_gelu;
-    bool fp8_static = false, fp8_calibrated = false, calibrating = false;
+    bool fp8_static = false, fp8_calibrated = false;
     bool fp8_installed = false;        //   the current scales came from vtq_fp8_set_scales: a weight reload keeps them
     float* amax_slot = nullptr;        //   device word the producers report max |value| into during a calibration forward
     int64_t PDp = 0;                   // patch_dim rounded up to the GEMM's K granule (row pitch of the packed patches / weight)
@@ -158,9 +158,10 @@ struct vtq_engine {
     float *fold_u = nullptr, *fold_part = nullptr;              //   folded attention (cls_tail.hip): W_k^T q per (sequence, head); chunk partials
     void* fold_z = nullptr;                                      //   its output planes (encoder format): [r_alloc][H / 64 * H]
     int64_t fold_z_plane = 0;
-    // vtq_forward_varlen: the per-call tables (sequence row offsets | lengths | patch-row prefix | attention block table), built on the host
-    // in a pinned image of this engine's own and uploaded on the call's stream ahead of the first launch.  vl_uploaded: recorded behind
-    // the upload, waited for before the next call rewrites the image.  Per engine: nothing of this is shared between handles.
+    // One call's device table (upload_table): vtq_forward_varlen's sequence row offsets | lengths | patch-row prefix | attention block
+    // table, or the group entries' ref_index.  Built on the host in a pinned image of this engine's own and uploaded on the call's stream
+    // ahead of the first launch.  vl_uploaded: recorded behind the upload, waited for before the next call rewrites the image.  Per
+    // engine: nothing of this is shared between handles.
     int* vl_tab = nullptr;               //   device (workspace)
     int* vl_host = nullptr;              //   pinned host image
     size_t vl_host_ints = 0;
@@ -171,17 +172,10 @@ struct vtq_engine {
     int* err_flag = nullptr;             // device word (vtq_input_errors): bit 0 = a position outside [0, 1) was clamped, bit 1 = non-finite CLS difference
     std::vector<void*> ws_allocs;
     float* trace = nullptr;
-    // vtq_forward_vit (one call's worth; NULL / 0 otherwise): per-layer residual rows (vit_rows per sequence) and attention probabilities
-    float* vit_states = nullptr;
-    float* vit_probs = nullptr;
-    int vit_rows = 0;
-    // vtq_forward_rollout: the caller's outputs (one call's worth; NULL otherwise) and the workspace only such a call reserves: one QKV
-    // buffer per layer, in which its Q / K planes survive the forward, the row vector (ping-pong), the step's partials
-    float* ro_out = nullptr;
-    float* ro_last = nullptr;
-    bool ro_on = false;
+    // vtq_forward_rollout: the workspace only such a call reserves (rollout_workspace): one QKV buffer per layer, in which its Q / K planes
+    // survive the forward, the row vector (ping-pong), the step's partials
     int ro_capB = 0, ro_capN = 0;
-    std::vector<void*> ro_qkv;
+    std::vector<void*> ro_qkv;                  // one slot per layer (vtq_create)
     int64_t ro_plane = 0;
     float *ro_r[2] = {nullptr, nullptr}, *ro_part = nullptr;
     std::vector<void*> ro_allocs;
@@ -195,9 +189,9 @@ struct vtq_engine {
 
 namespace {
 
-int dev_alloc(vtq_engine* e, void** p, size_t bytes, bool ws = false) {
+int dev_alloc(vtq_engine* e, void** p, size_t bytes) {
     HIP_TRY(hipMalloc(p, bytes ? bytes : 16));
-    (ws ? e->ws_allocs : e->allocs).push_back(*p);
+    e->allocs.push_back(*p);
     return 0;
 }
 
@@ -368,14 +362,29 @@ Geometry geometry_seq(const vtq_engine* e, int nseq, int N) {
     g.P_pad = round_up((int64_t)nseq * N, 256);
     // +128: attention over-read slack behind the last sequence.  vtq_k_attention's contract (include/vtamiq_hip.h) is ceil128(S_pad) - S_pad
     // <= 127 rows behind row nseq * S_pad <= M_pad, pinned by tests/test_gpu_footprint.py test_attention with exactly that many rows; 128 is
-    // that bound rounded to the GEMM half tile, and the length of the memset in forward_impl
+    // that bound rounded to the GEMM half tile, and the length of the memset in forward()
     g.rows_alloc = (g.M_pad > g.P_pad ? g.M_pad : g.P_pad) + 128;
     g.R_pad = round_up(g.nseq, 64);
     g.sm = SeqMap{g.S_pad, g.nseq, (int)(g.M_pad - (int64_t)g.nseq * g.S_pad)};
     return g;
 }
-// nimg images per item: 1 = single images (vtq_forward_vit), 2 = (ref, dist) FR pair, 3 = (ref, dist1, dist2) pairwise triplet
-Geometry geometry(const vtq_engine* e, int B, int N, int nimg = 2) { return geometry_seq(e, nimg * B, N); }
+// the capacity form: B sequence pairs of N patches
+Geometry geometry(const vtq_engine* e, int B, int N) { return geometry_seq(e, 2 * B, N); }
+// vtq_forward_varlen: B pairs of sumN patches in all, at most maxN in one.  Sequences packed back to back at their own length, so the
+// row counts come from the sum; S is the largest sequence (the chunk pitch of the CLS fold's partials), and the map describes the whole
+// batch as ONE run of rows, which is what the pad-row clear needs to know -- every other kernel addresses by the call's tables (VarLen)
+Geometry geometry_varlen(const vtq_engine* e, int B, int64_t sumN, int maxN) {
+    const int64_t rows = 2 * (sumN + (int64_t)B * e->T);
+    Geometry g;
+    g.S = g.S_pad = maxN + e->T;
+    g.nseq = 2 * B;
+    g.M_pad = round_up(rows, 256);
+    g.P_pad = round_up(2 * sumN, 256);
+    g.rows_alloc = (g.M_pad > g.P_pad ? g.M_pad : g.P_pad) + 128;
+    g.R_pad = round_up(g.nseq, 64);
+    g.sm = SeqMap{(int)rows, 1, (int)(g.M_pad - rows)};
+    return g;
+}
 
 // ints of vtq_forward_varlen's device tables for nseq sequences of at most S rows: row offsets [nseq + 1], lengths [nseq], patch prefix
 // [nseq / 2 + 1] (padded to whole int4), then 4 per attention workgroup -- sum_j ceil(S_j / 128) <= nseq * ceil(S / 128) query blocks per head
@@ -420,69 +429,58 @@ std::vector<WsBuf> workspace(vtq_engine* e, int B, int N) {
     return w;
 }
 
-int reserve(vtq_engine* e, int B, int N) {
-    if (B <= e->capB && N <= e->capN && e->x) return 0;
-    const int nB = B > e->capB ? B : e->capB, nN = N > e->capN ? N : e->capN;
+// vtq_forward_rollout's extra workspace (include/vtamiq_hip.h), held beside workspace() and reserved by such a call only: reserve_rollout()
+// allocates it, vtq_rollout_workspace_bytes sums it.  One QKV buffer per layer, zero-filled as `big` is.  The last layer's too: the CLS
+// tail never forms K, and its folded scores (fp32 rows against W_k^T q) are not the ones forward_vit reports -- they differ from them by
+// the operand rounding of the mode, 2e-2 in bf16 on peaked attention -- so a rollout call projects the last layer's Q and K as well
+// (run_encoder), and every layer's row comes from the same step kernel.
+std::vector<WsBuf> rollout_workspace(vtq_engine* e, int B, int N) {
+    const Geometry g = geometry(e, B, N);
+    const int64_t r = (int64_t)g.nseq * g.S;
+    std::vector<WsBuf> w;
+    for (void*& q : e->ro_qkv) w.push_back({&q, &e->ro_plane, g.rows_alloc * 3 * e->H, 2, e->apl, true});
+    w.push_back({(void**)&e->ro_r[0], nullptr, r, 4, 1, false});                              // the row vector (ping-pong)
+    w.push_back({(void**)&e->ro_r[1], nullptr, r, 4, 1, false});
+    w.push_back({(void**)&e->ro_part, nullptr, r * (e->H / 64) * ((g.S + 127) / 128), 4, 1, false});   // the step's partials
+    return w;
+}
+
+size_t ws_bytes(const std::vector<WsBuf>& w) {
+    size_t bytes = 0;
+    for (const WsBuf& b : w) bytes += (size_t)b.elems * b.esz * b.planes;
+    return bytes;
+}
+
+// Grows one of the two workspaces to the largest (B, N) seen: everything of it freed and allocated again.  The capacity is zero while
+// that goes on, so a call behind a failed allocation allocates again.
+int grow(vtq_engine* e, std::vector<WsBuf> (*list)(vtq_engine*, int, int), std::vector<void*>& owned, int& capB, int& capN, int B, int N) {
+    if (B <= capB && N <= capN) return 0;
+    const int nB = B > capB ? B : capB, nN = N > capN ? N : capN;
     HIP_TRY(hipDeviceSynchronize());
-    for (void* p : e->ws_allocs) (void)hipFree(p);
-    e->ws_allocs.clear();
-    e->x = nullptr;
-    for (const WsBuf& b : workspace(e, nB, nN)) {
+    for (void* p : owned) (void)hipFree(p);
+    owned.clear();
+    capB = capN = 0;
+    const std::vector<WsBuf> bufs = list(e, nB, nN);
+    for (const WsBuf& b : bufs) *b.ptr = nullptr;
+    for (const WsBuf& b : bufs) {
         const size_t bytes = (size_t)b.elems * b.esz * b.planes;
-        if (dev_alloc(e, b.ptr, bytes, true)) return 1;
+        HIP_TRY(hipMalloc(b.ptr, bytes ? bytes : 16));
+        owned.push_back(*b.ptr);
         if (b.stride) *b.stride = b.elems;
         if (b.zero) HIP_TRY(hipMemset(*b.ptr, 0, bytes));
     }
     HIP_TRY(hipDeviceSynchronize());
-    e->r_alloc = (int)geometry(e, nB, nN).R_pad;
-    e->capB = nB;
-    e->capN = nN;
+    capB = nB;
+    capN = nN;
     return 0;
 }
 
-// ---- vtq_forward_rollout's extra workspace (include/vtamiq_hip.h): held beside workspace(), reserved by such a call only -------------
-// One QKV buffer per layer.  The last layer's too: the CLS tail never forms K, and its folded scores (fp32 rows against W_k^T q) are not
-// the ones forward_vit reports -- they differ from them by the operand rounding of the mode, 2e-2 in bf16 on peaked attention -- so a
-// rollout call projects the last layer's Q and K as well (run_encoder), and every layer's row comes from the same step kernel.
-struct RolloutWs { int64_t qkv_elems, r_floats, part_floats; };
-RolloutWs rollout_ws(const vtq_engine* e, int B, int N) {
-    const Geometry g = geometry(e, B, N);
-    const int64_t nh = e->H / 64;
-    return RolloutWs{g.rows_alloc * 3 * e->H, (int64_t)g.nseq * g.S, (int64_t)g.nseq * nh * ((g.S + 127) / 128) * g.S};
-}
-size_t rollout_bytes(const vtq_engine* e, int B, int N) {
-    const RolloutWs w = rollout_ws(e, B, N);
-    return (size_t)e->cfg.num_layers * w.qkv_elems * 2 * e->apl + (size_t)(2 * w.r_floats + w.part_floats) * 4;
-}
-
-// grows like reserve(): to the largest (B, N) seen, everything freed and allocated again.  The QKV buffers are zero-filled as `big` is
-int reserve_rollout(vtq_engine* e, int B, int N) {
-    if (B <= e->ro_capB && N <= e->ro_capN && e->ro_part) return 0;
-    const int nB = B > e->ro_capB ? B : e->ro_capB, nN = N > e->ro_capN ? N : e->ro_capN;
-    HIP_TRY(hipDeviceSynchronize());
-    for (void* p : e->ro_allocs) (void)hipFree(p);
-    e->ro_allocs.clear();
-    e->ro_part = nullptr;
-    e->ro_capB = e->ro_capN = 0;
-    const RolloutWs w = rollout_ws(e, nB, nN);
-    auto alloc = [&](void** p, size_t bytes, bool zero) {
-        HIP_TRY(hipMalloc(p, bytes ? bytes : 16));
-        e->ro_allocs.push_back(*p);
-        if (zero) HIP_TRY(hipMemset(*p, 0, bytes));
-        return 0;
-    };
-    e->ro_qkv.assign(e->cfg.num_layers, nullptr);
-    for (void*& q : e->ro_qkv)
-        if (alloc(&q, (size_t)w.qkv_elems * 2 * e->apl, true)) return 1;
-    e->ro_plane = w.qkv_elems;
-    if (alloc((void**)&e->ro_r[0], w.r_floats * 4, false) || alloc((void**)&e->ro_r[1], w.r_floats * 4, false) ||
-        alloc((void**)&e->ro_part, w.part_floats * 4, false))
-        return 1;
-    HIP_TRY(hipDeviceSynchronize());
-    e->ro_capB = nB;
-    e->ro_capN = nN;
+int reserve(vtq_engine* e, int B, int N) {
+    if (grow(e, workspace, e->ws_allocs, e->capB, e->capN, B, N)) return 1;
+    e->r_alloc = (int)geometry(e, e->capB, e->capN).R_pad;
     return 0;
 }
+int reserve_rollout(vtq_engine* e, int B, int N) { return grow(e, rollout_workspace, e->ro_allocs, e->ro_capB, e->ro_capN, B, N); }
 
 struct Prof {
     vtq_engine* e; hipStream_t s; int cls; bool on; hipEvent_t a, b;
@@ -508,12 +506,40 @@ float fp8_pick_scale(float m, float keep) {
     return ldexpf(1.0f, (f <= 0.875f ? 8 : 7) - ex);
 }
 
+// The one-to-many forms of a call (include/vtamiq_hip.h): which sequences it encodes and where the head's reference rows come from.
+//   REF_GROUP   G references + B distorted images in one batch (nimg = 2), distorted image m scored against reference ref_index[m]
+//   REF_ENCODE  B single reference images (nimg = 1): the consumed token's residual row of each goes to the caller's `rows`, no head
+//   REF_CACHED  B single distorted images (nimg = 1) against the caller's G cached `rows`, through ref_index
+enum { REF_PAIRS = 0, REF_GROUP = 1, REF_ENCODE = 2, REF_CACHED = 3 };
+struct RefGroup { int mode; int G; const int32_t* ref_index; float* rows; };
+
+// What is true of ONE call only.  The entry fills it in and forward() passes it down by const reference; nothing of it is kept on the
+// handle, so no call -- refused, failed or finished -- leaves any of it behind for the next one.  (What the ABI makes sticky between
+// calls -- trace, iqa_token, dbg_stop, prof_mask, the fp8 scale state -- and what is a resource stay in vtq_engine.)
+struct Call {
+    const char* who = nullptr;                 // the entry's name
+    int nimg = 2;                              // images per item: 1 = single images, 2 = (ref, dist), 3 = (ref, dist1, dist2) triplet
+    bool tokens_in = false;                    // `in` holds (B, N, H) feature rows (transformer.py:534-535), not 5-D patches
+    const float *in[3] = {}, *pos[3] = {}, *scales[3] = {};      // per image (the embedding launches read slot 1 with nimg = 1 too: NULL)
+    int B = 0, N = 0;                          // B items of N patches per image, or
+    const int32_t* n_patches = nullptr;        //   vtq_forward_varlen: pair b has n_patches[b]; their sum and maximum
+    int64_t sumN = 0;
+    int maxN = 0;
+    float* q_out = nullptr;
+    // vtq_forward_vit: encoder_norm of `rows` rows per image; per-layer residual rows and attention probabilities (optional)
+    float *out = nullptr, *states = nullptr, *probs = nullptr;
+    int rows = 0;
+    float *rollout_out = nullptr, *last_attention_out = nullptr;   // vtq_forward_rollout ("rollout on" = rollout_out != NULL)
+    RefGroup rg{REF_PAIRS, 0, nullptr, nullptr};
+    bool calibrating = false;                  // fp8 mode: this forward chooses the activation scales (set by forward(), see kSPatch)
+};
+
 // One fp8 producer stage (a kernel that writes e4m3 activation bytes with scale `sc`).  Normal forwards: run it once, saturation
 // reported into the error word.  Calibration forward: run it reporting max |value|, read that (the one place a forward
 // synchronises), choose `sc`, run it again with the final scale.  launch(scale, obs) must be idempotent.
 template <typename F>
-int fp8_stage(vtq_engine* e, hipStream_t s, float& sc, F launch) {
-    if (!e->calibrating) return launch(sc, Fp8Obs{nullptr, e->err_flag});
+int fp8_stage(vtq_engine* e, const Call& c, hipStream_t s, float& sc, F launch) {
+    if (!c.calibrating) return launch(sc, Fp8Obs{nullptr, e->err_flag});
     HIP_TRY(hipMemsetAsync(e->amax_slot, 0, 4, s));
     if (launch(sc, Fp8Obs{e->amax_slot, nullptr})) return 1;
     float m = 0.f;
@@ -523,9 +549,9 @@ int fp8_stage(vtq_engine* e, hipStream_t s, float& sc, F launch) {
     return launch(sc, Fp8Obs{nullptr, e->err_flag});
 }
 
-// One call's host-built table of `ints` ints -> e->vl_tab, as vtq_forward_varlen uploads its own: through the engine's pinned image, ONE
-// copy on `s` ahead of the first launch that reads it, recorded in vl_uploaded, which the next call waits for before it rewrites the image.
-// fill(image) writes the ints.  The workspace must be reserved first (the table lives in it).
+// One call's host-built table of `ints` ints -> e->vl_tab: through the engine's pinned image, ONE copy on `s` ahead of the first launch
+// that reads it, recorded in vl_uploaded, which the next call waits for before it rewrites the image.  fill(image) writes the ints.
+// The workspace must be reserved first (the table lives in it).
 template <typename F>
 int upload_table(vtq_engine* e, const char* who, size_t ints, hipStream_t s, F fill) {
     if ((int64_t)ints > varlen_table_ints(e->capB * 2, e->capN + e->T, e->H)) return fail("%s: table of %zu ints exceeds the reserved workspace", who, ints);
@@ -543,18 +569,12 @@ int upload_table(vtq_engine* e, const char* who, size_t ints, hipStream_t s, F f
     return 0;
 }
 
-// The one-to-many forms of forward_impl (include/vtamiq_hip.h): which sequences a call encodes and where the head's reference rows come from.
-//   REF_GROUP   G references + B distorted images in one batch (nimg = 2), distorted image m scored against reference ref_index[m]
-//   REF_ENCODE  B single reference images (nimg = 1): the consumed token's residual row of each goes to the caller's `rows`, no head
-//   REF_CACHED  B single distorted images (nimg = 1) against the caller's G cached `rows`, through ref_index
-enum { REF_PAIRS = 0, REF_GROUP = 1, REF_ENCODE = 2, REF_CACHED = 3 };
-struct RefGroup { int mode; int G; const int32_t* ref_index; float* rows; const char* who; };
-
-// One vtq_forward_varlen call's device tables (in e->vl_tab): sequence j is the len[j] rows from row0[j]; `blocks`: attention_varlen.hip
+// One vtq_forward_varlen call's device tables (in e->vl_tab): sequence j is the len[j] rows from row0[j], pair b's patches the rows from
+// prefix[b] of each image; `blocks`: attention_varlen.hip.  All NULL / 0: a uniform call, addressed by its Geometry alone
 struct VarLen { const int* row0; const int* len; const int* prefix; const int* blocks; int nblocks; };
 
-// All encoder layers for the g.nseq sequences, enqueued on s.  vl != NULL: sequences of different lengths (g.S = the largest)
-int run_encoder(vtq_engine* e, const Geometry& g, hipStream_t s, bool prune, const VarLen* vl = nullptr) {
+// All encoder layers for the g.nseq sequences, enqueued on s.  vl.row0 != NULL: sequences of different lengths (g.S = the largest)
+int run_encoder(vtq_engine* e, const Call& call, const Geometry& g, hipStream_t s, bool prune, const VarLen& vl) {
     const vtq_config& c = e->cfg;
     const int H = e->H, Md = e->Mdim, T = e->T, L = c.num_layers, f16 = e->f16, apl = e->apl, Hqp = (int)e->Hqp;
     const Num lin = e->lin;
@@ -564,7 +584,8 @@ int run_encoder(vtq_engine* e, const Geometry& g, hipStream_t s, bool prune, con
     auto lnv = [&](int ld) { return View{e->lnbuf, e->ln_plane, ld}; };
     auto bigv = [&](int ld) { return View{e->big, e->big_plane, ld}; };
     // layer i's QKV planes: in `big`, or (vtq_forward_rollout) in a buffer of the layer's own, where Q and K survive the forward
-    auto qkvv = [&](int i) { return (e->ro_on && i < (int)e->ro_qkv.size()) ? View{e->ro_qkv[i], e->ro_plane, 3 * H} : bigv(3 * H); };
+    const bool rollout = call.rollout_out != nullptr;
+    auto qkvv = [&](int i) { return rollout ? View{e->ro_qkv[i], e->ro_plane, 3 * H} : bigv(3 * H); };
     float *xcls = e->xcls, *lncls = e->lncls, *qcls = e->qcls;
     const int64_t trace_stride = (int64_t)g.nseq * T * H;
     // LayerNorm inside the residual GEMMs (gemm_rowln.hip): the out-proj launch also writes LayerNorm 2's planes, the fc2 launch the
@@ -578,7 +599,7 @@ int run_encoder(vtq_engine* e, const Geometry& g, hipStream_t s, bool prune, con
     auto layernorm = [&](const float* w, const float* b, float& sc) -> int {
         Prof p(e, s, VTQ_K_LN);
         if (f8m)
-            return fp8_stage(e, s, sc, [&](float v, Fp8Obs ob) {
+            return fp8_stage(e, call, s, sc, [&](float v, Fp8Obs ob) {
                 HIP_TRY(launch_layernorm(x, w, b, e->lnbuf, e->ln_plane, M, H, 2, 1, s, v, ob));
                 return 0;
             });
@@ -618,9 +639,9 @@ int run_encoder(vtq_engine* e, const Geometry& g, hipStream_t s, bool prune, con
         const Layer& Ly = e->layers[i];
         const bool tail = prune && i == L - 1;
         if (!(fused && i > 0) && !tail && layernorm(Ly.ln1w, Ly.ln1b, e->s_ln1[i])) return 1;
-        if (tail && e->ro_on) {
+        if (tail && rollout) {
             // vtq_forward_rollout: the rollout needs this layer's Q and K planes of every row, which the tail below never forms (see
-            // RolloutWs).  LayerNorm 1 into lnbuf (free here: the tail reads x) and the query | key rows of the QKV GEMM; x is not touched
+            // rollout_workspace).  LayerNorm 1 into lnbuf (free here: the tail reads x) and the query | key rows of the QKV GEMM; x is not touched
             if (layernorm(Ly.ln1w, Ly.ln1b, e->s_ln1[i])) return 1;
             Prof p(e, s, VTQ_K_QKV);
             HIP_TRY(launch_gemm(gemm_args(lnv(H), lin_rows(Ly.qkv, 0, 2 * H), M, qkvv(i)), lin, EPI_BIAS, s));
@@ -634,7 +655,7 @@ int run_encoder(vtq_engine* e, const Geometry& g, hipStream_t s, bool prune, con
                 // skinny MFMA stages on the R CLS rows (skinny.hip); activations between them as planes in the encoder's format
                 const View tlv{e->tl, e->tl_plane, H}, thv{e->th, e->th_plane, Md};
                 const PlaneOut tl{e->tl, e->tl_plane, H, f16, apl, nullptr};       // every row kernel of the tail writes its consumer's planes
-                HIP_TRY(launch_rows_ln(x + (int64_t)e->iqa_token * H, (int64_t)g.S_pad * H, Ly.ln1w, Ly.ln1b, lncls, xcls, R, H, tl, s, vl ? vl->row0 : nullptr));
+                HIP_TRY(launch_rows_ln(x + (int64_t)e->iqa_token * H, (int64_t)g.S_pad * H, Ly.ln1w, Ly.ln1b, lncls, xcls, R, H, tl, s, vl.row0));
                 {   // query projection: rows 0 .. H-1 of the packed QKV weight
                     SkinnyArgs a = skinny_args(tlv, lin_rows(Ly.qkv, 0, H), R, apl);
                     a.epi = SK_PLAIN; a.y = qcls; a.ldy = H; a.ycols = H;
@@ -644,7 +665,7 @@ int run_encoder(vtq_engine* e, const Geometry& g, hipStream_t s, bool prune, con
                     const Lin wk = lin_rows(Ly.qkv, H, H);
                     const PlaneOut zo{e->fold_z, e->fold_z_plane, (H / 64) * H, f16, apl, nullptr};
                     HIP_TRY(launch_cls_fold(qcls, wk.w, wk.plane, wk.K, f16, e->wpl, x, (int64_t)g.S_pad * H, Ly.ln1w, Ly.ln1b, e->fold_u, e->fold_part,
-                                            R, g.S, H, zo, s, e->att.terms == 3, vl ? VarSeq{vl->row0, vl->len} : VarSeq{nullptr, nullptr}));
+                                            R, g.S, H, zo, s, e->att.terms == 3, VarSeq{vl.row0, vl.len}));
                 }
                 {   // value projection: ctx[64h ..] = W_v,h zbar_h + b_v (rows 2H .. 3H-1), head h reading columns h H .. of its row
                     SkinnyArgs a = skinny_args(View{e->fold_z, e->fold_z_plane, (H / 64) * H}, lin_rows(Ly.qkv, 2 * H, H), R, apl);
@@ -680,12 +701,12 @@ int run_encoder(vtq_engine* e, const Geometry& g, hipStream_t s, bool prune, con
             Prof p(e, s, VTQ_K_ATTN);
             const View qv = qkvv(i);
             if (f8m) {
-                if (fp8_stage(e, s, e->s_att[i], [&](float sc, Fp8Obs ob) { HIP_TRY(launch_attention(e->big, e->big_plane, e->lnbuf, e->ln_plane, g.nseq, g.S, g.S_pad, H, e->att, s, sc, ob, e->att.terms == 3)); return 0; })) return 1;
-            } else if (vl) HIP_TRY(launch_attention_varlen(qv.p, qv.plane, e->lnbuf, e->ln_plane, vl->blocks, vl->nblocks, H, e->att, s, e->att.terms == 3));
+                if (fp8_stage(e, call, s, e->s_att[i], [&](float sc, Fp8Obs ob) { HIP_TRY(launch_attention(e->big, e->big_plane, e->lnbuf, e->ln_plane, g.nseq, g.S, g.S_pad, H, e->att, s, sc, ob, e->att.terms == 3)); return 0; })) return 1;
+            } else if (vl.blocks) HIP_TRY(launch_attention_varlen(qv.p, qv.plane, e->lnbuf, e->ln_plane, vl.blocks, vl.nblocks, H, e->att, s, e->att.terms == 3));
             else HIP_TRY(launch_attention(qv.p, qv.plane, e->lnbuf, e->ln_plane, g.nseq, g.S, g.S_pad, H, e->att, s, 0.0f, Fp8Obs{nullptr, nullptr}, e->att.terms == 3));
             // forward_vit's attention maps: from the same QKV planes, before the out-proj (with adapters it reuses `big`)
-            if (e->vit_probs)
-                HIP_TRY(launch_attention_probs(qv.p, qv.plane, e->vit_probs + (int64_t)i * g.nseq * (H / 64) * g.S * g.S, g.nseq, g.S, g.S_pad, H,
+            if (call.probs)
+                HIP_TRY(launch_attention_probs(qv.p, qv.plane, call.probs + (int64_t)i * g.nseq * (H / 64) * g.S * g.S, g.nseq, g.S, g.S_pad, H,
                                                e->att, s, e->att.terms == 3));
         }
         if (e->dbg_stop == i * 7 + 2) return 0;
@@ -700,7 +721,7 @@ int run_encoder(vtq_engine* e, const Geometry& g, hipStream_t s, bool prune, con
             Prof p(e, s, VTQ_K_FC1);
             const GemmArgs a = gemm_args(lnv(H), Ly.fc1, M, bigv(Md), 1.0f / e->s_ln2[i]);
             if (f8m) {
-                if (fp8_stage(e, s, e->s_gelu[i], [&](float sc, Fp8Obs ob) { GemmArgs b = a; b.out_scale = sc; b.obs = ob; HIP_TRY(launch_gemm(b, lin, EPI_BIAS_GELU, s)); return 0; })) return 1;
+                if (fp8_stage(e, call, s, e->s_gelu[i], [&](float sc, Fp8Obs ob) { GemmArgs b = a; b.out_scale = sc; b.obs = ob; HIP_TRY(launch_gemm(b, lin, EPI_BIAS_GELU, s)); return 0; })) return 1;
             } else HIP_TRY(launch_gemm(a, lin, EPI_BIAS_GELU, s));
         }
         if (e->dbg_stop == i * 7 + 5) return 0;
@@ -713,7 +734,7 @@ int run_encoder(vtq_engine* e, const Geometry& g, hipStream_t s, bool prune, con
         }
         if (e->dbg_stop == i * 7 + 6) return 0;
         if (e->trace) HIP_TRY(launch_copy_tokens(x, e->trace + (i + 1) * trace_stride, g.nseq, g.sm, T, H, s));
-        if (e->vit_states) HIP_TRY(launch_copy_tokens(x, e->vit_states + (int64_t)i * g.nseq * e->vit_rows * H, g.nseq, g.sm, e->vit_rows, H, s));
+        if (call.states) HIP_TRY(launch_copy_tokens(x, call.states + (int64_t)i * g.nseq * call.rows * H, g.nseq, g.sm, call.rows, H, s));
     }
     return 0;
 }
@@ -850,6 +871,7 @@ int vtq_create(const vtq_config* cfg, vtq_handle* out) {
     }
     e->s_ln1.assign(c.num_layers, kSLn); e->s_att.assign(c.num_layers, kSAtt); e->s_ln2.assign(c.num_layers, kSLn); e->s_gelu.assign(c.num_layers, kSGelu);
     e->fp8_static = (c.options & VTQ_OPT_FP8_STATIC_SCALES) != 0;
+    e->ro_qkv.assign(c.num_layers, nullptr);
     if (hipMalloc((void**)&e->err_flag, 16) != hipSuccess || hipMemset(e->err_flag, 0, 16) != hipSuccess) {
         vtq_destroy(e);
         return fail("vtq_create: device allocation failed");
@@ -920,12 +942,7 @@ int vtq_load_weights(vtq_handle e, const vtq_tensor_desc* descs, int32_t n, void
     return 0;
 }
 
-size_t vtq_workspace_bytes(vtq_handle e, int32_t B, int32_t N) {
-    size_t bytes = 0;
-    if (e)
-        for (const WsBuf& b : workspace(e, B, N)) bytes += (size_t)b.elems * b.esz * b.planes;
-    return bytes;
-}
+size_t vtq_workspace_bytes(vtq_handle e, int32_t B, int32_t N) { return e ? ws_bytes(workspace(e, B, N)) : 0; }
 
 int vtq_reserve(vtq_handle e, int32_t B, int32_t N) {
     if (!e || B < 1 || N < 1) return fail("vtq_reserve: bad argument");
@@ -1039,75 +1056,122 @@ int vtq_profile_collect(vtq_handle e, double* ms_sum, int64_t* launches) {
 // first, every launch on s.  The walk starts at r = e_token, so the first step's per-head sums are the last layer's attention row of the
 // token: last_attention.  The row vector ping-pongs between the two workspace vectors; the LAST step writes the caller's rollout_out itself
 // ([nseq][S] is its layout), so there is no copy.
-static int run_rollout(vtq_engine* e, const Geometry& g, hipStream_t s) {
+static int run_rollout(vtq_engine* e, const Call& c, const Geometry& g, hipStream_t s) {
     const int H = e->H, L = e->cfg.num_layers, t = e->iqa_token;
     const bool ql = e->att.terms == 3;
-    auto dst = [&](int op) { return op == L - 1 ? e->ro_out : e->ro_r[op & 1]; };      // op 0 = the last layer ... op L - 1 = layer 0
+    auto dst = [&](int op) { return op == L - 1 ? c.rollout_out : e->ro_r[op & 1]; };      // op 0 = the last layer ... op L - 1 = layer 0
     for (int op = 0; op < L; ++op)
-        HIP_TRY(launch_rollout_step(e->ro_qkv[L - 1 - op], e->ro_plane, op ? dst(op - 1) : nullptr, t, e->ro_part, dst(op), op ? nullptr : e->ro_last,
-                                    g.nseq, g.S, g.S_pad, H, e->att, s, ql));
+        HIP_TRY(launch_rollout_step(e->ro_qkv[L - 1 - op], e->ro_plane, op ? dst(op - 1) : nullptr, t, e->ro_part, dst(op),
+                                    op ? nullptr : c.last_attention_out, g.nseq, g.S, g.S_pad, H, e->att, s, ql));
     return 0;
 }
 
-// nimg = 2: q_out[B] for (ref, dist); nimg = 3: q_out[2B] = scores of (ref, dist1) then (ref, dist2) with ref encoded once;
-// nimg = 1 (vtq_forward_vit): no head -- vit_out receives encoder_norm of `vit_rows` rows per image (e->vit_states / vit_probs set by the caller)
-// rg (vtq_forward_group / vtq_encode_reference / vtq_forward_cached): image 0 holds rg->G sequences instead of B (REF_GROUP), or the one image
-// is scored against / exported to the caller's rows; the head batch is then B, one score per distorted image
-static int forward_impl(vtq_handle e, int nimg, const float* const* patches, const float* const* pos, const float* const* scales,
-                        int32_t B, int32_t N, float* q_out, void* stream, bool tokens_in = false, float* vit_out = nullptr,
-                        const RefGroup* rg = nullptr) {
-    if (!e) return fail("vtq_forward: null handle");
-    const int mode = rg ? rg->mode : REF_PAIRS;
-    const int B0 = mode == REF_GROUP ? rg->G : B;            // sequences of image 0
+// The last step of a call: the consumed token's rows of the encoded sequences -> what the entry returns.
+//   nimg = 1, REF_PAIRS (vtq_forward_vit): no head -- c.out receives encoder_norm of c.rows rows per image
+//   REF_ENCODE: the rows go to the caller's cache, no head
+//   otherwise: the difference of each pair (nimg = 2: q_out[B]; nimg = 3: q_out[2B] = (ref, dist1) then (ref, dist2) with ref encoded once;
+//   REF_GROUP / REF_CACHED: q_out[B], distorted image m against reference ref_index[m]), the head, and the rollout where asked for
+static int finish(vtq_engine* e, const Call& c, const Geometry& g, hipStream_t s, bool prune, const VarLen& vl) {
+    const int H = e->H, B = c.B, mode = c.rg.mode, ndist = c.nimg - 1;
+    const int B0 = mode == REF_GROUP ? c.rg.G : B, HB = mode == REF_PAIRS ? ndist * B : B;      // sequences of image 0; head batch
+    if (c.nimg == 1 && mode == REF_PAIRS) {               // encoder_norm (transformer.py:376) of the requested rows
+        Prof p(e, s, VTQ_K_LN);
+        HIP_TRY(launch_seq_rows_ln(e->x, e->encw, e->encb, c.out, g.nseq, g.sm, c.rows, H, s, e->err_flag));
+        return 0;
+    }
+    {   // ---- head (vtamiq.py:104-117)
+        Prof p(e, s, VTQ_K_HEAD);
+        float* d = e->hb[0];
+        const PlaneOut hp{e->hp[0], e->hp_plane, H, 1, 2, head_first_slope(e)};      // the first head stage's input planes
+        const float* gamma = e->cfg.diff_scale ? e->diff_gamma : nullptr;
+        // the consumed token's residual row of sequence j: row j of the tail's output, or token row iqa_token of sequence j in x
+        const float* rows = prune ? e->xcls : e->x + (int64_t)e->iqa_token * H;
+        const int64_t stride = prune ? H : (int64_t)g.S_pad * H;
+        if (mode == REF_ENCODE) {
+            HIP_TRY(launch_export_rows(rows, stride, c.rg.rows, B, H, s, e->err_flag));
+            return 0;
+        }
+        if (mode == REF_GROUP) HIP_TRY(launch_group_diff(rows, stride, rows + B0 * stride, stride, e->vl_tab, B, e->encw, e->encb, gamma, d, H, hp, s, e->err_flag));
+        else if (mode == REF_CACHED) HIP_TRY(launch_group_diff(c.rg.rows, H, rows, stride, e->vl_tab, B, e->encw, e->encb, gamma, d, H, hp, s, e->err_flag));
+        else if (prune) HIP_TRY(launch_final_diff(e->xcls, e->encw, e->encb, gamma, d, B, ndist, SeqMap{1, g.nseq, 0}, H, hp, s, e->err_flag));
+        else HIP_TRY(launch_final_diff(e->x + (int64_t)e->iqa_token * H, e->encw, e->encb, gamma, d, B, ndist, g.sm, H, hp, s, e->err_flag, vl.row0));
+        if (run_head(e, d, HB, c.q_out, s, true)) return 1;
+    }
+    if (c.rollout_out && run_rollout(e, c, g, s)) return 1;
+    if (c.calibrating) e->fp8_calibrated = true;
+    return 0;
+}
+
+// THE forward path: every entry checks its own arguments, describes its batch as a Call and ends here.  Each step is stated once; what
+// differs between the entries is read off the Call where it differs.
+//   REF_GROUP: image 0 holds rg.G sequences instead of B;  vtq_forward_varlen (n_patches != NULL): B pairs, each at its own length
+static int forward(vtq_engine* e, Call c, void* stream) {
+    const vtq_config& cfg = e->cfg;
+    const bool varlen = c.n_patches != nullptr, rollout = c.rollout_out != nullptr, tokens_in = c.tokens_in, use_scales = cfg.num_scales > 1;
+    const int nimg = c.nimg, B = c.B, mode = c.rg.mode, H = e->H, T = e->T;
+    const int B0 = mode == REF_GROUP ? c.rg.G : B;           // sequences of image 0
     const int nseq = B0 + (nimg - 1) * B;
-    if (tokens_in && e->fp8) return fail("vtq_forward_tokens: the fp8 experiment has no pre-embedded input path");
-    for (int k = 0; k < nimg; ++k)
-        if (!patches[k] || !pos[k]) return fail("vtq_forward: null tensor");
-    if (!q_out && (nimg > 1 || mode == REF_CACHED)) return fail("vtq_forward: null output");
-    if (B < 1 || N < 1) return fail("vtq_forward: B=%d N=%d", B, N);
-    const vtq_config& c = e->cfg;
-    const bool use_scales = c.num_scales > 1;
-    if (use_scales)
-        for (int k = 0; k < nimg; ++k)
-            if (!scales[k]) return fail("Model uses scale embedding but scales is passed as None.");   // transformer.py:547-548
-    if (all_loaded(e, "vtq_forward")) return 1;
-    if (reserve(e, (nseq + 1) / 2, N)) return 1;           // capacity is kept in units of sequence pairs
-    if (e->ro_on && reserve_rollout(e, (nseq + 1) / 2, N)) return 1;
+    hipStream_t s = (hipStream_t)stream;
+    // ---- workspace: capacity is kept in units of sequence pairs; varlen reserves an upper bound, the batch is no larger than B pairs of maxN
+    if (reserve(e, (nseq + 1) / 2, varlen ? c.maxN : c.N)) return 1;
+    if (rollout && reserve_rollout(e, (nseq + 1) / 2, c.N)) return 1;
     // fp8 mode: the first forward of an engine calibrates the activation scales on its own batch (see kSPatch); it synchronises
     // the stream once per quantisation point and returns this batch's scores computed with the final scales
-    struct CalibGuard { vtq_engine* e; ~CalibGuard() { e->calibrating = false; } } calib_guard{e};
-    if (e->fp8 && !e->fp8_static && !e->fp8_calibrated && e->dbg_stop < 0) e->calibrating = true;
-    const int ndist = nimg - 1, HB = mode == REF_PAIRS ? ndist * B : B;      // head batch
-    hipStream_t s = (hipStream_t)stream;
-    const Geometry g = geometry_seq(e, nseq, N);
-    const int H = e->H, T = e->T;
-    if (mode == REF_GROUP || mode == REF_CACHED)             // ref_index -> the device, ahead of every launch of this call
-        if (upload_table(e, rg->who, (size_t)B, s, [&](int* t) { for (int m = 0; m < B; ++m) t[m] = rg->ref_index[m]; })) return 1;
-    {   // tile schedules of this geometry's GEMM shapes: built and uploaded here (first forward of a shape only), not inside a launch
+    c.calibrating = e->fp8 && !e->fp8_static && !e->fp8_calibrated && e->dbg_stop < 0;
+    const Geometry g = varlen ? geometry_varlen(e, B, c.sumN, c.maxN) : geometry_seq(e, nseq, c.N);
+
+    // ---- the call's device table: host image, then ONE upload on `s` ahead of every launch --------------------------------------
+    VarLen vl{};
+    if (varlen) {
+        const int off_len = nseq + 1, off_pfx = 2 * nseq + 1, off_blk = (int)round_up(3 * nseq + 4, 4);
+        std::vector<int> len(nseq);
+        for (int j = 0; j < nseq; ++j) len[j] = c.n_patches[j % B] + T;
+        const std::vector<int> blocks = attention_varlen_blocks(len.data(), nseq, H);
+        const auto fill = [&](int* t) {
+            int64_t r = 0;
+            for (int j = 0; j < nseq; ++j) { t[j] = (int)r; t[off_len + j] = len[j]; r += len[j]; }
+            t[nseq] = (int)r;
+            int pf = 0;
+            for (int b = 0; b < B; ++b) { t[off_pfx + b] = pf; pf += c.n_patches[b]; }
+            t[off_pfx + B] = pf;
+            for (int k = off_pfx + B + 1; k < off_blk; ++k) t[k] = 0;
+            memcpy(t + off_blk, blocks.data(), blocks.size() * sizeof(int));
+        };
+        if (upload_table(e, c.who, (size_t)off_blk + blocks.size(), s, fill)) return 1;
+        vl = VarLen{e->vl_tab, e->vl_tab + off_len, e->vl_tab + off_pfx, e->vl_tab + off_blk, (int)(blocks.size() / 4)};
+    } else if (mode == REF_GROUP || mode == REF_CACHED) {    // ref_index
+        if (upload_table(e, c.who, (size_t)B, s, [&](int* t) { for (int m = 0; m < B; ++m) t[m] = c.rg.ref_index[m]; })) return 1;
+    }
+    {   // tile schedules of this geometry's GEMM shapes: built and uploaded here (first forward of a tile grid only; DESIGN.md section 4
+        // has what bounds the cache), not inside a launch.  (M, 2H, H) is the rollout's query | key projection of the last layer; the
+        // uniform entries prepare it on every call, varlen -- which has no rollout -- never
         const int wpl = e->wpl, M = (int)g.M_pad;
         HIP_TRY(gemm_prepare((int)g.P_pad, H, (int)e->PDp, wpl, s));
         HIP_TRY(gemm_prepare(M, 3 * H, H, wpl, s));
-        HIP_TRY(gemm_prepare(M, 2 * H, H, wpl, s));
+        if (!varlen) HIP_TRY(gemm_prepare(M, 2 * H, H, wpl, s));
         HIP_TRY(gemm_prepare(M, H, H, wpl, s));
         HIP_TRY(gemm_prepare(M, e->Mdim, H, wpl, s));
         HIP_TRY(gemm_prepare(M, H, e->Mdim, wpl, s));
-        if (c.num_adapters > 0) { HIP_TRY(gemm_prepare(M, (int)e->Hqp, H, wpl, s)); HIP_TRY(gemm_prepare(M, H, (int)e->Hqp, wpl, s)); }
+        if (cfg.num_adapters > 0) { HIP_TRY(gemm_prepare(M, (int)e->Hqp, H, wpl, s)); HIP_TRY(gemm_prepare(M, H, (int)e->Hqp, wpl, s)); }
     }
 
     // ---- embeddings (transformer.py:526-562) -------------------------------------------------------------------
     // 5-D patches: packed to planes here, then one GEMM whose epilogue adds the table rows and scatters into x.  Pre-embedded input
-    // (transformer.py:534-535): `patches` are (B, N, H) feature rows; no patch convolution, a row kernel adds the table rows
+    // (transformer.py:534-535): `in` are (B, N, H) feature rows; no patch convolution, a row kernel adds the table rows.
+    // Patch rows lie (image, item, patch): N1 per image after image 0's R0 -- uniform B * N after B0 * N, varlen the sum of the pairs'
+    // counts with the kernels' defaults for R0 and B0, the sequence map replaced by the tables, the pad rows cleared as the one run of g.sm
     {
+        const int N1 = varlen ? (int)c.sumN : B * c.N, R0 = varlen ? 0 : B0 * c.N;
         Prof p(e, s, VTQ_K_CONVERT);
         if (!tokens_in && e->fp8) {
-            if (fp8_stage(e, s, e->s_patch, [&](float sc, Fp8Obs ob) { HIP_TRY(launch_pack_patches(patches, nimg, e->big, e->big_plane, B * N, c.patch_dim, (int)g.P_pad, 2, 1, s, sc, (int)e->PDp, ob)); return 0; })) return 1;
-        } else if (!tokens_in) HIP_TRY(launch_pack_patches(patches, nimg, e->big, e->big_plane, B * N, c.patch_dim, (int)g.P_pad, e->f16, e->apl, s, 1.0f, (int)e->PDp, Fp8Obs{nullptr, nullptr}, B0 * N));
-        HIP_TRY(launch_embed_index(pos, use_scales ? scales : nullptr, nimg, e->pidx, e->sidx, e->row_map, B, N, (int)g.P_pad, g.sm, T,
-                                   c.pos_grid, c.num_scales, e->err_flag, s, nullptr, nullptr, B0));
-        HIP_TRY(launch_zero_pad_rows(e->x, g.nseq, g.S, g.sm, H, (int)g.rows_alloc, s));
-        HIP_TRY(launch_tokens(e->x, e->cls, e->pos_table, e->extra, g.nseq, g.sm, T, H, s));
+            if (fp8_stage(e, c, s, e->s_patch, [&](float sc, Fp8Obs ob) { HIP_TRY(launch_pack_patches(c.in, nimg, e->big, e->big_plane, N1, cfg.patch_dim, (int)g.P_pad, 2, 1, s, sc, (int)e->PDp, ob)); return 0; })) return 1;
+        } else if (!tokens_in) HIP_TRY(launch_pack_patches(c.in, nimg, e->big, e->big_plane, N1, cfg.patch_dim, (int)g.P_pad, e->f16, e->apl, s, 1.0f, (int)e->PDp, Fp8Obs{nullptr, nullptr}, R0));
+        HIP_TRY(launch_embed_index(c.pos, use_scales ? c.scales : nullptr, nimg, e->pidx, e->sidx, e->row_map, B, varlen ? (int)c.sumN : c.N, (int)g.P_pad, g.sm, T,
+                                   cfg.pos_grid, cfg.num_scales, e->err_flag, s, vl.prefix, vl.row0, varlen ? 0 : B0));
+        HIP_TRY(launch_zero_pad_rows(e->x, g.sm.per, g.sm.pitch, g.sm, H, (int)g.rows_alloc, s));
+        HIP_TRY(launch_tokens(e->x, e->cls, e->pos_table, e->extra, g.nseq, g.sm, T, H, s, vl.row0));
         if (tokens_in)
-            HIP_TRY(launch_embed_rows(patches, nimg, B * N, e->row_map, e->pidx, e->sidx, e->pos_table, use_scales ? e->scale_table : nullptr, e->x, H, s, B0 * N));
+            HIP_TRY(launch_embed_rows(c.in, nimg, N1, e->row_map, e->pidx, e->sidx, e->pos_table, use_scales ? e->scale_table : nullptr, e->x, H, s, R0));
     }
     if (!tokens_in) {
         Prof p(e, s, VTQ_K_PATCH);
@@ -1129,7 +1193,7 @@ static int forward_impl(vtq_handle e, int nimg, const float* const* patches, con
         HIP_TRY(hipMemsetAsync((char*)e->big + ((size_t)pl * e->big_plane + (size_t)g.M_pad * 3 * H) * 2, 0, (size_t)128 * 3 * H * 2, s));
     // (vtq_forward_rollout: the same rows of every retained QKV buffer -- no later stage of this forward writes them, and an earlier,
     // larger call may have)
-    if (e->ro_on)
+    if (rollout)
         for (void* q : e->ro_qkv)
             for (int pl = 0; pl < e->apl; ++pl)
                 HIP_TRY(hipMemsetAsync((char*)q + ((size_t)pl * e->ro_plane + (size_t)g.M_pad * 3 * H) * 2, 0, (size_t)128 * 3 * H * 2, s));
@@ -1139,36 +1203,42 @@ static int forward_impl(vtq_handle e, int nimg, const float* const* patches, con
     // (fp8 mode runs the full last layer: its CLS row then goes through the same e4m3 GEMMs as every other row)
     // (forward_vit needs every row of the last layer: always the full last layer)
     // (vtq_encode_reference / vtq_forward_cached encode single images in the form vtq_forward would pick: their rows meet in one difference)
-    const bool prune = e->cls_prune && !e->trace && !e->fp8 && c.num_adapters == 0 && (nimg > 1 || mode != REF_PAIRS);
-    if (run_encoder(e, g, s, prune)) return 1;
-    if (nimg == 1 && mode == REF_PAIRS) {                 // ---- forward_vit: encoder_norm (transformer.py:376) of the requested rows, no head
-        Prof p(e, s, VTQ_K_LN);
-        HIP_TRY(launch_seq_rows_ln(e->x, e->encw, e->encb, vit_out, g.nseq, g.sm, e->vit_rows, H, s, e->err_flag));
-        return 0;
-    }
+    // (vtq_forward_varlen refuses a trace and the fp8 engine before it gets here: for it this is cls_prune && no adapters)
+    const bool prune = e->cls_prune && !e->trace && !e->fp8 && cfg.num_adapters == 0 && (nimg > 1 || mode != REF_PAIRS);
+    if (run_encoder(e, c, g, s, prune, vl)) return 1;
+    return finish(e, c, g, s, prune, vl);
+}
 
-    // ---- head (vtamiq.py:104-117) ------------------------------------------------------------------------------
-    {
-        Prof p(e, s, VTQ_K_HEAD);
-        float* d = e->hb[0];
-        const PlaneOut hp{e->hp[0], e->hp_plane, H, 1, 2, head_first_slope(e)};      // the first head stage's input planes
-        const float* gamma = c.diff_scale ? e->diff_gamma : nullptr;
-        // the consumed token's residual row of sequence j: row j of the tail's output, or token row iqa_token of sequence j in x
-        const float* rows = prune ? e->xcls : e->x + (int64_t)e->iqa_token * H;
-        const int64_t stride = prune ? H : (int64_t)g.S_pad * H;
-        if (mode == REF_ENCODE) {
-            HIP_TRY(launch_export_rows(rows, stride, rg->rows, B, H, s, e->err_flag));
-            return 0;
-        }
-        if (mode == REF_GROUP) HIP_TRY(launch_group_diff(rows, stride, rows + B0 * stride, stride, e->vl_tab, B, e->encw, e->encb, gamma, d, H, hp, s, e->err_flag));
-        else if (mode == REF_CACHED) HIP_TRY(launch_group_diff(rg->rows, H, rows, stride, e->vl_tab, B, e->encw, e->encb, gamma, d, H, hp, s, e->err_flag));
-        else if (prune) HIP_TRY(launch_final_diff(e->xcls, e->encw, e->encb, gamma, d, B, ndist, SeqMap{1, g.nseq, 0}, H, hp, s, e->err_flag));
-        else HIP_TRY(launch_final_diff(e->x + (int64_t)e->iqa_token * H, e->encw, e->encb, gamma, d, B, ndist, g.sm, H, hp, s, e->err_flag));
-        if (run_head(e, d, HB, q_out, s, true)) return 1;
-    }
-    if (e->ro_on && run_rollout(e, g, s)) return 1;
-    if (e->calibrating) e->fp8_calibrated = true;
-    return 0;
+// The uniform entries (every image B -- image 0 of REF_GROUP: rg.G -- sequences of N patches): the checks they share, behind their own
+static int forward_uniform(vtq_handle e, const Call& c, void* stream) {
+    if (!e) return fail("vtq_forward: null handle");
+    if (c.tokens_in && e->fp8) return fail("vtq_forward_tokens: the fp8 experiment has no pre-embedded input path");
+    for (int k = 0; k < c.nimg; ++k)
+        if (!c.in[k] || !c.pos[k]) return fail("vtq_forward: null tensor");
+    if (!c.q_out && (c.nimg > 1 || c.rg.mode == REF_CACHED)) return fail("vtq_forward: null output");
+    if (c.B < 1 || c.N < 1) return fail("vtq_forward: B=%d N=%d", c.B, c.N);
+    if (e->cfg.num_scales > 1)
+        for (int k = 0; k < c.nimg; ++k)
+            if (!c.scales[k]) return fail("Model uses scale embedding but scales is passed as None.");   // transformer.py:547-548
+    if (all_loaded(e, "vtq_forward")) return 1;
+    return forward(e, c, stream);
+}
+
+// one image per item, the (ref, dist) pair, the (ref, dist1, dist2) triplet as a Call
+static Call call_images(const char* who, bool tokens_in, int nimg, const float* const* in, const float* const* pos, const float* const* scales,
+                        int32_t B, int32_t N, float* q_out) {
+    Call c;
+    c.who = who; c.tokens_in = tokens_in; c.nimg = nimg; c.B = B; c.N = N; c.q_out = q_out;
+    for (int k = 0; k < nimg; ++k) { c.in[k] = in[k]; c.pos[k] = pos[k]; c.scales[k] = scales ? scales[k] : nullptr; }
+    return c;
+}
+static Call call_single(const char* who, int32_t tokens_in, const float* in, const float* pos, const float* scales, int32_t B, int32_t N, float* q_out) {
+    return call_images(who, tokens_in != 0, 1, &in, &pos, &scales, B, N, q_out);
+}
+static Call call_pair(const char* who, bool tokens_in, const float* in_ref, const float* in_dist, const float* pos_ref, const float* pos_dist,
+                      const float* scales_ref, const float* scales_dist, int32_t B, int32_t N, float* q_out) {
+    const float *in[2] = {in_ref, in_dist}, *pos[2] = {pos_ref, pos_dist}, *scales[2] = {scales_ref, scales_dist};
+    return call_images(who, tokens_in, 2, in, pos, scales, B, N, q_out);
 }
 
 #ifdef VTQ_WITH_FP8
@@ -1219,22 +1289,14 @@ int vtq_fp8_reset(vtq_handle e) {
 }
 #endif
 
-static int forward_pair(vtq_handle e, bool tokens_in, const float* in_ref, const float* in_dist, const float* pos_ref, const float* pos_dist,
-                        const float* scales_ref, const float* scales_dist, int32_t B, int32_t N, float* q_out, void* stream) {
-    const float* p[2] = {in_ref, in_dist};
-    const float* ps[2] = {pos_ref, pos_dist};
-    const float* sc[2] = {scales_ref, scales_dist};
-    return forward_impl(e, 2, p, ps, sc, B, N, q_out, stream, tokens_in);
-}
-
 int vtq_forward(vtq_handle e, const float* patches_ref, const float* patches_dist, const float* pos_ref, const float* pos_dist,
                 const float* scales_ref, const float* scales_dist, int32_t B, int32_t N, float* q_out, void* stream) {
-    return forward_pair(e, false, patches_ref, patches_dist, pos_ref, pos_dist, scales_ref, scales_dist, B, N, q_out, stream);
+    return forward_uniform(e, call_pair("vtq_forward", false, patches_ref, patches_dist, pos_ref, pos_dist, scales_ref, scales_dist, B, N, q_out), stream);
 }
 
 int vtq_forward_tokens(vtq_handle e, const float* feats_ref, const float* feats_dist, const float* pos_ref, const float* pos_dist,
                        const float* scales_ref, const float* scales_dist, int32_t B, int32_t N, float* q_out, void* stream) {
-    return forward_pair(e, true, feats_ref, feats_dist, pos_ref, pos_dist, scales_ref, scales_dist, B, N, q_out, stream);
+    return forward_uniform(e, call_pair("vtq_forward_tokens", true, feats_ref, feats_dist, pos_ref, pos_dist, scales_ref, scales_dist, B, N, q_out), stream);
 }
 
 // vtq_forward with the attention rollout of the consumed token (include/vtamiq_hip.h).  What it does not offer is refused before any launch
@@ -1247,11 +1309,10 @@ static int forward_rollout(const char* who, vtq_handle e, bool tokens_in, const 
     if (!rollout_out) return fail("%s: null rollout_out", who);
     if (B < 1 || N < 1 || B > 32767) return fail("%s: B=%d N=%d", who, (int)B, (int)N);
     if (e->dbg_stop >= 0) return fail("%s: vtq_debug_stop_after is set", who);
-    struct Reset { vtq_engine* e; ~Reset() { e->ro_on = false; e->ro_out = nullptr; e->ro_last = nullptr; } } reset{e};
-    e->ro_on = true;
-    e->ro_out = rollout_out;
-    e->ro_last = last_attention_out;
-    return forward_pair(e, tokens_in, in_ref, in_dist, pos_ref, pos_dist, scales_ref, scales_dist, B, N, q_out, stream);
+    Call c = call_pair(who, tokens_in, in_ref, in_dist, pos_ref, pos_dist, scales_ref, scales_dist, B, N, q_out);
+    c.rollout_out = rollout_out;
+    c.last_attention_out = last_attention_out;
+    return forward_uniform(e, c, stream);
 }
 
 int vtq_forward_rollout(vtq_handle e, const float* patches_ref, const float* patches_dist, const float* pos_ref, const float* pos_dist,
@@ -1268,7 +1329,7 @@ int vtq_forward_rollout_tokens(vtq_handle e, const float* feats_ref, const float
                            rollout_out, last_attention_out, stream);
 }
 
-size_t vtq_rollout_workspace_bytes(vtq_handle e, int32_t B, int32_t N) { return (e && B >= 1 && N >= 1) ? rollout_bytes(e, B, N) : 0; }
+size_t vtq_rollout_workspace_bytes(vtq_handle e, int32_t B, int32_t N) { return (e && B >= 1 && N >= 1) ? ws_bytes(rollout_workspace(e, B, N)) : 0; }
 
 // B pairs of different patch counts through one launch sequence (include/vtamiq_hip.h).  Layout: sequences packed back to back at their
 // own length, all reference sequences, then all distorted ones; the packed patch rows likewise (image, pair, patch).  Every kernel is
@@ -1285,115 +1346,24 @@ int vtq_forward_varlen(vtq_handle e, const float* patches_ref, const float* patc
     if (!patches_ref || !patches_dist || !pos_ref || !pos_dist) return fail("vtq_forward_varlen: null tensor");
     if (!q_out) return fail("vtq_forward_varlen: null output");
     if (e->trace) return fail("vtq_forward_varlen: a token trace buffer is set (vtq_set_token_trace): the trace layout is per uniform batch");
-    const vtq_config& c = e->cfg;
-    const int H = e->H, T = e->T, nseq = 2 * B;
-    int64_t sumN = 0;
-    int maxN = 0;
+    Call c = call_pair("vtq_forward_varlen", false, patches_ref, patches_dist, pos_ref, pos_dist, scales_ref, scales_dist, B, 0, q_out);
+    c.n_patches = n_patches;
     for (int b = 0; b < B; ++b) {
-        sumN += n_patches[b];
-        if (n_patches[b] > maxN) maxN = n_patches[b];
+        c.sumN += n_patches[b];
+        if (n_patches[b] > c.maxN) c.maxN = n_patches[b];
     }
-    const int64_t rows = 2 * (sumN + (int64_t)B * T);
-    if (rows + 512 > INT32_MAX / 4 || (int64_t)nseq * (maxN + T) + 512 > INT32_MAX / 4)
+    const int64_t rows = 2 * (c.sumN + (int64_t)B * e->T);
+    if (rows + 512 > INT32_MAX / 4 || (int64_t)2 * B * (c.maxN + e->T) + 512 > INT32_MAX / 4)
         return fail("vtq_forward_varlen: %lld token rows exceed the 32-bit row index of the kernels", (long long)rows);
-    const bool use_scales = c.num_scales > 1;
-    if (use_scales && (!scales_ref || !scales_dist)) return fail("Model uses scale embedding but scales is passed as None.");   // transformer.py:547-548
+    if (e->cfg.num_scales > 1 && (!scales_ref || !scales_dist)) return fail("Model uses scale embedding but scales is passed as None.");   // transformer.py:547-548
     if (all_loaded(e, "vtq_forward_varlen")) return 1;
-    if (reserve(e, B, maxN)) return 1;                      // an upper bound for every buffer: the batch is no larger than B pairs of maxN
-    hipStream_t s = (hipStream_t)stream;
-
-    Geometry g;
-    g.S = g.S_pad = maxN + T;                               // the largest sequence: the chunk pitch of the CLS fold's partials
-    g.nseq = nseq;
-    g.M_pad = round_up(rows, 256);
-    g.P_pad = round_up(2 * sumN, 256);
-    g.rows_alloc = (g.M_pad > g.P_pad ? g.M_pad : g.P_pad) + 128;
-    g.R_pad = round_up(nseq, 64);
-    g.sm = SeqMap{(int)rows, 1, (int)(g.M_pad - rows)};     // the whole batch as ONE run of rows: what the pad-row clear needs to know
-
-    // ---- the call's tables: host image, then ONE upload on `s` ahead of every launch ---------------------------------------------
-    const int off_len = nseq + 1, off_pfx = 2 * nseq + 1, off_blk = (int)round_up(3 * nseq + 4, 4);
-    VarLen vl{};
-    {
-        std::vector<int> len(nseq);
-        for (int j = 0; j < nseq; ++j) len[j] = n_patches[j % B] + T;
-        const std::vector<int> blocks = attention_varlen_blocks(len.data(), nseq, H);
-        const size_t ints = (size_t)off_blk + blocks.size();
-        if ((int64_t)ints > varlen_table_ints(e->capB * 2, e->capN + T, H)) return fail("vtq_forward_varlen: table of %zu ints exceeds the reserved workspace", ints);
-        if (!e->vl_uploaded) HIP_TRY(hipEventCreateWithFlags(&e->vl_uploaded, hipEventDisableTiming));
-        else HIP_TRY(hipEventSynchronize(e->vl_uploaded));  // the previous call's upload has read the image (long done, as a rule)
-        if (e->vl_host_ints < ints) {
-            if (e->vl_host) (void)hipHostFree(e->vl_host);
-            e->vl_host = nullptr; e->vl_host_ints = 0;
-            HIP_TRY(hipHostMalloc((void**)&e->vl_host, ints * sizeof(int), hipHostMallocDefault));
-            e->vl_host_ints = ints;
-        }
-        int* t = e->vl_host;
-        int64_t r = 0;
-        for (int j = 0; j < nseq; ++j) { t[j] = (int)r; t[off_len + j] = len[j]; r += len[j]; }
-        t[nseq] = (int)r;
-        int pf = 0;
-        for (int b = 0; b < B; ++b) { t[off_pfx + b] = pf; pf += n_patches[b]; }
-        t[off_pfx + B] = pf;
-        for (int k = off_pfx + B + 1; k < off_blk; ++k) t[k] = 0;
-        memcpy(t + off_blk, blocks.data(), blocks.size() * sizeof(int));
-        HIP_TRY(hipMemcpyAsync(e->vl_tab, t, ints * sizeof(int), hipMemcpyHostToDevice, s));
-        HIP_TRY(hipEventRecord(e->vl_uploaded, s));
-        vl = VarLen{e->vl_tab, e->vl_tab + off_len, e->vl_tab + off_pfx, e->vl_tab + off_blk, (int)(blocks.size() / 4)};
-    }
-    {   // tile schedules of this batch's GEMM shapes (first forward of a tile grid only; see DESIGN.md section 4 for what bounds the cache)
-        const int wpl = e->wpl, M = (int)g.M_pad;
-        HIP_TRY(gemm_prepare((int)g.P_pad, H, (int)e->PDp, wpl, s));
-        HIP_TRY(gemm_prepare(M, 3 * H, H, wpl, s));
-        HIP_TRY(gemm_prepare(M, H, H, wpl, s));
-        HIP_TRY(gemm_prepare(M, e->Mdim, H, wpl, s));
-        HIP_TRY(gemm_prepare(M, H, e->Mdim, wpl, s));
-        if (c.num_adapters > 0) { HIP_TRY(gemm_prepare(M, (int)e->Hqp, H, wpl, s)); HIP_TRY(gemm_prepare(M, H, (int)e->Hqp, wpl, s)); }
-    }
-
-    // ---- embeddings: vtq_forward's launches, the sequence map replaced by the tables ----------------------------------------------
-    const float* patches[2] = {patches_ref, patches_dist};
-    const float* pos[2] = {pos_ref, pos_dist};
-    const float* scales[2] = {scales_ref, scales_dist};
-    {
-        Prof p(e, s, VTQ_K_CONVERT);
-        HIP_TRY(launch_pack_patches(patches, 2, e->big, e->big_plane, (int)sumN, c.patch_dim, (int)g.P_pad, e->f16, e->apl, s, 1.0f, (int)e->PDp));
-        HIP_TRY(launch_embed_index(pos, use_scales ? scales : nullptr, 2, e->pidx, e->sidx, e->row_map, B, (int)sumN, (int)g.P_pad, g.sm, T,
-                                   c.pos_grid, c.num_scales, e->err_flag, s, vl.prefix, vl.row0));
-        HIP_TRY(launch_zero_pad_rows(e->x, 1, (int)rows, g.sm, H, (int)g.rows_alloc, s));
-        HIP_TRY(launch_tokens(e->x, e->cls, e->pos_table, e->extra, nseq, g.sm, T, H, s, vl.row0));
-    }
-    {
-        Prof p(e, s, VTQ_K_PATCH);
-        GemmArgs a = gemm_args(View{e->big, e->big_plane, (int)e->PDp}, e->patch, (int)g.P_pad, View{}, 1.0f / e->s_patch);
-        a.x = e->x;
-        a.row_map = e->row_map; a.idx1 = e->pidx; a.table1 = e->pos_table;
-        a.idx2 = e->sidx; a.table2 = use_scales ? e->scale_table : nullptr;
-        HIP_TRY(launch_gemm(a, e->lin, EPI_EMBED, s));
-    }
-    // the 128 slack rows of the QKV layout behind M_pad (forward_impl has the reasoning): finite before the first layer reads them
-    for (int pl = 0; pl < e->apl; ++pl)
-        HIP_TRY(hipMemsetAsync((char*)e->big + ((size_t)pl * e->big_plane + (size_t)g.M_pad * 3 * H) * 2, 0, (size_t)128 * 3 * H * 2, s));
-
-    const bool prune = e->cls_prune && c.num_adapters == 0;
-    if (run_encoder(e, g, s, prune, &vl)) return 1;
-    {
-        Prof p(e, s, VTQ_K_HEAD);
-        float* d = e->hb[0];
-        const PlaneOut hp{e->hp[0], e->hp_plane, H, 1, 2, head_first_slope(e)};
-        const float* gamma = c.diff_scale ? e->diff_gamma : nullptr;
-        if (prune) HIP_TRY(launch_final_diff(e->xcls, e->encw, e->encb, gamma, d, B, 1, SeqMap{1, nseq, 0}, H, hp, s, e->err_flag));
-        else HIP_TRY(launch_final_diff(e->x + (int64_t)e->iqa_token * H, e->encw, e->encb, gamma, d, B, 1, g.sm, H, hp, s, e->err_flag, vl.row0));
-        if (run_head(e, d, B, q_out, s, true)) return 1;
-    }
-    return 0;
+    return forward(e, c, stream);
 }
 
 static int forward_triplet(vtq_handle e, const char* who, bool tokens_in, const float* const* in, const float* const* pos,
                            const float* const* scales, int32_t B, int32_t N, float* q_out, void* stream) {
     if (!in || !pos) return fail("%s: null argument", who);
-    const float* sc[3] = {scales ? scales[0] : nullptr, scales ? scales[1] : nullptr, scales ? scales[2] : nullptr};
-    return forward_impl(e, 3, in, pos, sc, B, N, q_out, stream, tokens_in);
+    return forward_uniform(e, call_images(who, tokens_in, 3, in, pos, scales, B, N, q_out), stream);
 }
 
 int vtq_forward_pairwise(vtq_handle e, const float* const* patches, const float* const* pos, const float* const* scales, int32_t B,
@@ -1413,15 +1383,12 @@ int vtq_forward_vit(vtq_handle e, const float* in, int32_t tokens_in, const floa
     if (!in || !pos) return fail("vtq_forward_vit: null input");
     if (!out) return fail("vtq_forward_vit: null output");
     if (B < 1 || N < 1) return fail("vtq_forward_vit: B=%d N=%d", (int)B, (int)N);
-    // two-entry arrays: the embedding launches read the second image's pointer slot (unused with nimg = 1)
-    const float* p[2] = {in, nullptr};
-    const float* ps[2] = {pos, nullptr};
-    const float* sc[2] = {scales, nullptr};
-    struct Reset { vtq_engine* e; ~Reset() { e->vit_states = nullptr; e->vit_probs = nullptr; e->vit_rows = 0; } } reset{e};
-    e->vit_states = states;
-    e->vit_probs = probs;
-    e->vit_rows = all_tokens ? N + e->T : e->T;
-    return forward_impl(e, 1, p, ps, sc, B, N, nullptr, stream, tokens_in != 0, out);
+    Call c = call_single("vtq_forward_vit", tokens_in, in, pos, scales, B, N, nullptr);
+    c.out = out;
+    c.states = states;
+    c.probs = probs;
+    c.rows = all_tokens ? N + e->T : e->T;
+    return forward_uniform(e, c, stream);
 }
 
 // ---- one-to-many scoring: every reference encoded once (include/vtamiq_hip.h) ---------------------------------------------------------
@@ -1448,11 +1415,9 @@ static int forward_group(const char* who, vtq_handle e, bool tokens_in, const fl
     if (check_group(who, G, M, N, ref_index, true) || check_group_handle(who, e)) return 1;
     if (!in_ref || !in_dist || !pos_ref || !pos_dist) return fail("%s: null tensor", who);
     if (!q_out) return fail("%s: null output", who);
-    const float* p[2] = {in_ref, in_dist};
-    const float* ps[2] = {pos_ref, pos_dist};
-    const float* sc[2] = {scales_ref, scales_dist};
-    const RefGroup rg{REF_GROUP, G, ref_index, nullptr, who};
-    return forward_impl(e, 2, p, ps, sc, M, N, q_out, stream, tokens_in, nullptr, &rg);
+    Call c = call_pair(who, tokens_in, in_ref, in_dist, pos_ref, pos_dist, scales_ref, scales_dist, M, N, q_out);
+    c.rg = RefGroup{REF_GROUP, G, ref_index, nullptr};
+    return forward_uniform(e, c, stream);
 }
 
 int vtq_forward_group(vtq_handle e, const float* patches_ref, const float* patches_dist, const float* pos_ref, const float* pos_dist,
@@ -1475,11 +1440,9 @@ int vtq_encode_reference(vtq_handle e, const float* in, int32_t tokens_in, const
     if (check_group(who, G, 1, N, nullptr, false) || check_group_handle(who, e)) return 1;
     if (!in || !pos) return fail("%s: null tensor", who);
     if (!ref_rows) return fail("%s: null output", who);
-    const float* p[2] = {in, nullptr};
-    const float* ps[2] = {pos, nullptr};
-    const float* sc[2] = {scales, nullptr};
-    const RefGroup rg{REF_ENCODE, G, nullptr, ref_rows, who};
-    return forward_impl(e, 1, p, ps, sc, G, N, nullptr, stream, tokens_in != 0, nullptr, &rg);
+    Call c = call_single(who, tokens_in, in, pos, scales, G, N, nullptr);
+    c.rg = RefGroup{REF_ENCODE, G, nullptr, ref_rows};
+    return forward_uniform(e, c, stream);
 }
 
 int vtq_forward_cached(vtq_handle e, const float* ref_rows, int32_t G, const float* in, int32_t tokens_in, const float* pos, const float* scales,
@@ -1488,11 +1451,9 @@ int vtq_forward_cached(vtq_handle e, const float* ref_rows, int32_t G, const flo
     if (check_group(who, G, M, N, ref_index, true) || check_group_handle(who, e)) return 1;
     if (!ref_rows || !in || !pos) return fail("%s: null tensor", who);
     if (!q_out) return fail("%s: null output", who);
-    const float* p[2] = {in, nullptr};
-    const float* ps[2] = {pos, nullptr};
-    const float* sc[2] = {scales, nullptr};
-    const RefGroup rg{REF_CACHED, G, ref_index, const_cast<float*>(ref_rows), who};
-    return forward_impl(e, 1, p, ps, sc, M, N, q_out, stream, tokens_in != 0, nullptr, &rg);
+    Call c = call_single(who, tokens_in, in, pos, scales, M, N, q_out);
+    c.rg = RefGroup{REF_CACHED, G, ref_index, const_cast<float*>(ref_rows)};
+    return forward_uniform(e, c, stream);
 }
 
 int vtq_input_errors(vtq_handle e, int32_t* flags, void* stream) {
@@ -1582,15 +1543,21 @@ int vtq_k_attention(const void* qkv, int64_t plane, void* out, int64_t o_plane, 
     return 0;
 }
 
-int vtq_vl_attention_blocks(int32_t nseq, const int32_t* seq_len, int32_t H, int32_t* out, int32_t cap) {
-    if (nseq < 1 || !seq_len || H < 64 || H % 64) return -1;
+// the attention block table of nseq sequences (4 ints per workgroup), or an empty one for what vtq_vl_attention_blocks answers with -1
+static std::vector<int> vl_blocks_checked(int32_t nseq, const int32_t* seq_len, int32_t H) {
+    if (nseq < 1 || !seq_len || H < 64 || H % 64) return {};
     int64_t rows = 0;
     for (int j = 0; j < nseq; ++j) {
-        if (seq_len[j] < 1) return -1;
+        if (seq_len[j] < 1) return {};
         rows += seq_len[j];
     }
-    if (rows + 512 > INT32_MAX / 4) return -1;
-    const std::vector<int> t = attention_varlen_blocks(seq_len, nseq, H);
+    if (rows + 512 > INT32_MAX / 4) return {};
+    return attention_varlen_blocks(seq_len, nseq, H);
+}
+
+int vtq_vl_attention_blocks(int32_t nseq, const int32_t* seq_len, int32_t H, int32_t* out, int32_t cap) {
+    const std::vector<int> t = vl_blocks_checked(nseq, seq_len, H);
+    if (t.empty()) return -1;
     if (out)
         for (size_t i = 0; i < t.size() && (int64_t)i < (int64_t)cap * 4; ++i) out[i] = t[i];
     return (int)(t.size() / 4);
@@ -1601,10 +1568,10 @@ int vtq_vl_attention(const void* qkv, int64_t plane, void* out, int64_t o_plane,
     const Num nm = num_from_code(num);
     if (!num_valid(nm) || nm.terms == 2 || nm.f16 > 1) return fail("vtq_vl_attention: operand format code %d", num);
     if (!qkv || !out || !seq_len) return fail("vtq_vl_attention: null argument");
-    const int nblocks = vtq_vl_attention_blocks(nseq, seq_len, H, nullptr, 0);
+    const std::vector<int> t = vl_blocks_checked(nseq, seq_len, H);
+    const int nblocks = (int)(t.size() / 4);
     if (nblocks < 1) return fail("vtq_vl_attention: nseq=%d, H=%d or a sequence length < 1", (int)nseq, (int)H);
     hipStream_t s = (hipStream_t)stream;
-    const std::vector<int> t = attention_varlen_blocks(seq_len, nseq, H);
     int* dev = nullptr;
     HIP_TRY(hipMalloc((void**)&dev, t.size() * sizeof(int)));
     hipError_t err = hipMemcpyAsync(dev, t.data(), t.size() * sizeof(int), hipMemcpyHostToDevice, s);
