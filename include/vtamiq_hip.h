@@ -102,7 +102,8 @@ int  vtq_load_weights(vtq_handle h, const vtq_tensor_desc* descs, int32_t n, voi
 /* Bytes of device workspace the handle holds for a (B pairs, N patches) call.  A capacity of (B, N) is an upper bound for EVERY workspace
  * buffer of a vtq_forward_varlen call of at most B pairs with at most N patches each (its token rows, patch rows, per-sequence rows,
  * fold partials and per-call tables are all no larger than those of B uniform pairs of N patches): vtq_reserve(h, B, max n) ahead of
- * such calls means none of them allocates. */
+ * such calls means none of them allocates.  The same holds for vtq_forward_group_varlen, vtq_encode_reference_varlen and
+ * vtq_forward_cached_varlen with B = ceil(sequences / 2) and N = the largest count of any image, the per-call table included. */
 size_t vtq_workspace_bytes(vtq_handle h, int32_t B, int32_t N);
 /* Grows the workspace ahead of time (hipMalloc happens here, or lazily on the first larger vtq_forward). */
 int  vtq_reserve(vtq_handle h, int32_t B, int32_t N);
@@ -124,7 +125,7 @@ int  vtq_forward(vtq_handle h,
  * q_out[b] has the bits vtq_forward gives for pair b alone (B = 1, N = n_patches[b]) on the same handle, in every numerics mode, with the
  * CLS-only last layer and with VTQ_OPT_FULL_LAST_LAYER; with all n_patches equal the call is bit-identical to vtq_forward.  Sequences
  * (n_patches[b] + T token rows) are packed back to back at their own length, all reference sequences, then all distorted ones; the
- * call's tables (row offsets, patch-row prefix, attention block table) are built on the host and uploaded to buffers of THIS handle
+ * call's tables (row offsets, lengths, attention block table) are built on the host and uploaded to buffers of THIS handle
  * on `stream` ahead of the first launch.  Asynchronous on `stream` (a second call waits for the previous call's table upload, not for
  * its kernels); vtq_input_errors bits 0 and 1 as vtq_forward.  Workspace: as vtq_forward(B, max n_patches) -- see vtq_workspace_bytes.
  * Refused with vtq_last_error text and no launch: a NULL handle, tensor, n_patches or q_out; B < 1; an n_patches[b] < 1; the fp8
@@ -154,7 +155,9 @@ int  vtq_forward_tokens(vtq_handle h, const float* feats_ref, const float* feats
  * vtq_workspace_bytes and every other entry are unchanged.  The scores still come from the CLS-only last layer; its Q and K rows are
  * projected in addition, because the probabilities vtq_forward_vit reports are those of the 16-bit Q / K planes, which the tail never forms.
  * Refused with vtq_last_error text and no launch: a NULL handle or rollout_out; B or N < 1; the fp8 experiment's handle; a set token trace
- * buffer (vtq_set_token_trace); a set vtq_debug_stop_after.  The varlen, group, cached and pairwise entries have no rollout form. */
+ * buffer (vtq_set_token_trace); a set vtq_debug_stop_after.  The varlen, group, cached and pairwise entries have no rollout form, and
+ * neither have the variable-length one-to-many entries (vtq_forward_group_varlen ...), which take 5-D patches only: pre-embedded ragged input
+ * and a ragged rollout are not offered. */
 int  vtq_forward_rollout(vtq_handle h, const float* patches_ref, const float* patches_dist, const float* pos_ref, const float* pos_dist,
                          const float* scales_ref, const float* scales_dist, int32_t B, int32_t N, float* q_out, float* rollout_out,
                          float* last_attention_out, void* stream);
@@ -230,6 +233,36 @@ int  vtq_encode_reference(vtq_handle h, const float* in, int32_t tokens_in, cons
  * N need not be the N the references were encoded with: nothing behind the encoder depends on it. */
 int  vtq_forward_cached(vtq_handle h, const float* ref_rows, int32_t G, const float* in, int32_t tokens_in, const float* pos,
                         const float* scales, int32_t M, int32_t N, const int32_t* ref_index, float* q_out, void* stream);
+
+/* ---- one-to-many scoring on images of DIFFERENT patch counts: the entries above with vtq_forward_varlen's layout ----------------------------
+ * Mixed-size full-reference data: a few references with many distorted versions each, patch counts differing between images.  Every image
+ * has its own count >= 1 (HOST arrays, read before the call returns); a distorted image's count need NOT equal its reference's: nothing
+ * behind the encoder depends on it.  Tensors as in vtq_forward_varlen, the images' patches one after the other, 5-D patches only:
+ *   patches_ref : (sum n_ref, 3, P, P) fp32 contiguous      pos_ref  : (sum n_ref, 2)       scales_ref  : (sum n_ref) or NULL, vtq_forward's rule
+ *   patches_dist: (sum n_dist, 3, P, P)                     pos_dist : (sum n_dist, 2)      scales_dist : (sum n_dist) or NULL
+ *   n_ref : HOST int32 [G]    n_dist : HOST int32 [M]    ref_index : HOST int32 [M], entries in [0, G)    q_out : [M] fp32    ref_rows : [G, hidden_size]
+ * Sequences (count + T token rows) are packed back to back at their own length, all G reference sequences, then all M distorted ones.  The
+ * call's table (row offsets, lengths, ref_index, attention block table) is built on the host and uploaded ONCE through the handle's pinned
+ * image on `stream` ahead of the first launch; a second call waits for the previous call's upload, not for its kernels.  Asynchronous on
+ * `stream`.  In every numerics mode, with the CLS-only last layer and with VTQ_OPT_FULL_LAST_LAYER:
+ *   - ref_rows[g] of vtq_encode_reference_varlen has the bits vtq_encode_reference gives reference g alone (G = 1, N = n_patches[g]);
+ *   - q_out[m] of vtq_forward_cached_varlen has the bits vtq_forward_cached gives that image alone (M = 1, N = n_patches[m]) against the same rows;
+ *   - q_out[m] of vtq_forward_group_varlen has the bits of that chain: reference ref_index[m] encoded alone, then distorted image m scored
+ *     alone against it -- where n_ref[ref_index[m]] == n_dist[m], the bits of vtq_forward on the single pair;
+ *   - with all counts equal a call is bit-identical to the uniform entry.
+ * A NaN distorted image makes only its own score NaN, a NaN reference exactly the scores that point at it; vtq_input_errors bits 0 and 1
+ * as vtq_forward.  Workspace: as vtq_forward with ceil((G + M) / 2) pairs (ceil(G / 2), ceil(M / 2) for the single-image entries) of the
+ * largest count -- see vtq_workspace_bytes.
+ * Refused with vtq_last_error text that names the entry and the offending argument, and no launch: a NULL count array, ref_index, handle,
+ * tensor or output; G or M < 1; a count < 1; a ref_index[m] outside [0, G); the fp8 experiment's handle; a set token trace buffer
+ * (vtq_set_token_trace).  The checks of the batch description need no device and come first. */
+int  vtq_forward_group_varlen(vtq_handle h, const float* patches_ref, const float* patches_dist, const float* pos_ref, const float* pos_dist,
+                              const float* scales_ref, const float* scales_dist, int32_t G, int32_t M, const int32_t* n_ref,
+                              const int32_t* n_dist, const int32_t* ref_index, float* q_out, void* stream);
+int  vtq_encode_reference_varlen(vtq_handle h, const float* patches, const float* pos, const float* scales, int32_t G, const int32_t* n_patches,
+                                 float* ref_rows, void* stream);
+int  vtq_forward_cached_varlen(vtq_handle h, const float* ref_rows, int32_t G, const float* patches, const float* pos, const float* scales,
+                               int32_t M, const int32_t* n_patches, const int32_t* ref_index, float* q_out, void* stream);
 
 /* Input check.  The reference raises (IndexError / device assert) when a position lies outside [0, 1)
  * (transformer.py:417-421); vtq_forward clamps such an index into the table instead of gathering out of bounds and records it.

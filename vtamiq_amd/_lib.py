@@ -69,6 +69,12 @@ SIGNATURES = {
     "vtq_encode_reference": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "vtq_forward_cached": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                      C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]),
+    # the same on images of different patch counts: host count arrays in place of N
+    "vtq_forward_group_varlen": (C.c_int, [C.c_void_p] + [C.c_void_p] * 6 + [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                           C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]),
+    "vtq_encode_reference_varlen": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]),
+    "vtq_forward_cached_varlen": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32),
+                                            C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]),
     "vtq_set_token_trace": (C.c_int, [C.c_void_p, C.c_void_p]),
     "vtq_set_iqa_token": (C.c_int, [C.c_void_p, C.c_int32]),
     "vtq_debug_stop_after": (C.c_int, [C.c_void_p, C.c_int32]),

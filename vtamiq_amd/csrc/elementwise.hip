@@ -125,12 +125,11 @@ __global__ __launch_bounds__(256) void pack_patches_kernel(ImgPtrs src, int nimg
 // A scale id is clamped by the reference itself, so no finite or infinite value is an error; a NaN scale id survives the
 // reference's clamp, becomes INT64_MIN as an index and raises there: here it takes table row 1 and is reported through bit 0 too.
 __global__ void embed_index_kernel(ImgPtrs pos, ImgPtrs sc, int nimg, int* __restrict__ pidx, int* __restrict__ sidx,
-                                   int* __restrict__ row_map, int B0, int B, int N, int rows_pad, SeqMap sm, int T, int grid, int num_scales,
-                                   int* __restrict__ err, const int* __restrict__ vl_prefix, const int* __restrict__ vl_row0) {
+                                   int* __restrict__ row_map, int B0, int B, int N, int R0, int BN, int rows_pad, SeqMap sm, int T, int grid,
+                                   int num_scales, int* __restrict__ err, const int* __restrict__ vl_row0) {
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= rows_pad) return;
-    const int BN = vl_prefix ? N : B * N;                 // variable length: N = the patches of one image (all pairs)
-    const int R0 = vl_prefix ? N : B0 * N;                // image 0 holds B0 sequences, every later image B (variable length: B0 = B)
+    // image 0 holds B0 sequences and R0 patch rows, every later image B sequences and BN patch rows (uniform: B0 * N and B * N)
     int img;
     int64_t rr64;
     img_of_row(r, R0, BN, img, rr64);
@@ -153,13 +152,17 @@ __global__ void embed_index_kernel(ImgPtrs pos, ImgPtrs sc, int nimg, int* __res
         si = (int)sv;
     }
     sidx[r] = si;
-    if (vl_prefix) {                                      // the pair whose patches hold row rr: vl_prefix[b] <= rr < vl_prefix[b + 1]
-        int lo = 0, hi = B;
+    if (vl_row0) {
+        // Variable length: item i of this image is sequence base + i, and in front of its patches lie prefix(i) = vl_row0[base + i] -
+        // vl_row0[base] - i * T patches of the image (the rows of the i sequences before it, less their T token rows each).  The item
+        // whose patches hold row rr: prefix(i) <= rr < prefix(i + 1); its patch rr - prefix(i) goes T rows behind the sequence's first
+        const int base = img == 0 ? 0 : B0, n = img == 0 ? B0 : B, first = vl_row0[base];
+        int lo = 0, hi = n;
         while (hi - lo > 1) {
             const int mid = (lo + hi) >> 1;
-            if (vl_prefix[mid] <= rr) lo = mid; else hi = mid;
+            if (vl_row0[base + mid] - first - mid * T <= rr) lo = mid; else hi = mid;
         }
-        row_map[r] = vl_row0[img * B + lo] + T + (rr - vl_prefix[lo]);
+        row_map[r] = first + (lo + 1) * T + rr;
         return;
     }
     const int b = rr / N, n = rr - b * N;
@@ -321,17 +324,21 @@ template <int V4>
 __global__ __launch_bounds__(64) void group_diff_kernel(const float* __restrict__ xr, int64_t r_stride, const float* __restrict__ xd,
                                                         int64_t d_stride, const int* __restrict__ ref_index, const float* __restrict__ w,
                                                         const float* __restrict__ b, const float* __restrict__ gamma, float* __restrict__ d,
-                                                        PlaneOut po, int* __restrict__ err) {
-    const int m = blockIdx.x;
-    diff_rows<V4>(xr + (int64_t)ref_index[m] * r_stride, xd + (int64_t)m * d_stride, w, b, gamma, d, (int64_t)m, po, err, threadIdx.x);
+                                                        PlaneOut po, int* __restrict__ err, const int* __restrict__ r_row0,
+                                                        const int* __restrict__ d_row0) {
+    constexpr int H = 256 * V4;
+    const int m = blockIdx.x, g = ref_index[m];
+    // r_row0 / d_row0 (sequences of different lengths in the residual stream): the row of reference g / distorted image m comes from the table
+    diff_rows<V4>(xr + (r_row0 ? (int64_t)r_row0[g] * H : (int64_t)g * r_stride), xd + (d_row0 ? (int64_t)d_row0[m] * H : (int64_t)m * d_stride), w, b,
+                  gamma, d, (int64_t)m, po, err, threadIdx.x);
 }
 
 // vtq_encode_reference: rows src + r * stride (the consumed token's residual row of each sequence, BEFORE encoder_norm: exactly what the
 // difference kernels read) -> out[r][H], fp32.  A non-finite value raises bit 1 of the error word, as seq_rows_ln_kernel does.
 __global__ __launch_bounds__(256) void export_rows_kernel(const float* __restrict__ src, int64_t stride, float* __restrict__ out, int H4,
-                                                          int* __restrict__ err) {
+                                                          int* __restrict__ err, const int* __restrict__ row0) {
     const int r = blockIdx.x;
-    const float4* s4 = (const float4*)(src + (int64_t)r * stride);
+    const float4* s4 = (const float4*)(src + (row0 ? (int64_t)row0[r] * H4 * 4 : (int64_t)r * stride));      // row0: as group_diff_kernel's tables
     float4* o = (float4*)out + (int64_t)r * H4;
     bool ok = true;
     for (int c = threadIdx.x; c < H4; c += blockDim.x) {
@@ -441,15 +448,16 @@ hipError_t launch_pack_patches(const float* const* imgs, int nimg, void* dst, in
 }
 
 hipError_t launch_embed_index(const float* const* pos, const float* const* sc, int nimg, int* pidx, int* sidx, int* row_map, int B, int N,
-                              int rows_pad, SeqMap sm, int T, int grid, int num_scales, int* err, hipStream_t s, const int* vl_prefix,
-                              const int* vl_row0, int B0) {
-    if ((vl_prefix != nullptr) != (vl_row0 != nullptr)) return hipErrorInvalidValue;
+                              int rows_pad, SeqMap sm, int T, int grid, int num_scales, int* err, hipStream_t s, const int* vl_row0, int B0,
+                              int N0) {
     if (B0 == 0) B0 = B;
-    if (B < 1 || B0 < 1 || N < 1 || (vl_prefix && B0 != B)) return hipErrorInvalidValue;
+    if (N0 == 0) N0 = N;
+    if (B < 1 || B0 < 1 || N < 1 || N0 < 1) return hipErrorInvalidValue;
+    const int R0 = vl_row0 ? N0 : B0 * N, BN = vl_row0 ? N : B * N;
     ImgPtrs pp{{pos[0], pos[1], nimg > 2 ? pos[2] : nullptr}};
     ImgPtrs sp{{sc ? sc[0] : nullptr, sc ? sc[1] : nullptr, (sc && nimg > 2) ? sc[2] : nullptr}};
-    hipLaunchKernelGGL(embed_index_kernel, dim3((rows_pad + 255) / 256), dim3(256), 0, s, pp, sp, nimg, pidx, sidx, row_map, B0, B, N, rows_pad,
-                       sm, T, grid, num_scales, err, vl_prefix, vl_row0);
+    hipLaunchKernelGGL(embed_index_kernel, dim3((rows_pad + 255) / 256), dim3(256), 0, s, pp, sp, nimg, pidx, sidx, row_map, B0, B, N, R0, BN,
+                       rows_pad, sm, T, grid, num_scales, err, vl_row0);
     return hipGetLastError();
 }
 
@@ -505,17 +513,18 @@ hipError_t launch_final_diff(const float* x, const float* ln_w, const float* ln_
 }
 
 hipError_t launch_group_diff(const float* xr, int64_t r_stride, const float* xd, int64_t d_stride, const int* ref_index, int M, const float* ln_w,
-                             const float* ln_b, const float* gamma, float* d, int H, PlaneOut po, hipStream_t s, int* err) {
+                             const float* ln_b, const float* gamma, float* d, int H, PlaneOut po, hipStream_t s, int* err, const int* r_row0,
+                             const int* d_row0) {
     if (M < 1 || !ref_index || r_stride % 4 || d_stride % 4) return hipErrorInvalidValue;
-    if (H == 768) hipLaunchKernelGGL(group_diff_kernel<3>, dim3(M), dim3(64), 0, s, xr, r_stride, xd, d_stride, ref_index, ln_w, ln_b, gamma, d, po, err);
-    else if (H == 1024) hipLaunchKernelGGL(group_diff_kernel<4>, dim3(M), dim3(64), 0, s, xr, r_stride, xd, d_stride, ref_index, ln_w, ln_b, gamma, d, po, err);
+    if (H == 768) hipLaunchKernelGGL(group_diff_kernel<3>, dim3(M), dim3(64), 0, s, xr, r_stride, xd, d_stride, ref_index, ln_w, ln_b, gamma, d, po, err, r_row0, d_row0);
+    else if (H == 1024) hipLaunchKernelGGL(group_diff_kernel<4>, dim3(M), dim3(64), 0, s, xr, r_stride, xd, d_stride, ref_index, ln_w, ln_b, gamma, d, po, err, r_row0, d_row0);
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }
 
-hipError_t launch_export_rows(const float* src, int64_t stride, float* out, int rows, int H, hipStream_t s, int* err) {
+hipError_t launch_export_rows(const float* src, int64_t stride, float* out, int rows, int H, hipStream_t s, int* err, const int* row0) {
     if (rows < 1 || H % 4 || stride % 4) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(export_rows_kernel, dim3(rows), dim3(256), 0, s, src, stride, out, H / 4, err);
+    hipLaunchKernelGGL(export_rows_kernel, dim3(rows), dim3(256), 0, s, src, stride, out, H / 4, err, row0);
     return hipGetLastError();
 }
 

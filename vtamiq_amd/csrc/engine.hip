@@ -158,10 +158,9 @@ struct vtq_engine {
     float *fold_u = nullptr, *fold_part = nullptr;              //   folded attention (cls_tail.hip): W_k^T q per (sequence, head); chunk partials
     void* fold_z = nullptr;                                      //   its output planes (encoder format): [r_alloc][H / 64 * H]
     int64_t fold_z_plane = 0;
-    // One call's device table (upload_table): vtq_forward_varlen's sequence row offsets | lengths | patch-row prefix | attention block
-    // table, or the group entries' ref_index.  Built on the host in a pinned image of this engine's own and uploaded on the call's stream
-    // ahead of the first launch.  vl_uploaded: recorded behind the upload, waited for before the next call rewrites the image.  Per
-    // engine: nothing of this is shared between handles.
+    // One call's device table (upload_table; its sections: Table below).  Built on the host in a pinned image of this engine's own and
+    // uploaded on the call's stream ahead of the first launch.  vl_uploaded: recorded behind the upload, waited for before the next call
+    // rewrites the image.  Per engine: nothing of this is shared between handles.
     int* vl_tab = nullptr;               //   device (workspace)
     int* vl_host = nullptr;              //   pinned host image
     size_t vl_host_ints = 0;
@@ -370,25 +369,37 @@ Geometry geometry_seq(const vtq_engine* e, int nseq, int N) {
 }
 // the capacity form: B sequence pairs of N patches
 Geometry geometry(const vtq_engine* e, int B, int N) { return geometry_seq(e, 2 * B, N); }
-// vtq_forward_varlen: B pairs of sumN patches in all, at most maxN in one.  Sequences packed back to back at their own length, so the
-// row counts come from the sum; S is the largest sequence (the chunk pitch of the CLS fold's partials), and the map describes the whole
-// batch as ONE run of rows, which is what the pad-row clear needs to know -- every other kernel addresses by the call's tables (VarLen)
-Geometry geometry_varlen(const vtq_engine* e, int B, int64_t sumN, int maxN) {
-    const int64_t rows = 2 * (sumN + (int64_t)B * e->T);
+// The variable-length entries: nseq sequences of sumN patches in all (every image counted), at most maxN in one.  Sequences packed back to
+// back at their own length, so the row counts come from the sum; S is the largest sequence (the chunk pitch of the CLS fold's partials),
+// and the map describes the whole batch as ONE run of rows, which is what the pad-row clear needs to know -- every other kernel addresses
+// by the call's tables (VarLen)
+Geometry geometry_varlen(const vtq_engine* e, int nseq, int64_t sumN, int maxN) {
+    const int64_t rows = sumN + (int64_t)nseq * e->T;
     Geometry g;
     g.S = g.S_pad = maxN + e->T;
-    g.nseq = 2 * B;
+    g.nseq = nseq;
     g.M_pad = round_up(rows, 256);
-    g.P_pad = round_up(2 * sumN, 256);
+    g.P_pad = round_up(sumN, 256);
     g.rows_alloc = (g.M_pad > g.P_pad ? g.M_pad : g.P_pad) + 128;
     g.R_pad = round_up(g.nseq, 64);
     g.sm = SeqMap{(int)rows, 1, (int)(g.M_pad - rows)};
     return g;
 }
 
-// ints of vtq_forward_varlen's device tables for nseq sequences of at most S rows: row offsets [nseq + 1], lengths [nseq], patch prefix
-// [nseq / 2 + 1] (padded to whole int4), then 4 per attention workgroup -- sum_j ceil(S_j / 128) <= nseq * ceil(S / 128) query blocks per head
-int64_t varlen_table_ints(int64_t nseq, int64_t S, int H) { return round_up(3 * nseq + 4, 4) + 4 * nseq * ((S + 127) / 128) * (H / 64); }
+// THE layout of one call's device table (e->vl_tab), in ints.  A variable-length call of nseq sequences, M of them scored through ref_index
+// (0: pairs, or vtq_encode_reference_varlen):
+//     [0, nseq]          row offsets: sequence j is the rows [row0[j], row0[j + 1]) of the activation buffers
+//     [len, len + nseq)  lengths S_j
+//     [ref, ref + M)     ref_index
+//     [blk, ...)         the attention block table, 4 ints per workgroup (attention_varlen.hip); the ints between ref + M and blk are zero
+// There is no patch-row prefix: embed_index_kernel derives it from the row offsets.  A uniform group / cached call holds ref_index alone,
+// at 0.  blk does not depend on M, so the table of any call of nseq sequences of at most S rows fits varlen_table_ints(nseq, S, H).
+struct Table {
+    int len, ref, blk;
+    explicit Table(int nseq) : len(nseq + 1), ref(2 * nseq + 1), blk((int)round_up(3 * (int64_t)nseq + 4, 4)) {}      // ref + M <= 3 nseq + 1 <= blk
+};
+// upper bound in ints: blk, then 4 per attention workgroup -- sum_j ceil(S_j / 128) <= nseq * ceil(S / 128) query blocks per head
+int64_t varlen_table_ints(int64_t nseq, int64_t S, int H) { return Table((int)nseq).blk + 4 * nseq * ((S + 127) / 128) * (H / 64); }
 
 // One workspace buffer: the engine member it fills, its `planes` planes of `elems` elements of `esz` bytes (the plane stride goes
 // to *stride where the engine keeps one), and whether reserve() zero-fills it.
@@ -425,7 +436,7 @@ std::vector<WsBuf> workspace(vtq_engine* e, int B, int N) {
         {&e->fold_z, &e->fold_z_plane, R * nh * H, 2, apl, true},
     };
     for (float*& hb : e->hb) w.push_back({(void**)&hb, nullptr, g.nseq * H, 4, 1, false});   // head ping-pong rows
-    w.push_back({(void**)&e->vl_tab, nullptr, varlen_table_ints(g.nseq, g.S, (int)H), 4, 1, false});   // vtq_forward_varlen's tables
+    w.push_back({(void**)&e->vl_tab, nullptr, varlen_table_ints(g.nseq, g.S, (int)H), 4, 1, false});   // one call's device table (Table)
     return w;
 }
 
@@ -522,9 +533,9 @@ struct Call {
     bool tokens_in = false;                    // `in` holds (B, N, H) feature rows (transformer.py:534-535), not 5-D patches
     const float *in[3] = {}, *pos[3] = {}, *scales[3] = {};      // per image (the embedding launches read slot 1 with nimg = 1 too: NULL)
     int B = 0, N = 0;                          // B items of N patches per image, or
-    const int32_t* n_patches = nullptr;        //   vtq_forward_varlen: pair b has n_patches[b]; their sum and maximum
-    int64_t sumN = 0;
-    int maxN = 0;
+    const int32_t* n_img[2] = {};              //   variable length (HOST arrays): item i of image k has n_img[k][i] patches -- image 0 holds rg.G
+    int64_t sumN[2] = {};                      //   items with REF_GROUP, else B; vtq_forward_varlen passes ONE array for both images.  Their sums
+    int maxN = 0;                              //   per image and the maximum over all
     float* q_out = nullptr;
     // vtq_forward_vit: encoder_norm of `rows` rows per image; per-layer residual rows and attention probabilities (optional)
     float *out = nullptr, *states = nullptr, *probs = nullptr;
@@ -569,9 +580,9 @@ int upload_table(vtq_engine* e, const char* who, size_t ints, hipStream_t s, F f
     return 0;
 }
 
-// One vtq_forward_varlen call's device tables (in e->vl_tab): sequence j is the len[j] rows from row0[j], pair b's patches the rows from
-// prefix[b] of each image; `blocks`: attention_varlen.hip.  All NULL / 0: a uniform call, addressed by its Geometry alone
-struct VarLen { const int* row0; const int* len; const int* prefix; const int* blocks; int nblocks; };
+// Where one call's device tables lie in e->vl_tab (Table): sequence j is the len[j] rows from row0[j]; `blocks`: attention_varlen.hip.  All
+// NULL / 0: a uniform call, addressed by its Geometry alone.  ref_index: the group / cached forms of either kind
+struct VarLen { const int* row0; const int* len; const int* blocks; int nblocks; const int* ref_index; };
 
 // All encoder layers for the g.nseq sequences, enqueued on s.  vl.row0 != NULL: sequences of different lengths (g.S = the largest)
 int run_encoder(vtq_engine* e, const Call& call, const Geometry& g, hipStream_t s, bool prune, const VarLen& vl) {
@@ -1087,12 +1098,17 @@ static int finish(vtq_engine* e, const Call& c, const Geometry& g, hipStream_t s
         // the consumed token's residual row of sequence j: row j of the tail's output, or token row iqa_token of sequence j in x
         const float* rows = prune ? e->xcls : e->x + (int64_t)e->iqa_token * H;
         const int64_t stride = prune ? H : (int64_t)g.S_pad * H;
+        // sequences of different lengths in x (the unpruned path of a variable-length call): sequence j's row comes from the row offsets
+        const int* row0 = prune ? nullptr : vl.row0;
         if (mode == REF_ENCODE) {
-            HIP_TRY(launch_export_rows(rows, stride, c.rg.rows, B, H, s, e->err_flag));
+            HIP_TRY(launch_export_rows(rows, stride, c.rg.rows, B, H, s, e->err_flag, row0));
             return 0;
         }
-        if (mode == REF_GROUP) HIP_TRY(launch_group_diff(rows, stride, rows + B0 * stride, stride, e->vl_tab, B, e->encw, e->encb, gamma, d, H, hp, s, e->err_flag));
-        else if (mode == REF_CACHED) HIP_TRY(launch_group_diff(c.rg.rows, H, rows, stride, e->vl_tab, B, e->encw, e->encb, gamma, d, H, hp, s, e->err_flag));
+        if (mode == REF_GROUP)
+            HIP_TRY(launch_group_diff(rows, stride, rows + (row0 ? 0 : B0 * stride), stride, vl.ref_index, B, e->encw, e->encb, gamma, d, H, hp, s, e->err_flag,
+                                      row0, row0 ? row0 + B0 : nullptr));
+        else if (mode == REF_CACHED)
+            HIP_TRY(launch_group_diff(c.rg.rows, H, rows, stride, vl.ref_index, B, e->encw, e->encb, gamma, d, H, hp, s, e->err_flag, nullptr, row0));
         else if (prune) HIP_TRY(launch_final_diff(e->xcls, e->encw, e->encb, gamma, d, B, ndist, SeqMap{1, g.nseq, 0}, H, hp, s, e->err_flag));
         else HIP_TRY(launch_final_diff(e->x + (int64_t)e->iqa_token * H, e->encw, e->encb, gamma, d, B, ndist, g.sm, H, hp, s, e->err_flag, vl.row0));
         if (run_head(e, d, HB, c.q_out, s, true)) return 1;
@@ -1104,10 +1120,10 @@ static int finish(vtq_engine* e, const Call& c, const Geometry& g, hipStream_t s
 
 // THE forward path: every entry checks its own arguments, describes its batch as a Call and ends here.  Each step is stated once; what
 // differs between the entries is read off the Call where it differs.
-//   REF_GROUP: image 0 holds rg.G sequences instead of B;  vtq_forward_varlen (n_patches != NULL): B pairs, each at its own length
+//   REF_GROUP: image 0 holds rg.G sequences instead of B;  the variable-length entries (n_img[0] != NULL): every sequence at its own length
 static int forward(vtq_engine* e, Call c, void* stream) {
     const vtq_config& cfg = e->cfg;
-    const bool varlen = c.n_patches != nullptr, rollout = c.rollout_out != nullptr, tokens_in = c.tokens_in, use_scales = cfg.num_scales > 1;
+    const bool varlen = c.n_img[0] != nullptr, rollout = c.rollout_out != nullptr, tokens_in = c.tokens_in, use_scales = cfg.num_scales > 1;
     const int nimg = c.nimg, B = c.B, mode = c.rg.mode, H = e->H, T = e->T;
     const int B0 = mode == REF_GROUP ? c.rg.G : B;           // sequences of image 0
     const int nseq = B0 + (nimg - 1) * B;
@@ -1118,29 +1134,30 @@ static int forward(vtq_engine* e, Call c, void* stream) {
     // fp8 mode: the first forward of an engine calibrates the activation scales on its own batch (see kSPatch); it synchronises
     // the stream once per quantisation point and returns this batch's scores computed with the final scales
     c.calibrating = e->fp8 && !e->fp8_static && !e->fp8_calibrated && e->dbg_stop < 0;
-    const Geometry g = varlen ? geometry_varlen(e, B, c.sumN, c.maxN) : geometry_seq(e, nseq, c.N);
+    const Geometry g = varlen ? geometry_varlen(e, nseq, c.sumN[0] + c.sumN[1], c.maxN) : geometry_seq(e, nseq, c.N);
 
     // ---- the call's device table: host image, then ONE upload on `s` ahead of every launch --------------------------------------
     VarLen vl{};
+    const bool indexed = mode == REF_GROUP || mode == REF_CACHED;
     if (varlen) {
-        const int off_len = nseq + 1, off_pfx = 2 * nseq + 1, off_blk = (int)round_up(3 * nseq + 4, 4);
+        const Table tb(nseq);
+        const int nref = indexed ? B : 0;
         std::vector<int> len(nseq);
-        for (int j = 0; j < nseq; ++j) len[j] = c.n_patches[j % B] + T;
+        for (int j = 0; j < nseq; ++j) len[j] = (j < B0 ? c.n_img[0][j] : c.n_img[1][j - B0]) + T;
         const std::vector<int> blocks = attention_varlen_blocks(len.data(), nseq, H);
         const auto fill = [&](int* t) {
             int64_t r = 0;
-            for (int j = 0; j < nseq; ++j) { t[j] = (int)r; t[off_len + j] = len[j]; r += len[j]; }
+            for (int j = 0; j < nseq; ++j) { t[j] = (int)r; t[tb.len + j] = len[j]; r += len[j]; }
             t[nseq] = (int)r;
-            int pf = 0;
-            for (int b = 0; b < B; ++b) { t[off_pfx + b] = pf; pf += c.n_patches[b]; }
-            t[off_pfx + B] = pf;
-            for (int k = off_pfx + B + 1; k < off_blk; ++k) t[k] = 0;
-            memcpy(t + off_blk, blocks.data(), blocks.size() * sizeof(int));
+            for (int m = 0; m < nref; ++m) t[tb.ref + m] = c.rg.ref_index[m];
+            for (int k = tb.ref + nref; k < tb.blk; ++k) t[k] = 0;
+            memcpy(t + tb.blk, blocks.data(), blocks.size() * sizeof(int));
         };
-        if (upload_table(e, c.who, (size_t)off_blk + blocks.size(), s, fill)) return 1;
-        vl = VarLen{e->vl_tab, e->vl_tab + off_len, e->vl_tab + off_pfx, e->vl_tab + off_blk, (int)(blocks.size() / 4)};
-    } else if (mode == REF_GROUP || mode == REF_CACHED) {    // ref_index
+        if (upload_table(e, c.who, (size_t)tb.blk + blocks.size(), s, fill)) return 1;
+        vl = VarLen{e->vl_tab, e->vl_tab + tb.len, e->vl_tab + tb.blk, (int)(blocks.size() / 4), indexed ? e->vl_tab + tb.ref : nullptr};
+    } else if (indexed) {
         if (upload_table(e, c.who, (size_t)B, s, [&](int* t) { for (int m = 0; m < B; ++m) t[m] = c.rg.ref_index[m]; })) return 1;
+        vl.ref_index = e->vl_tab;
     }
     {   // tile schedules of this geometry's GEMM shapes: built and uploaded here (first forward of a tile grid only; DESIGN.md section 4
         // has what bounds the cache), not inside a launch.  (M, 2H, H) is the rollout's query | key projection of the last layer; the
@@ -1158,16 +1175,16 @@ static int forward(vtq_engine* e, Call c, void* stream) {
     // ---- embeddings (transformer.py:526-562) -------------------------------------------------------------------
     // 5-D patches: packed to planes here, then one GEMM whose epilogue adds the table rows and scatters into x.  Pre-embedded input
     // (transformer.py:534-535): `in` are (B, N, H) feature rows; no patch convolution, a row kernel adds the table rows.
-    // Patch rows lie (image, item, patch): N1 per image after image 0's R0 -- uniform B * N after B0 * N, varlen the sum of the pairs'
-    // counts with the kernels' defaults for R0 and B0, the sequence map replaced by the tables, the pad rows cleared as the one run of g.sm
+    // Patch rows lie (image, item, patch): N1 per image after image 0's R0 -- uniform B * N after B0 * N, varlen the sums of each image's
+    // counts, the sequence map replaced by the tables, the pad rows cleared as the one run of g.sm
     {
-        const int N1 = varlen ? (int)c.sumN : B * c.N, R0 = varlen ? 0 : B0 * c.N;
+        const int N1 = varlen ? (int)c.sumN[nimg > 1] : B * c.N, R0 = varlen ? (int)c.sumN[0] : B0 * c.N;
         Prof p(e, s, VTQ_K_CONVERT);
         if (!tokens_in && e->fp8) {
             if (fp8_stage(e, c, s, e->s_patch, [&](float sc, Fp8Obs ob) { HIP_TRY(launch_pack_patches(c.in, nimg, e->big, e->big_plane, N1, cfg.patch_dim, (int)g.P_pad, 2, 1, s, sc, (int)e->PDp, ob)); return 0; })) return 1;
         } else if (!tokens_in) HIP_TRY(launch_pack_patches(c.in, nimg, e->big, e->big_plane, N1, cfg.patch_dim, (int)g.P_pad, e->f16, e->apl, s, 1.0f, (int)e->PDp, Fp8Obs{nullptr, nullptr}, R0));
-        HIP_TRY(launch_embed_index(c.pos, use_scales ? c.scales : nullptr, nimg, e->pidx, e->sidx, e->row_map, B, varlen ? (int)c.sumN : c.N, (int)g.P_pad, g.sm, T,
-                                   cfg.pos_grid, cfg.num_scales, e->err_flag, s, vl.prefix, vl.row0, varlen ? 0 : B0));
+        HIP_TRY(launch_embed_index(c.pos, use_scales ? c.scales : nullptr, nimg, e->pidx, e->sidx, e->row_map, B, varlen ? N1 : c.N, (int)g.P_pad, g.sm, T,
+                                   cfg.pos_grid, cfg.num_scales, e->err_flag, s, vl.row0, B0, varlen ? R0 : 0));
         HIP_TRY(launch_zero_pad_rows(e->x, g.sm.per, g.sm.pitch, g.sm, H, (int)g.rows_alloc, s));
         HIP_TRY(launch_tokens(e->x, e->cls, e->pos_table, e->extra, g.nseq, g.sm, T, H, s, vl.row0));
         if (tokens_in)
@@ -1203,7 +1220,7 @@ static int forward(vtq_engine* e, Call c, void* stream) {
     // (fp8 mode runs the full last layer: its CLS row then goes through the same e4m3 GEMMs as every other row)
     // (forward_vit needs every row of the last layer: always the full last layer)
     // (vtq_encode_reference / vtq_forward_cached encode single images in the form vtq_forward would pick: their rows meet in one difference)
-    // (vtq_forward_varlen refuses a trace and the fp8 engine before it gets here: for it this is cls_prune && no adapters)
+    // (the variable-length entries refuse a trace and the fp8 engine before they get here: for them this is cls_prune && no adapters)
     const bool prune = e->cls_prune && !e->trace && !e->fp8 && cfg.num_adapters == 0 && (nimg > 1 || mode != REF_PAIRS);
     if (run_encoder(e, c, g, s, prune, vl)) return 1;
     return finish(e, c, g, s, prune, vl);
@@ -1331,6 +1348,25 @@ int vtq_forward_rollout_tokens(vtq_handle e, const float* feats_ref, const float
 
 size_t vtq_rollout_workspace_bytes(vtq_handle e, int32_t B, int32_t N) { return (e && B >= 1 && N >= 1) ? ws_bytes(rollout_workspace(e, B, N)) : 0; }
 
+// The variable-length entries (n_img set, every count checked >= 1): what they share behind their own argument checks -- the sums and the
+// maximum of the counts, the kernels' 32-bit row index, the scale rule, the weights
+static int forward_ragged(vtq_handle e, Call c, void* stream) {
+    const int B0 = c.rg.mode == REF_GROUP ? c.rg.G : c.B, nseq = B0 + (c.nimg - 1) * c.B;
+    for (int k = 0; k < c.nimg; ++k)
+        for (int i = 0, n = k == 0 ? B0 : c.B; i < n; ++i) {
+            c.sumN[k] += c.n_img[k][i];
+            if (c.n_img[k][i] > c.maxN) c.maxN = c.n_img[k][i];
+        }
+    const int64_t rows = c.sumN[0] + c.sumN[1] + (int64_t)nseq * e->T;
+    if (rows + 512 > INT32_MAX / 4 || (int64_t)nseq * (c.maxN + e->T) + 512 > INT32_MAX / 4)
+        return fail("%s: %lld token rows exceed the 32-bit row index of the kernels", c.who, (long long)rows);
+    if (e->cfg.num_scales > 1)
+        for (int k = 0; k < c.nimg; ++k)
+            if (!c.scales[k]) return fail("Model uses scale embedding but scales is passed as None.");   // transformer.py:547-548
+    if (all_loaded(e, c.who)) return 1;
+    return forward(e, c, stream);
+}
+
 // B pairs of different patch counts through one launch sequence (include/vtamiq_hip.h).  Layout: sequences packed back to back at their
 // own length, all reference sequences, then all distorted ones; the packed patch rows likewise (image, pair, patch).  Every kernel is
 // row- or sequence-independent and the GEMMs are bitwise independent of M, so pair b's score has the bits of a B = 1 call on pair b.
@@ -1347,17 +1383,8 @@ int vtq_forward_varlen(vtq_handle e, const float* patches_ref, const float* patc
     if (!q_out) return fail("vtq_forward_varlen: null output");
     if (e->trace) return fail("vtq_forward_varlen: a token trace buffer is set (vtq_set_token_trace): the trace layout is per uniform batch");
     Call c = call_pair("vtq_forward_varlen", false, patches_ref, patches_dist, pos_ref, pos_dist, scales_ref, scales_dist, B, 0, q_out);
-    c.n_patches = n_patches;
-    for (int b = 0; b < B; ++b) {
-        c.sumN += n_patches[b];
-        if (n_patches[b] > c.maxN) c.maxN = n_patches[b];
-    }
-    const int64_t rows = 2 * (c.sumN + (int64_t)B * e->T);
-    if (rows + 512 > INT32_MAX / 4 || (int64_t)2 * B * (c.maxN + e->T) + 512 > INT32_MAX / 4)
-        return fail("vtq_forward_varlen: %lld token rows exceed the 32-bit row index of the kernels", (long long)rows);
-    if (e->cfg.num_scales > 1 && (!scales_ref || !scales_dist)) return fail("Model uses scale embedding but scales is passed as None.");   // transformer.py:547-548
-    if (all_loaded(e, "vtq_forward_varlen")) return 1;
-    return forward(e, c, stream);
+    c.n_img[0] = c.n_img[1] = n_patches;
+    return forward_ragged(e, c, stream);
 }
 
 static int forward_triplet(vtq_handle e, const char* who, bool tokens_in, const float* const* in, const float* const* pos,
@@ -1454,6 +1481,70 @@ int vtq_forward_cached(vtq_handle e, const float* ref_rows, int32_t G, const flo
     Call c = call_single(who, tokens_in, in, pos, scales, M, N, q_out);
     c.rg = RefGroup{REF_CACHED, G, ref_index, const_cast<float*>(ref_rows)};
     return forward_uniform(e, c, stream);
+}
+
+// ---- one-to-many scoring on images of different patch counts (include/vtamiq_hip.h) ------------------------------------------------------
+// Packed as vtq_forward_varlen packs: all G reference sequences, then all M distorted ones, each at its own length; the patch rows likewise.
+// Every kernel is row- or sequence-independent, so a sequence has the bits of the uniform entry on that image alone.
+static int check_counts(const char* who, const char* name, const int32_t* n, int32_t count) {
+    for (int i = 0; i < count; ++i)
+        if (n[i] < 1) return fail("%s: %s[%d] = %d (every image needs at least one patch)", who, name, i, (int)n[i]);
+    return 0;
+}
+
+// the batch description (it needs no handle): G references, M distorted images, ref_index where one is taken
+static int check_group_varlen(const char* who, int32_t G, int32_t M, const int32_t* ref_index, bool need_index) {
+    if (need_index && !ref_index) return fail("%s: null ref_index", who);
+    if (G < 1 || M < 1) return fail("%s: G=%d M=%d", who, (int)G, (int)M);
+    if (ref_index)
+        for (int m = 0; m < M; ++m)
+            if (ref_index[m] < 0 || ref_index[m] >= G) return fail("%s: ref_index[%d] = %d outside [0, %d)", who, m, (int)ref_index[m], (int)G);
+    return 0;
+}
+
+int vtq_forward_group_varlen(vtq_handle e, const float* patches_ref, const float* patches_dist, const float* pos_ref, const float* pos_dist,
+                             const float* scales_ref, const float* scales_dist, int32_t G, int32_t M, const int32_t* n_ref, const int32_t* n_dist,
+                             const int32_t* ref_index, float* q_out, void* stream) {
+    const char* who = "vtq_forward_group_varlen";
+    if (!n_ref) return fail("%s: null n_ref", who);
+    if (!n_dist) return fail("%s: null n_dist", who);
+    if (check_group_varlen(who, G, M, ref_index, true) || check_counts(who, "n_ref", n_ref, G) || check_counts(who, "n_dist", n_dist, M)) return 1;
+    if (check_group_handle(who, e)) return 1;
+    if (!patches_ref || !patches_dist || !pos_ref || !pos_dist) return fail("%s: null tensor", who);
+    if (!q_out) return fail("%s: null output", who);
+    Call c = call_pair(who, false, patches_ref, patches_dist, pos_ref, pos_dist, scales_ref, scales_dist, M, 0, q_out);
+    c.rg = RefGroup{REF_GROUP, G, ref_index, nullptr};
+    c.n_img[0] = n_ref;
+    c.n_img[1] = n_dist;
+    return forward_ragged(e, c, stream);
+}
+
+int vtq_encode_reference_varlen(vtq_handle e, const float* patches, const float* pos, const float* scales, int32_t G, const int32_t* n_patches,
+                                float* ref_rows, void* stream) {
+    const char* who = "vtq_encode_reference_varlen";
+    if (!n_patches) return fail("%s: null n_patches", who);
+    if (check_group_varlen(who, G, 1, nullptr, false) || check_counts(who, "n_patches", n_patches, G)) return 1;
+    if (check_group_handle(who, e)) return 1;
+    if (!patches || !pos) return fail("%s: null tensor", who);
+    if (!ref_rows) return fail("%s: null output", who);
+    Call c = call_single(who, 0, patches, pos, scales, G, 0, nullptr);
+    c.rg = RefGroup{REF_ENCODE, G, nullptr, ref_rows};
+    c.n_img[0] = n_patches;
+    return forward_ragged(e, c, stream);
+}
+
+int vtq_forward_cached_varlen(vtq_handle e, const float* ref_rows, int32_t G, const float* patches, const float* pos, const float* scales, int32_t M,
+                              const int32_t* n_patches, const int32_t* ref_index, float* q_out, void* stream) {
+    const char* who = "vtq_forward_cached_varlen";
+    if (!n_patches) return fail("%s: null n_patches", who);
+    if (check_group_varlen(who, G, M, ref_index, true) || check_counts(who, "n_patches", n_patches, M)) return 1;
+    if (check_group_handle(who, e)) return 1;
+    if (!ref_rows || !patches || !pos) return fail("%s: null tensor", who);
+    if (!q_out) return fail("%s: null output", who);
+    Call c = call_single(who, 0, patches, pos, scales, M, 0, q_out);
+    c.rg = RefGroup{REF_CACHED, G, ref_index, const_cast<float*>(ref_rows)};
+    c.n_img[0] = n_patches;
+    return forward_ragged(e, c, stream);
 }
 
 int vtq_input_errors(vtq_handle e, int32_t* flags, void* stream) {

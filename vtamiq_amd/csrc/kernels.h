@@ -33,7 +33,7 @@ inline bool num_valid(Num n) {
 // sequences per part-batch, each part-batch padded by `gap` rows to a multiple of 256 (the GEMM tile height).
 struct SeqMap { int pitch, per, gap; };
 __host__ __device__ inline int64_t seq_row(const SeqMap& m, int s) { return (int64_t)s * m.pitch + (int64_t)(s / m.per) * m.gap; }
-// Variable-length batches (vtq_forward_varlen): sequences of different lengths packed back to back.  Device tables, [nseq] each: the
+// Variable-length batches (vtq_forward_varlen, vtq_forward_group_varlen ...): sequences of different lengths packed back to back.  Device tables, [nseq] each: the
 // first row of sequence j in the activation buffers (the prefix sum of the lengths) and its length S_j.  Both NULL = the uniform
 // SeqMap / (stride, S) form of the kernel that takes one; with tables the kernel addresses by them and computes the same arithmetic.
 struct VarSeq { const int* row0; const int* len; };
@@ -121,10 +121,11 @@ hipError_t launch_pack_patches(const float* const* imgs, int nimg, void* dst, in
 // positions outside [0, 1) are clamped into the table and flagged in *err (bit 0)
 hipError_t launch_embed_index(const float* const* pos, const float* const* sc, int nimg, int* pidx, int* sidx, int* row_map, int B, int N,
                               int rows_pad, SeqMap sm, int T, int grid, int num_scales, int* err, hipStream_t s,
-                              const int* vl_prefix = nullptr, const int* vl_row0 = nullptr, int B0 = 0);
+                              const int* vl_row0 = nullptr, int B0 = 0, int N0 = 0);
 // B0 != 0 (unequal groups): image 0 holds B0 sequences (the first B0 of the batch), every later image B, N patches each
-// vl_prefix != NULL (variable length): vl_prefix[b] patches lie in front of pair b in each image, vl_prefix[B] = N = the patches of one
-// image (all pairs); patch row -> pair by search in the prefix, row_map = vl_row0[img * B + pair] + T + (row - vl_prefix[pair])
+// vl_row0 != NULL (variable length): N = the patch rows of every later image (all its items), N0 (0: = N) those of image 0; item i of an
+// image is sequence base + i (base: 0 for image 0, B0 behind it) and the patch-row prefix of item i is derived from the row offsets, vl_row0[base + i] -
+// vl_row0[base] - i * T: patch row -> item by search in that prefix, row_map = the item's first row + T + (row - prefix)
 
 // CLS (+pos row 0) and register tokens into the first T rows of every sequence
 // pre-embedded input (transformer.py:534-535): x[row_map[r]] = feats[r] + table1[pidx[r]] (+ table2[sidx[r]]); feats: nimg pointers to (B*N, H) fp32
@@ -178,11 +179,14 @@ hipError_t launch_final_diff(const float* x, const float* ln_w, const float* ln_
 
 // The one-to-many difference: d[m] = gamma * (LN(xr + ref_index[m] * r_stride) - LN(xd + m * d_stride)), m < M, with launch_final_diff's
 // arithmetic, plane store and non-finite report.  ref_index: DEVICE table [M] of values the host has checked against the reference count;
-// strides in elements (% 4 == 0)
+// strides in elements (% 4 == 0).  r_row0 / d_row0 != NULL (DEVICE tables; sequences of different lengths): reference g lies at
+// xr + r_row0[g] * H, distorted image m at xd + d_row0[m] * H, whatever the stride says
 hipError_t launch_group_diff(const float* xr, int64_t r_stride, const float* xd, int64_t d_stride, const int* ref_index, int M, const float* ln_w,
-                             const float* ln_b, const float* gamma, float* d, int H, PlaneOut po, hipStream_t s, int* err = nullptr);
-// out[r][H] = the fp32 row src + r * stride, r < rows (vtq_encode_reference); bit 1 of *err for a non-finite value
-hipError_t launch_export_rows(const float* src, int64_t stride, float* out, int rows, int H, hipStream_t s, int* err = nullptr);
+                             const float* ln_b, const float* gamma, float* d, int H, PlaneOut po, hipStream_t s, int* err = nullptr,
+                             const int* r_row0 = nullptr, const int* d_row0 = nullptr);
+// out[r][H] = the fp32 row src + r * stride (row0 != NULL: src + row0[r] * H), r < rows (vtq_encode_reference); bit 1 of *err for a non-finite value
+hipError_t launch_export_rows(const float* src, int64_t stride, float* out, int rows, int H, hipStream_t s, int* err = nullptr,
+                              const int* row0 = nullptr);
 
 // one-time RCAB weight fold [Wc ; Wd Wc], bcat = [bc ; Wd bc + bd] (head.hip)
 hipError_t launch_fold_ca(const float* Wc, const float* bc, const float* Wd, const float* bd, float* Wcat, float* bcat, int H, int hid,

@@ -111,6 +111,39 @@ def _ref_index(ref_index, G: int, M: int):
     return idx
 
 
+def _lengths(lengths, what: str):
+    """Per-image patch counts of the one-to-many entries (`lengths=`) as a list of ints >= 1, checked on the host before any tensor or device
+    is looked at: a sequence of ints or a 1-D CPU integer tensor."""
+    if isinstance(lengths, torch.Tensor):
+        if lengths.device.type != "cpu":
+            raise ValueError(f"{what} must be a sequence of ints or a CPU integer tensor: a CUDA tensor would force a device synchronisation")
+        if lengths.dtype.is_floating_point or lengths.dtype.is_complex or lengths.dtype == torch.bool or lengths.dim() != 1:
+            raise ValueError(f"{what} must be a 1-D integer tensor")
+        lengths = lengths.tolist()
+    try:
+        lengths = list(lengths)
+    except TypeError:
+        raise ValueError(f"{what} must be a sequence of ints or a CPU integer tensor, got {lengths!r}") from None
+    if not lengths or any(isinstance(v, bool) or not isinstance(v, numbers.Integral) or v < 1 for v in lengths):
+        raise ValueError(f"{what} must hold at least one image and only integers >= 1, got {lengths}")
+    return [int(v) for v in lengths]
+
+
+def _ragged(t, lens, what: str, tail):
+    """One image's tensor of a `lengths=` call -- the images' rows concatenated, (sum(lengths), *tail), or a list of per-image (n_i, *tail)
+    tensors, concatenated here on their device -- as the one "batch" of sum(lengths) rows VTAMIQ._inputs checks.  None stays None."""
+    if t is None:
+        return None
+    total = sum(lens)
+    if isinstance(t, (list, tuple)):
+        if len(t) != len(lens) or any(u.shape[0] != n for u, n in zip(t, lens)):
+            raise ValueError(f"{what}: a list must hold one tensor per image with lengths[i] rows each")
+        t = torch.cat([u.reshape(u.shape[0], *tail) for u in t], 0)
+    if t.shape[0] != total or t.numel() != total * math.prod(tail):
+        raise ValueError(f"{what}: {tuple(t.shape)} does not hold sum(lengths) = {total} rows of shape {tuple(tail)}")
+    return t.reshape(1, total, *tail)
+
+
 class _Params(nn.Module):
     """A container whose forward must never run."""
 
@@ -757,7 +790,26 @@ class VTAMIQ(nn.Module):
         t = int(self.token_num)
         return t + self.spec.num_tokens if t < 0 else t
 
-    def forward_group(self, patches, pos, scales, ref_index):
+    def _ragged_image(self, what, patches, pos, scales, lens):
+        """One image's (patches, pos, scales) of a `lengths=` call as the one-item batches _inputs takes, their row counts checked against
+        sum(lengths) -- before any device is looked at."""
+        P = self.spec.patch_size
+        first = patches[0] if isinstance(patches, (list, tuple)) else patches
+        if first.dim() != 4:
+            raise ValueError(f"{what}: with lengths, patches are (sum(lengths), 3, {P}, {P}) tensors (pre-embedded input is not offered), "
+                             f"got {tuple(first.shape)}")
+        pt = _ragged(patches, lens, "patches", tuple(first.shape[1:]))
+        ps = _ragged(pos, lens, "pos", (2,)) if self.spec.use_pos_embedding else pos
+        sc = _ragged(scales, lens, "scales", ()) if self.spec.use_scale_embedding else None
+        return pt, ps, sc
+
+    def _ragged_inputs(self, what, patches, pos, scales, lens):
+        """_ragged_image through _inputs: (device, patches, pos, scales), each the concatenated tensor, fp32 and contiguous."""
+        pt, ps, sc = self._ragged_image(what, patches, pos, scales, lens) if lens is not None else (patches, pos, scales)
+        device, _, _, _, (pt,), (ps,), (sc,) = self._inputs((pt,), (ps,), (sc,))
+        return device, pt, ps, sc
+
+    def forward_group(self, patches, pos, scales, ref_index, *, lengths=None):
         """M distorted images over G references in ONE call, every reference encoded once: G + M sequences where forward() on the expanded
         pairs encodes 2 M.
           patches    (p_ref, p_dist): (G, N, 3, P, P) and (M, N, 3, P, P) -- or both pre-embedded, (G | M, N, H), as in forward()
@@ -765,10 +817,37 @@ class VTAMIQ(nn.Module):
           ref_index  M integers in [0, G), a sequence or a CPU integer tensor (a CUDA tensor is refused: reading it would synchronise the
                      stream); any order, repeats and unused references are allowed
         Returns (q, None), q (M,) fp32: q[m] has the bits `self((p_ref[i:i+1], p_dist[m:m+1]), ...)[0]` gives, i = ref_index[m], in every
-        precision and model configuration.  The input / range policy ("auto", validate_inputs, check_inputs) is forward()'s."""
+        precision and model configuration.  The input / range policy ("auto", validate_inputs, check_inputs) is forward()'s.
+          lengths    None, or (lengths_ref, lengths_dist) for images of DIFFERENT patch counts: G and M integers >= 1, each a sequence or a
+                     CPU integer tensor.  patches / pos / scales are then per image the concatenated tensors, (sum, 3, P, P) / (sum, 2) /
+                     (sum,), or lists of per-image tensors, as in forward_varlen (5-D patches only).  A distorted image's count need not be
+                     its reference's.  q[m] has the bits of encode_reference on reference i alone followed by forward_cached on image m
+                     alone -- with equal counts, of `self(...)` on the pair; all counts equal give the bits of the call without lengths."""
         self._group_guard("forward_group")
         if len(patches) != 2:
             raise ValueError("forward_group expects patches = (p_ref, p_dist)")
+        if lengths is not None:
+            if isinstance(lengths, torch.Tensor) or len(lengths) != 2 or lengths[0] is None or lengths[1] is None:
+                raise ValueError("forward_group: lengths must be (lengths_ref, lengths_dist), one entry per image of each")
+            lr, ld = _lengths(lengths[0], "lengths[0]"), _lengths(lengths[1], "lengths[1]")
+            G, M = len(lr), len(ld)
+            idx = _ref_index(ref_index, G, M)
+            pos = pos if pos is not None else (None, None)
+            scales = scales if scales is not None else (None, None)
+            ref = self._ragged_image("forward_group", patches[0], pos[0], scales[0], lr)
+            dist = self._ragged_image("forward_group", patches[1], pos[1], scales[1], ld)
+            device, pr, qr, sr = self._ragged_inputs("forward_group", *ref, None)
+            device_d, pd, qd, sdist = self._ragged_inputs("forward_group", *dist, None)
+            if device_d != device:
+                raise ValueError("forward_group: references and distorted images must live on one device")
+            with torch.cuda.device(device):
+                q = torch.empty(M, device=device, dtype=torch.float32)
+                nr, nd, arr = (C.c_int32 * G)(*lr), (C.c_int32 * M)(*ld), (C.c_int32 * M)(*idx)
+                stream = torch.cuda.current_stream(device).cuda_stream
+                self._launch_checked(device, lambda lib: self._check(lib.vtq_forward_group_varlen(
+                    self._engine, pr.data_ptr(), pd.data_ptr(), qr.data_ptr(), qd.data_ptr(), _ptr(sr), _ptr(sdist), G, M, nr, nd, arr,
+                    q.data_ptr(), stream)))
+            return q, None
         G, M = int(patches[0].shape[0]), int(patches[1].shape[0])
         idx = _ref_index(ref_index, G, M)
         pos = pos if pos is not None else (None, None)
@@ -786,11 +865,25 @@ class VTAMIQ(nn.Module):
                 self._engine, pr.data_ptr(), pd.data_ptr(), qr.data_ptr(), qd.data_ptr(), _ptr(sr), _ptr(sdist), G, M, N, arr, q.data_ptr(), stream)))
         return q, None
 
-    def encode_reference(self, patches, pos, scales=None) -> ReferenceFeatures:
+    def encode_reference(self, patches, pos, scales=None, *, lengths=None) -> ReferenceFeatures:
         """Encode G reference images once, for forward_cached(): (G, N, 3, P, P) patches (or pre-embedded (G, N, H)), pos (G, N, 2), scales
         (G, N) or None.  Returns a ReferenceFeatures whose `.rows` (G, H) are an ordinary tensor of the caller's.  The input / range policy is
-        forward()'s; check_inputs() raises FloatingPointError for a non-finite row."""
+        forward()'s; check_inputs() raises FloatingPointError for a non-finite row.
+          lengths  None, or G integers >= 1 (a sequence or a CPU integer tensor): references of DIFFERENT patch counts, patches / pos / scales
+                   the concatenated (sum(lengths), ...) tensors or lists of per-image tensors, as forward_group(lengths=...).  Row g has the
+                   bits of encode_reference on reference g alone."""
         self._group_guard("encode_reference")
+        if lengths is not None:
+            lens = _lengths(lengths, "lengths")
+            G = len(lens)
+            device, pt, pp, ps = self._ragged_inputs("encode_reference", patches, pos, scales, lens)
+            with torch.cuda.device(device):
+                rows = torch.empty(G, self.spec.hidden_size, device=device, dtype=torch.float32)
+                n_arr = (C.c_int32 * G)(*lens)
+                stream = torch.cuda.current_stream(device).cuda_stream
+                self._launch_checked(device, lambda lib: self._check(lib.vtq_encode_reference_varlen(
+                    self._engine, pt.data_ptr(), pp.data_ptr(), _ptr(ps), G, n_arr, rows.data_ptr(), stream)))
+            return ReferenceFeatures(rows, self.engine_precision, self._token(), self.engine_options, self._signature())
         device, G, N, tokens_in, (pt,), (pp,), (ps,) = self._inputs((patches,), (pos,), (scales,))
         with torch.cuda.device(device):
             rows = torch.empty(G, self.spec.hidden_size, device=device, dtype=torch.float32)
@@ -808,23 +901,30 @@ class VTAMIQ(nn.Module):
             return "the model's weights are not the ones that encoded them (another model, load_state_dict, .to(), an optimizer step)"
         return None
 
-    def forward_cached(self, ref: ReferenceFeatures, patches_dist, pos_dist, scales_dist=None, ref_index=None):
+    def forward_cached(self, ref: ReferenceFeatures, patches_dist, pos_dist, scales_dist=None, ref_index=None, *, lengths=None):
         """Score M distorted images against references encoded earlier (encode_reference): M sequences are encoded, nothing of the references.
           ref           ReferenceFeatures of G references, made by THIS model in its present state (else StaleReferenceError, a ValueError)
           patches_dist  (M, N, 3, P, P) or pre-embedded (M, N, H); pos_dist (M, N, 2); scales_dist (M, N) or None.  N need not be the
                         references' N
           ref_index     as forward_group(); None = range(M), which needs G == M
         Returns (q, None) with forward_group()'s contract.  Under precision "auto" an fp16 overflow switches the model to bf16x3 as usual and
-        the call then raises StaleReferenceError: the cached rows are fp16x3 rows; encode the references again."""
+        the call then raises StaleReferenceError: the cached rows are fp16x3 rows; encode the references again.
+          lengths       None, or M integers >= 1 (a sequence or a CPU integer tensor): distorted images of DIFFERENT patch counts, the
+                        tensors concatenated or lists of per-image tensors, as forward_group(lengths=...).  q[m] has the bits of
+                        forward_cached on image m alone against the same rows."""
         self._group_guard("forward_cached")
         if not isinstance(ref, ReferenceFeatures):
             raise TypeError("forward_cached takes the ReferenceFeatures of encode_reference as its first argument")
-        G, M = len(ref), int(patches_dist.shape[0])
+        lens = _lengths(lengths, "lengths") if lengths is not None else None
+        G, M = len(ref), (len(lens) if lens is not None else int(patches_dist.shape[0]))
         idx = _ref_index(ref_index, G, M)
         why = self._stale(ref)
         if why:
             raise StaleReferenceError(f"forward_cached: the reference features are stale: {why}; encode_reference again")
-        device, _, N, tokens_in, (pt,), (pp,), (ps,) = self._inputs((patches_dist,), (pos_dist,), (scales_dist,))
+        if lens is not None:
+            device, pt, pp, ps = self._ragged_inputs("forward_cached", patches_dist, pos_dist, scales_dist, lens)
+        else:
+            device, _, N, tokens_in, (pt,), (pp,), (ps,) = self._inputs((patches_dist,), (pos_dist,), (scales_dist,))
         rows = ref.rows
         if rows.device != device or rows.dtype != torch.float32 or tuple(rows.shape) != (G, self.spec.hidden_size) or not rows.is_contiguous():
             raise ValueError(f"forward_cached: ref.rows must be a contiguous fp32 (G, {self.spec.hidden_size}) tensor on {device}")
@@ -832,8 +932,13 @@ class VTAMIQ(nn.Module):
             q = torch.empty(M, device=device, dtype=torch.float32)
             arr = (C.c_int32 * M)(*idx)
             stream = torch.cuda.current_stream(device).cuda_stream
-            self._launch_checked(device, lambda lib: self._check(lib.vtq_forward_cached(
-                self._engine, rows.data_ptr(), G, pt.data_ptr(), int(tokens_in), pp.data_ptr(), _ptr(ps), M, N, arr, q.data_ptr(), stream)))
+            if lens is not None:
+                n_arr = (C.c_int32 * M)(*lens)
+                self._launch_checked(device, lambda lib: self._check(lib.vtq_forward_cached_varlen(
+                    self._engine, rows.data_ptr(), G, pt.data_ptr(), pp.data_ptr(), _ptr(ps), M, n_arr, arr, q.data_ptr(), stream)))
+            else:
+                self._launch_checked(device, lambda lib: self._check(lib.vtq_forward_cached(
+                    self._engine, rows.data_ptr(), G, pt.data_ptr(), int(tokens_in), pp.data_ptr(), _ptr(ps), M, N, arr, q.data_ptr(), stream)))
         if self.engine_precision != ref.precision:
             raise StaleReferenceError(f"forward_cached: an operand left the fp16 range and the model now runs {self.engine_precision!r}; the cached "
                                       f"rows are {ref.precision!r} rows: encode_reference again")
