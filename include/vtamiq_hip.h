@@ -155,16 +155,18 @@ int  vtq_forward_tokens(vtq_handle h, const float* feats_ref, const float* feats
  * vtq_workspace_bytes and every other entry are unchanged.  The scores still come from the CLS-only last layer; its Q and K rows are
  * projected in addition, because the probabilities vtq_forward_vit reports are those of the 16-bit Q / K planes, which the tail never forms.
  * Refused with vtq_last_error text and no launch: a NULL handle or rollout_out; B or N < 1; the fp8 experiment's handle; a set token trace
- * buffer (vtq_set_token_trace); a set vtq_debug_stop_after.  The varlen, group, cached and pairwise entries have no rollout form, and
- * neither have the variable-length one-to-many entries (vtq_forward_group_varlen ...), which take 5-D patches only: pre-embedded ragged input
- * and a ragged rollout are not offered. */
+ * buffer (vtq_set_token_trace); a set vtq_debug_stop_after.  vtq_forward_pairwise has no rollout form; the varlen, group and cached entries
+ * have one each ("rollout forms" below, behind the one-to-many entries); the ragged rollouts (vtq_forward_varlen_rollout,
+ * vtq_forward_group_varlen_rollout ...) take 5-D patches only: pre-embedded ragged input is not offered. */
 int  vtq_forward_rollout(vtq_handle h, const float* patches_ref, const float* patches_dist, const float* pos_ref, const float* pos_dist,
                          const float* scales_ref, const float* scales_dist, int32_t B, int32_t N, float* q_out, float* rollout_out,
                          float* last_attention_out, void* stream);
 int  vtq_forward_rollout_tokens(vtq_handle h, const float* feats_ref, const float* feats_dist, const float* pos_ref, const float* pos_dist,
                                 const float* scales_ref, const float* scales_dist, int32_t B, int32_t N, float* q_out, float* rollout_out,
                                 float* last_attention_out, void* stream);
-/* Bytes of the extra device workspace a vtq_forward_rollout call of (B pairs, N patches) holds beside vtq_workspace_bytes(h, B, N). */
+/* Bytes of the extra device workspace a vtq_forward_rollout call of (B pairs, N patches) holds beside vtq_workspace_bytes(h, B, N).  The
+ * rollout forms of the other entries hold vtq_rollout_workspace_bytes(h, ceil(sequences / 2), N), the variable-length ones with N = the
+ * largest count of any image -- an upper bound for every buffer of such a call, as vtq_workspace_bytes is for the base entry. */
 size_t vtq_rollout_workspace_bytes(vtq_handle h, int32_t B, int32_t N);
 
 /* Pairwise items (train.predict, train.py:281-301: two model calls sharing the reference image): patches/pos/scales are HOST
@@ -263,6 +265,53 @@ int  vtq_encode_reference_varlen(vtq_handle h, const float* patches, const float
                                  float* ref_rows, void* stream);
 int  vtq_forward_cached_varlen(vtq_handle h, const float* ref_rows, int32_t G, const float* patches, const float* pos, const float* scales,
                                int32_t M, const int32_t* n_patches, const int32_t* ref_index, float* q_out, void* stream);
+
+/* ---- rollout forms of the variable-length and one-to-many entries ---------------------------------------------------------------------------
+ * Each is its base entry -- the same arguments, the same q_out / ref_rows bits, the same refusals -- plus the rollout of vtq_forward_rollout
+ * for every sequence the call ENCODES, in the same launch sequence: `float* rollout_out, float* last_attention_out` stand before `stream`.
+ * A sequence's maps depend on its own image alone: they have the bits vtq_forward_rollout gives for a single pair (B = 1) holding that image
+ * with the same patch count, on the reference side for a reference and on the distorted side for a distorted image.  A NaN image makes
+ * exactly its own maps NaN.  h = num_heads, S = T + N; S_j = T + the count of sequence j.
+ *   uniform (vtq_forward_group_rollout, _tokens):  rollout_out : fp32, EXACTLY (G + M) * S floats ([G + M][S], the references first)
+ *                                                  last_attention_out : fp32, EXACTLY (G + M) * h * S floats ([G + M][h][S]); may be NULL
+ *   vtq_encode_reference_rollout:                  rollout_out : fp32, EXACTLY G * S floats ([G][S])
+ *                                                  last_attention_out : fp32, EXACTLY G * h * S floats ([G][h][S]); may be NULL
+ *   vtq_forward_cached_rollout:                    rollout_out : fp32, EXACTLY M * S floats ([M][S])
+ *                                                  last_attention_out : fp32, EXACTLY M * h * S floats ([M][h][S]); may be NULL
+ *                                                  (the cached references are not encoded: their maps come from vtq_encode_reference_rollout)
+ *   variable-length (vtq_forward_varlen_rollout, vtq_forward_group_varlen_rollout, vtq_encode_reference_varlen_rollout,
+ *   vtq_forward_cached_varlen_rollout), with R = the sum of S_j over the call's sequences in call order -- vtq_forward_varlen_rollout: all B
+ *   reference sequences, then all B distorted ones; the group form: the G references, then the M distorted images:
+ *                                                  rollout_out : fp32, EXACTLY R floats: sequence j's S_j values at the sum of S_i, i < j
+ *                                                  last_attention_out : fp32, EXACTLY h * R floats: sequence j's [h][S_j] block at h times
+ *                                                  that offset; may be NULL
+ * Both are written by the call's last launches on `stream` (no copy); nothing outside the stated extents is written.  Extra workspace: see
+ * vtq_rollout_workspace_bytes.  Refused with vtq_last_error text that names the entry, and no launch: everything the base entry refuses (bad
+ * counts and ref_index, the fp8 experiment's handle, a set token trace buffer ...); a NULL rollout_out (with the batch description, ahead of
+ * the handle); a set vtq_debug_stop_after; more than 65535 sequences. */
+int  vtq_forward_varlen_rollout(vtq_handle h, const float* patches_ref, const float* patches_dist, const float* pos_ref, const float* pos_dist,
+                                const float* scales_ref, const float* scales_dist, int32_t B, const int32_t* n_patches, float* q_out,
+                                float* rollout_out, float* last_attention_out, void* stream);
+int  vtq_forward_group_rollout(vtq_handle h, const float* patches_ref, const float* patches_dist, const float* pos_ref, const float* pos_dist,
+                               const float* scales_ref, const float* scales_dist, int32_t G, int32_t M, int32_t N, const int32_t* ref_index,
+                               float* q_out, float* rollout_out, float* last_attention_out, void* stream);
+int  vtq_forward_group_rollout_tokens(vtq_handle h, const float* feats_ref, const float* feats_dist, const float* pos_ref, const float* pos_dist,
+                                      const float* scales_ref, const float* scales_dist, int32_t G, int32_t M, int32_t N, const int32_t* ref_index,
+                                      float* q_out, float* rollout_out, float* last_attention_out, void* stream);
+int  vtq_encode_reference_rollout(vtq_handle h, const float* in, int32_t tokens_in, const float* pos, const float* scales, int32_t G, int32_t N,
+                                  float* ref_rows, float* rollout_out, float* last_attention_out, void* stream);
+int  vtq_forward_cached_rollout(vtq_handle h, const float* ref_rows, int32_t G, const float* in, int32_t tokens_in, const float* pos,
+                                const float* scales, int32_t M, int32_t N, const int32_t* ref_index, float* q_out, float* rollout_out,
+                                float* last_attention_out, void* stream);
+int  vtq_forward_group_varlen_rollout(vtq_handle h, const float* patches_ref, const float* patches_dist, const float* pos_ref, const float* pos_dist,
+                                      const float* scales_ref, const float* scales_dist, int32_t G, int32_t M, const int32_t* n_ref,
+                                      const int32_t* n_dist, const int32_t* ref_index, float* q_out, float* rollout_out, float* last_attention_out,
+                                      void* stream);
+int  vtq_encode_reference_varlen_rollout(vtq_handle h, const float* patches, const float* pos, const float* scales, int32_t G,
+                                         const int32_t* n_patches, float* ref_rows, float* rollout_out, float* last_attention_out, void* stream);
+int  vtq_forward_cached_varlen_rollout(vtq_handle h, const float* ref_rows, int32_t G, const float* patches, const float* pos, const float* scales,
+                                       int32_t M, const int32_t* n_patches, const int32_t* ref_index, float* q_out, float* rollout_out,
+                                       float* last_attention_out, void* stream);
 
 /* Input check.  The reference raises (IndexError / device assert) when a position lies outside [0, 1)
  * (transformer.py:417-421); vtq_forward clamps such an index into the table instead of gathering out of bounds and records it.

@@ -75,6 +75,20 @@ SIGNATURES = {
     "vtq_encode_reference_varlen": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]),
     "vtq_forward_cached_varlen": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32),
                                             C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]),
+    # the rollout forms: the base entry's arguments with rollout_out, last_attention_out before the stream
+    "vtq_forward_varlen_rollout": (C.c_int, [C.c_void_p] + [C.c_void_p] * 6 + [C.c_int32, C.POINTER(C.c_int32)] + [C.c_void_p] * 4),
+    "vtq_forward_group_rollout": (C.c_int, [C.c_void_p] + [C.c_void_p] * 6 + [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)] + [C.c_void_p] * 4),
+    "vtq_forward_group_rollout_tokens": (C.c_int, [C.c_void_p] + [C.c_void_p] * 6 + [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]
+                                         + [C.c_void_p] * 4),
+    "vtq_encode_reference_rollout": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 4),
+    "vtq_forward_cached_rollout": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                             C.POINTER(C.c_int32)] + [C.c_void_p] * 4),
+    "vtq_forward_group_varlen_rollout": (C.c_int, [C.c_void_p] + [C.c_void_p] * 6 + [C.c_int32, C.c_int32, C.POINTER(C.c_int32),
+                                                   C.POINTER(C.c_int32), C.POINTER(C.c_int32)] + [C.c_void_p] * 4),
+    "vtq_encode_reference_varlen_rollout": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
+                                            + [C.c_void_p] * 4),
+    "vtq_forward_cached_varlen_rollout": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                                    C.POINTER(C.c_int32), C.POINTER(C.c_int32)] + [C.c_void_p] * 4),
     "vtq_set_token_trace": (C.c_int, [C.c_void_p, C.c_void_p]),
     "vtq_set_iqa_token": (C.c_int, [C.c_void_p, C.c_int32]),
     "vtq_debug_stop_after": (C.c_int, [C.c_void_p, C.c_int32]),
@@ -124,10 +138,12 @@ SIGNATURES = {
                                         C.c_int32, C.c_void_p]),
 }
 
-# include/vtamiq_hip_rollout.h: the unit entry of the attention-rollout step (the scoring entries vtq_forward_rollout* are in SIGNATURES)
+# include/vtamiq_hip_rollout.h: the unit entries of the attention-rollout step (the scoring entries vtq_*_rollout* are in SIGNATURES)
 ROLLOUT_SIGNATURES = {
     "vtq_k_rollout_step": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                      C.c_int32, C.c_int32, C.c_void_p]),
+    "vtq_vl_rollout_step": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_int32,
+                                      C.c_int32, C.c_int32, C.c_void_p]),
 }
 
 # the fp8 experiment (include/vtamiq_hip_fp8.h): exported only by a library built with -DVTQ_WITH_FP8 (python -m vtamiq_amd.build --fp8 ->

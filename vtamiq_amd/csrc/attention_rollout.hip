@@ -15,6 +15,11 @@
 // sequences, the CU count or arrival order (the rule cls_tail.hip states for itself), so a pair's rollout does not depend on its batch.
 // Query rows and keys >= S are masked (weight 0 / not stored); K and Q rows are clamped to row S - 1 of the sequence, so nothing
 // outside the sequence's own rows [seq * S_pad, seq * S_pad + S) is read, and nothing outside [0, S) of a partial is written.
+//
+// Two decodes in front of ONE body (rollout_step_block): the uniform kernels, and rollout_step_varlen_kernel / rollout_combine_varlen_kernel
+// for sequences of different lengths packed back to back (vtq_forward_varlen's layout), which look their work item up in the call's attention
+// block table and address r, the result and the partials like the rows.  The body sees (first row, S, block, head) and two pointers either way,
+// so a sequence's bits are those of the uniform kernel at S = S_pad = S_j, whatever else the launch holds.
 #include "dev_common.h"
 #include "kernels.h"
 
@@ -24,10 +29,12 @@ namespace {
 constexpr int kRKT = 64;                   // keys per LDS tile (two 32-key MFMA blocks)
 constexpr int kRTB = kRKT * 128;           // bytes of one tile plane: 64 keys x 64 dims x 2 B
 
-// r == NULL: r = e_token (the first step of a walk: the last layer)
+// THE step of one workgroup: query block qb (128 rows) of head `head` of the sequence that is the S rows from row0.  r: the sequence's own
+// S weights (NULL: e_token, the first step of a walk: the last layer); pout: the block's S partial column sums.  Both kernels below
+// decode their work item and call this, so a sequence's arithmetic -- nt, nwv, every summation order -- is a function of S alone in both.
 template <typename T, int NSPLIT>
-__global__ __launch_bounds__(256) void rollout_step_kernel(const T* __restrict__ qkv, int64_t plane, const float* __restrict__ r,
-                                                           float* __restrict__ part, int S, int S_pad, int H, int q_log2, int token) {
+__device__ __forceinline__ void rollout_step_block(const T* __restrict__ qkv, int64_t plane, int64_t row0, int S, int qb, int head,
+                                                   const float* __restrict__ r, float* __restrict__ pout, int H, int q_log2, int token) {
     typedef typename Vec<T>::x8 tx8;
     constexpr int NPL = (NSPLIT == 1) ? 1 : 2;
     __shared__ __attribute__((aligned(16))) char sk[NPL * kRTB];
@@ -35,10 +42,7 @@ __global__ __launch_bounds__(256) void rollout_step_kernel(const T* __restrict__
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int c = lane & 31, hh = lane >> 5;
-    const int nqb = (S + 127) / 128, nh = H / 64;
-    const int qb = blockIdx.x % nqb, head = (blockIdx.x / nqb) % nh, seq = blockIdx.x / (nqb * nh);
     const int ld = 3 * H;
-    const int64_t row0 = (int64_t)seq * S_pad;
     const int qw = qb * 128 + wave * 32;                     // first query row of this wave
     const bool wave_active = qw < S;
     const int nwv = min(4, (S - qb * 128 + 31) / 32);        // waves of this block with a row < S
@@ -79,7 +83,6 @@ __global__ __launch_bounds__(256) void rollout_step_kernel(const T* __restrict__
     float m[16], l[16];
 #pragma unroll
     for (int j = 0; j < 16; ++j) { m[j] = -INFINITY; l[j] = 0.f; }
-    float* pout = part + (((int64_t)seq * nh + head) * nqb + qb) * S;
 
     load_tile(0);
     for (int it = 0; it < 2 * nt; ++it) {
@@ -141,7 +144,7 @@ __global__ __launch_bounds__(256) void rollout_step_kernel(const T* __restrict__
                 }
                 const int q = qw + (j & 3) + 8 * (j >> 2) + 4 * hh;
                 float rv = 0.f;                                  // rows >= S carry no weight
-                if (q < S) rv = r ? r[(int64_t)seq * S + q] : (q == token ? 1.0f : 0.0f);
+                if (q < S) rv = r ? r[q] : (q == token ? 1.0f : 0.0f);
                 l[j] = rv * (1.0f / l[j]);
             }
         }
@@ -156,23 +159,69 @@ __global__ __launch_bounds__(256) void rollout_step_kernel(const T* __restrict__
     }
 }
 
-// out[seq][j] = 1/2 r[seq][j] + 1/(2 nh) sum_head sum_block part[seq][head][block][j], heads then blocks ascending; heads_out (may be NULL):
-// [seq][head][j] = sum_block part[seq][head][block][j] (with r = e_token that is row `token` of the head's probabilities).  r == NULL: e_token.
-__global__ __launch_bounds__(256) void rollout_combine_kernel(const float* __restrict__ part, const float* __restrict__ r, int token,
-                                                              float* __restrict__ out, float* __restrict__ heads_out, int S, int nh, int nqb) {
-    const int j = blockIdx.x * 256 + threadIdx.x, seq = blockIdx.y;
-    if (j >= S) return;
-    const float* p = part + (int64_t)seq * nh * nqb * S + j;
+// Uniform sequences: work item blockIdx.x = (sequence, head, query block) of nseq sequences of S rows at pitch S_pad; r: [nseq][S],
+// part: [sequence][head][block][S]
+template <typename T, int NSPLIT>
+__global__ __launch_bounds__(256) void rollout_step_kernel(const T* __restrict__ qkv, int64_t plane, const float* __restrict__ r,
+                                                           float* __restrict__ part, int S, int S_pad, int H, int q_log2, int token) {
+    const int nqb = (S + 127) / 128, nh = H / 64;
+    const int qb = blockIdx.x % nqb, head = (blockIdx.x / nqb) % nh, seq = blockIdx.x / (nqb * nh);
+    rollout_step_block<T, NSPLIT>(qkv, plane, (int64_t)seq * S_pad, S, qb, head, r ? r + (int64_t)seq * S : nullptr,
+                                  part + (((int64_t)seq * nh + head) * nqb + qb) * S, H, q_log2, token);
+}
+
+// Sequences of different lengths packed back to back (the layout vtq_forward_varlen leaves in the QKV planes): work item blockIdx.x is entry
+// blocks[blockIdx.x] = {first row, S_j, query block, head} of attention_varlen_blocks().  r is packed like the rows (sequence j's S_j
+// weights at its first row), part is [head][block < nqb_max][R] with R the total row count: a (head, block) plane is packed like the rows
+// too, so a sequence's partials lie at its first row in every plane and need no per-sequence offset table.
+template <typename T, int NSPLIT>
+__global__ __launch_bounds__(256) void rollout_step_varlen_kernel(const T* __restrict__ qkv, int64_t plane, const float* __restrict__ r,
+                                                                  float* __restrict__ part, const int4* __restrict__ blocks, int nqb_max,
+                                                                  int64_t R, int H, int q_log2, int token) {
+    const int4 blk = blocks[blockIdx.x];
+    const int64_t row0 = blk.x;
+    rollout_step_block<T, NSPLIT>(qkv, plane, row0, blk.y, blk.z, blk.w, r ? r + row0 : nullptr,
+                                  part + ((int64_t)blk.w * nqb_max + blk.z) * R + row0, H, q_log2, token);
+}
+
+// Element j of one sequence: out = 1/2 r + 1/(2 nh) sum_head sum_block p[head * hstride + block * bstride], heads then blocks ascending;
+// heads_out (may be NULL): [head * S] = sum_block (with r = e_token that is row `token` of the head's probabilities).  rv: r[j] or e_token[j]
+__device__ __forceinline__ void rollout_combine_one(const float* __restrict__ p, int64_t hstride, int64_t bstride, int nh, int nqb, float rv,
+                                                    float* __restrict__ out, float* __restrict__ heads_out, int S) {
     float tot = 0.f;
     for (int h = 0; h < nh; ++h) {
         float hs = 0.f;
 #pragma unroll 4
-        for (int b = 0; b < nqb; ++b) hs += p[((int64_t)h * nqb + b) * S];
-        if (heads_out) heads_out[((int64_t)seq * nh + h) * S + j] = hs;
+        for (int b = 0; b < nqb; ++b) hs += p[h * hstride + b * bstride];
+        if (heads_out) heads_out[(int64_t)h * S] = hs;
         tot += hs;
     }
+    *out = 0.5f * rv + (0.5f / nh) * tot;
+}
+
+// out[seq][j] = 1/2 r[seq][j] + 1/(2 nh) sum_head sum_block part[seq][head][block][j]; heads_out (may be NULL): [seq][head][j].  r == NULL: e_token.
+__global__ __launch_bounds__(256) void rollout_combine_kernel(const float* __restrict__ part, const float* __restrict__ r, int token,
+                                                              float* __restrict__ out, float* __restrict__ heads_out, int S, int nh, int nqb) {
+    const int j = blockIdx.x * 256 + threadIdx.x, seq = blockIdx.y;
+    if (j >= S) return;
     const float rv = r ? r[(int64_t)seq * S + j] : (j == token ? 1.0f : 0.0f);
-    out[(int64_t)seq * S + j] = 0.5f * rv + (0.5f / nh) * tot;
+    rollout_combine_one(part + (int64_t)seq * nh * nqb * S + j, (int64_t)nqb * S, S, nh, nqb, rv, out + (int64_t)seq * S + j,
+                        heads_out ? heads_out + (int64_t)seq * nh * S + j : nullptr, S);
+}
+
+// The same per (sequence, 256-key chunk) of packed sequences: row0 / len = the call's tables.  r and out packed like the rows; heads_out:
+// sequence j's [nh][S_j] block at nh * row0[j]; blocks b < ceil(S_j / 128) of the nqb_max planes per head are the sequence's
+__global__ __launch_bounds__(256) void rollout_combine_varlen_kernel(const float* __restrict__ part, const float* __restrict__ r, int token,
+                                                                     float* __restrict__ out, float* __restrict__ heads_out,
+                                                                     const int* __restrict__ row0, const int* __restrict__ len, int nh,
+                                                                     int nqb_max, int64_t R) {
+    const int j = blockIdx.x * 256 + threadIdx.x, seq = blockIdx.y;
+    const int S = len[seq];
+    if (j >= S) return;
+    const int64_t r0 = row0[seq];
+    const float rv = r ? r[r0 + j] : (j == token ? 1.0f : 0.0f);
+    rollout_combine_one(part + r0 + j, (int64_t)nqb_max * R, R, nh, (S + 127) / 128, rv, out + r0 + j,
+                        heads_out ? heads_out + nh * r0 + j : nullptr, S);
 }
 
 }  // namespace
@@ -197,6 +246,30 @@ hipError_t launch_rollout_step(const void* qkv, int64_t plane, const float* r, i
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(rollout_combine_kernel, dim3((S + 255) / 256, nseq), dim3(256), 0, s, (const float*)part, r, token, out, heads_out, S, nh, nqb);
+    return hipGetLastError();
+}
+
+hipError_t launch_rollout_step_varlen(const void* qkv, int64_t plane, const float* r, int token, float* part, float* out, float* heads_out,
+                                      const int* blocks, int nblocks, const int* row0, const int* len, int nseq, int S_max, int64_t R, int H,
+                                      Num num, hipStream_t s, bool q_log2) {
+    if (nseq < 1 || nseq > 65535 || S_max < 1 || R < nseq || nblocks < 1 || !blocks || !row0 || !len || H % 64 || H < 64 ||
+        (num.terms != 1 && num.terms != 3) || num.f16 > 1 || !part || !out || (!r && token < 0))
+        return hipErrorInvalidValue;
+    const int nh = H / 64, nqb_max = (S_max + 127) / 128;
+    const dim3 g((unsigned)nblocks), b(256);
+    const int ql = q_log2 ? 1 : 0;
+    const int4* bl = (const int4*)blocks;
+    if (num.f16) {
+        if (num.terms == 3) hipLaunchKernelGGL((rollout_step_varlen_kernel<f16, 3>), g, b, 0, s, (const f16*)qkv, plane, r, part, bl, nqb_max, R, H, ql, token);
+        else hipLaunchKernelGGL((rollout_step_varlen_kernel<f16, 1>), g, b, 0, s, (const f16*)qkv, plane, r, part, bl, nqb_max, R, H, ql, token);
+    } else {
+        if (num.terms == 3) hipLaunchKernelGGL((rollout_step_varlen_kernel<bf16, 3>), g, b, 0, s, (const bf16*)qkv, plane, r, part, bl, nqb_max, R, H, ql, token);
+        else hipLaunchKernelGGL((rollout_step_varlen_kernel<bf16, 1>), g, b, 0, s, (const bf16*)qkv, plane, r, part, bl, nqb_max, R, H, ql, token);
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(rollout_combine_varlen_kernel, dim3((S_max + 255) / 256, nseq), dim3(256), 0, s, (const float*)part, r, token, out, heads_out,
+                       row0, len, nh, nqb_max, R);
     return hipGetLastError();
 }
 

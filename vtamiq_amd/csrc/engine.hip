@@ -1066,20 +1066,28 @@ int vtq_profile_collect(vtq_handle e, double* ms_sum, int64_t* launches) {
 // Attention rollout of the consumed token behind a forward that kept every layer's Q / K planes (e->ro_qkv): one step per layer, last to
 // first, every launch on s.  The walk starts at r = e_token, so the first step's per-head sums are the last layer's attention row of the
 // token: last_attention.  The row vector ping-pongs between the two workspace vectors; the LAST step writes the caller's rollout_out itself
-// ([nseq][S] is its layout), so there is no copy.
-static int run_rollout(vtq_engine* e, const Call& c, const Geometry& g, hipStream_t s) {
+// ([nseq][S] is its layout), so there is no copy.  A variable-length call (vl.blocks) takes the table-driven step on the call's own tables: the
+// vectors, the partials and both outputs are then packed like the rows (launch_rollout_step_varlen) -- g.sm.pitch is the call's row count --
+// and fit what reserve_rollout(ceil(nseq / 2), maxN) holds: ro_r >= nseq * S_max >= rows, ro_part = that * heads * ceil(S_max / 128).
+static int run_rollout(vtq_engine* e, const Call& c, const Geometry& g, hipStream_t s, const VarLen& vl) {
     const int H = e->H, L = e->cfg.num_layers, t = e->iqa_token;
     const bool ql = e->att.terms == 3;
     auto dst = [&](int op) { return op == L - 1 ? c.rollout_out : e->ro_r[op & 1]; };      // op 0 = the last layer ... op L - 1 = layer 0
-    for (int op = 0; op < L; ++op)
-        HIP_TRY(launch_rollout_step(e->ro_qkv[L - 1 - op], e->ro_plane, op ? dst(op - 1) : nullptr, t, e->ro_part, dst(op),
-                                    op ? nullptr : c.last_attention_out, g.nseq, g.S, g.S_pad, H, e->att, s, ql));
+    for (int op = 0; op < L; ++op) {
+        const float* r = op ? dst(op - 1) : nullptr;
+        float* last = op ? nullptr : c.last_attention_out;
+        if (vl.blocks)
+            HIP_TRY(launch_rollout_step_varlen(e->ro_qkv[L - 1 - op], e->ro_plane, r, t, e->ro_part, dst(op), last, vl.blocks, vl.nblocks, vl.row0,
+                                               vl.len, g.nseq, g.S, g.sm.pitch, H, e->att, s, ql));
+        else
+            HIP_TRY(launch_rollout_step(e->ro_qkv[L - 1 - op], e->ro_plane, r, t, e->ro_part, dst(op), last, g.nseq, g.S, g.S_pad, H, e->att, s, ql));
+    }
     return 0;
 }
 
 // The last step of a call: the consumed token's rows of the encoded sequences -> what the entry returns.
 //   nimg = 1, REF_PAIRS (vtq_forward_vit): no head -- c.out receives encoder_norm of c.rows rows per image
-//   REF_ENCODE: the rows go to the caller's cache, no head
+//   REF_ENCODE: the rows go to the caller's cache, no head (and the rollout of its G sequences where asked for)
 //   otherwise: the difference of each pair (nimg = 2: q_out[B]; nimg = 3: q_out[2B] = (ref, dist1) then (ref, dist2) with ref encoded once;
 //   REF_GROUP / REF_CACHED: q_out[B], distorted image m against reference ref_index[m]), the head, and the rollout where asked for
 static int finish(vtq_engine* e, const Call& c, const Geometry& g, hipStream_t s, bool prune, const VarLen& vl) {
@@ -1102,7 +1110,7 @@ static int finish(vtq_engine* e, const Call& c, const Geometry& g, hipStream_t s
         const int* row0 = prune ? nullptr : vl.row0;
         if (mode == REF_ENCODE) {
             HIP_TRY(launch_export_rows(rows, stride, c.rg.rows, B, H, s, e->err_flag, row0));
-            return 0;
+            return c.rollout_out ? run_rollout(e, c, g, s, vl) : 0;
         }
         if (mode == REF_GROUP)
             HIP_TRY(launch_group_diff(rows, stride, rows + (row0 ? 0 : B0 * stride), stride, vl.ref_index, B, e->encw, e->encb, gamma, d, H, hp, s, e->err_flag,
@@ -1113,7 +1121,7 @@ static int finish(vtq_engine* e, const Call& c, const Geometry& g, hipStream_t s
         else HIP_TRY(launch_final_diff(e->x + (int64_t)e->iqa_token * H, e->encw, e->encb, gamma, d, B, ndist, g.sm, H, hp, s, e->err_flag, vl.row0));
         if (run_head(e, d, HB, c.q_out, s, true)) return 1;
     }
-    if (c.rollout_out && run_rollout(e, c, g, s)) return 1;
+    if (c.rollout_out && run_rollout(e, c, g, s, vl)) return 1;
     if (c.calibrating) e->fp8_calibrated = true;
     return 0;
 }
@@ -1130,7 +1138,7 @@ static int forward(vtq_engine* e, Call c, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     // ---- workspace: capacity is kept in units of sequence pairs; varlen reserves an upper bound, the batch is no larger than B pairs of maxN
     if (reserve(e, (nseq + 1) / 2, varlen ? c.maxN : c.N)) return 1;
-    if (rollout && reserve_rollout(e, (nseq + 1) / 2, c.N)) return 1;
+    if (rollout && reserve_rollout(e, (nseq + 1) / 2, varlen ? c.maxN : c.N)) return 1;
     // fp8 mode: the first forward of an engine calibrates the activation scales on its own batch (see kSPatch); it synchronises
     // the stream once per quantisation point and returns this batch's scores computed with the final scales
     c.calibrating = e->fp8 && !e->fp8_static && !e->fp8_calibrated && e->dbg_stop < 0;
@@ -1161,11 +1169,11 @@ static int forward(vtq_engine* e, Call c, void* stream) {
     }
     {   // tile schedules of this geometry's GEMM shapes: built and uploaded here (first forward of a tile grid only; DESIGN.md section 4
         // has what bounds the cache), not inside a launch.  (M, 2H, H) is the rollout's query | key projection of the last layer; the
-        // uniform entries prepare it on every call, varlen -- which has no rollout -- never
+        // uniform entries prepare it on every call, a variable-length call exactly when it asks for a rollout
         const int wpl = e->wpl, M = (int)g.M_pad;
         HIP_TRY(gemm_prepare((int)g.P_pad, H, (int)e->PDp, wpl, s));
         HIP_TRY(gemm_prepare(M, 3 * H, H, wpl, s));
-        if (!varlen) HIP_TRY(gemm_prepare(M, 2 * H, H, wpl, s));
+        if (!varlen || rollout) HIP_TRY(gemm_prepare(M, 2 * H, H, wpl, s));
         HIP_TRY(gemm_prepare(M, H, H, wpl, s));
         HIP_TRY(gemm_prepare(M, e->Mdim, H, wpl, s));
         HIP_TRY(gemm_prepare(M, H, e->Mdim, wpl, s));
@@ -1208,8 +1216,8 @@ static int forward(vtq_engine* e, Call c, void* stream) {
     // them reaches an output, for zeros and for NaNs alike).
     for (int pl = 0; pl < e->apl; ++pl)
         HIP_TRY(hipMemsetAsync((char*)e->big + ((size_t)pl * e->big_plane + (size_t)g.M_pad * 3 * H) * 2, 0, (size_t)128 * 3 * H * 2, s));
-    // (vtq_forward_rollout: the same rows of every retained QKV buffer -- no later stage of this forward writes them, and an earlier,
-    // larger call may have)
+    // (a rollout call: the same rows of every retained QKV buffer -- no later stage of this forward writes them, and an earlier,
+    // larger call may have.  g is this call's geometry, so a variable-length call clears behind ITS M_pad)
     if (rollout)
         for (void* q : e->ro_qkv)
             for (int pl = 0; pl < e->apl; ++pl)
@@ -1346,6 +1354,22 @@ int vtq_forward_rollout_tokens(vtq_handle e, const float* feats_ref, const float
                            rollout_out, last_attention_out, stream);
 }
 
+// The rollout form of the variable-length and one-to-many entries: the caller's two outputs (last_attention may be NULL); the base entries
+// pass no RolloutOut.  What a rollout form refuses beyond its base entry, with no launch: a NULL rollout_out -- checked with the batch
+// description, ahead of the handle -- and, with the handle, vtq_debug_stop_after and more sequences than the combine launch's grid takes.
+// (The fp8 engine and a token trace are refused by every one of these entries anyway.)
+struct RolloutOut { float *rollout, *last_attention; };
+static int check_rollout_out(const char* who, const RolloutOut* ro) { return ro && !ro->rollout ? fail("%s: null rollout_out", who) : 0; }
+static int check_rollout_handle(const char* who, vtq_handle e, const RolloutOut* ro, int64_t nseq) {
+    if (!ro) return 0;
+    if (e->dbg_stop >= 0) return fail("%s: vtq_debug_stop_after is set", who);
+    if (nseq > 65535) return fail("%s: %lld sequences (a rollout call takes at most 65535)", who, (long long)nseq);
+    return 0;
+}
+static void set_rollout(Call& c, const RolloutOut* ro) {
+    if (ro) { c.rollout_out = ro->rollout; c.last_attention_out = ro->last_attention; }
+}
+
 size_t vtq_rollout_workspace_bytes(vtq_handle e, int32_t B, int32_t N) { return (e && B >= 1 && N >= 1) ? ws_bytes(rollout_workspace(e, B, N)) : 0; }
 
 // The variable-length entries (n_img set, every count checked >= 1): what they share behind their own argument checks -- the sums and the
@@ -1370,21 +1394,40 @@ static int forward_ragged(vtq_handle e, Call c, void* stream) {
 // B pairs of different patch counts through one launch sequence (include/vtamiq_hip.h).  Layout: sequences packed back to back at their
 // own length, all reference sequences, then all distorted ones; the packed patch rows likewise (image, pair, patch).  Every kernel is
 // row- or sequence-independent and the GEMMs are bitwise independent of M, so pair b's score has the bits of a B = 1 call on pair b.
+static int forward_varlen(const char* who, vtq_handle e, const float* patches_ref, const float* patches_dist, const float* pos_ref,
+                          const float* pos_dist, const float* scales_ref, const float* scales_dist, int32_t B, const int32_t* n_patches, float* q_out,
+                          const RolloutOut* ro, void* stream) {
+    // the batch description first (it needs no handle), then the handle, then what the handle decides
+    if (!n_patches) return fail("%s: null n_patches", who);
+    if (B < 1) return fail("%s: B=%d", who, (int)B);
+    for (int b = 0; b < B; ++b)
+        if (n_patches[b] < 1) return fail("%s: n_patches[%d] = %d (every pair needs at least one patch)", who, b, (int)n_patches[b]);
+    if (check_rollout_out(who, ro)) return 1;
+    if (!e) return fail("%s: null handle", who);
+    if (e->fp8) return fail("%s: not available for the fp8 experiment's engine", who);
+    if (!patches_ref || !patches_dist || !pos_ref || !pos_dist) return fail("%s: null tensor", who);
+    if (!q_out) return fail("%s: null output", who);
+    if (e->trace) return fail("%s: a token trace buffer is set (vtq_set_token_trace): the trace layout is per uniform batch", who);
+    if (check_rollout_handle(who, e, ro, 2 * (int64_t)B)) return 1;
+    Call c = call_pair(who, false, patches_ref, patches_dist, pos_ref, pos_dist, scales_ref, scales_dist, B, 0, q_out);
+    c.n_img[0] = c.n_img[1] = n_patches;
+    set_rollout(c, ro);
+    return forward_ragged(e, c, stream);
+}
+
 int vtq_forward_varlen(vtq_handle e, const float* patches_ref, const float* patches_dist, const float* pos_ref, const float* pos_dist,
                        const float* scales_ref, const float* scales_dist, int32_t B, const int32_t* n_patches, float* q_out, void* stream) {
-    // the batch description first (it needs no handle), then the handle, then what the handle decides
-    if (!n_patches) return fail("vtq_forward_varlen: null n_patches");
-    if (B < 1) return fail("vtq_forward_varlen: B=%d", (int)B);
-    for (int b = 0; b < B; ++b)
-        if (n_patches[b] < 1) return fail("vtq_forward_varlen: n_patches[%d] = %d (every pair needs at least one patch)", b, (int)n_patches[b]);
-    if (!e) return fail("vtq_forward_varlen: null handle");
-    if (e->fp8) return fail("vtq_forward_varlen: not available for the fp8 experiment's engine");
-    if (!patches_ref || !patches_dist || !pos_ref || !pos_dist) return fail("vtq_forward_varlen: null tensor");
-    if (!q_out) return fail("vtq_forward_varlen: null output");
-    if (e->trace) return fail("vtq_forward_varlen: a token trace buffer is set (vtq_set_token_trace): the trace layout is per uniform batch");
-    Call c = call_pair("vtq_forward_varlen", false, patches_ref, patches_dist, pos_ref, pos_dist, scales_ref, scales_dist, B, 0, q_out);
-    c.n_img[0] = c.n_img[1] = n_patches;
-    return forward_ragged(e, c, stream);
+    return forward_varlen("vtq_forward_varlen", e, patches_ref, patches_dist, pos_ref, pos_dist, scales_ref, scales_dist, B, n_patches, q_out, nullptr,
+                          stream);
+}
+
+// The same with the attention rollout of every sequence, packed in call order: all reference sequences, then all distorted ones
+int vtq_forward_varlen_rollout(vtq_handle e, const float* patches_ref, const float* patches_dist, const float* pos_ref, const float* pos_dist,
+                               const float* scales_ref, const float* scales_dist, int32_t B, const int32_t* n_patches, float* q_out,
+                               float* rollout_out, float* last_attention_out, void* stream) {
+    const RolloutOut ro{rollout_out, last_attention_out};
+    return forward_varlen("vtq_forward_varlen_rollout", e, patches_ref, patches_dist, pos_ref, pos_dist, scales_ref, scales_dist, B, n_patches, q_out,
+                          &ro, stream);
 }
 
 static int forward_triplet(vtq_handle e, const char* who, bool tokens_in, const float* const* in, const float* const* pos,
@@ -1438,12 +1481,14 @@ static int check_group_handle(const char* who, vtq_handle e) {
 
 static int forward_group(const char* who, vtq_handle e, bool tokens_in, const float* in_ref, const float* in_dist, const float* pos_ref,
                          const float* pos_dist, const float* scales_ref, const float* scales_dist, int32_t G, int32_t M, int32_t N,
-                         const int32_t* ref_index, float* q_out, void* stream) {
-    if (check_group(who, G, M, N, ref_index, true) || check_group_handle(who, e)) return 1;
+                         const int32_t* ref_index, float* q_out, const RolloutOut* ro, void* stream) {
+    if (check_group(who, G, M, N, ref_index, true) || check_rollout_out(who, ro) || check_group_handle(who, e)) return 1;
     if (!in_ref || !in_dist || !pos_ref || !pos_dist) return fail("%s: null tensor", who);
     if (!q_out) return fail("%s: null output", who);
+    if (check_rollout_handle(who, e, ro, (int64_t)G + M)) return 1;
     Call c = call_pair(who, tokens_in, in_ref, in_dist, pos_ref, pos_dist, scales_ref, scales_dist, M, N, q_out);
     c.rg = RefGroup{REF_GROUP, G, ref_index, nullptr};
+    set_rollout(c, ro);
     return forward_uniform(e, c, stream);
 }
 
@@ -1451,36 +1496,79 @@ int vtq_forward_group(vtq_handle e, const float* patches_ref, const float* patch
                       const float* scales_ref, const float* scales_dist, int32_t G, int32_t M, int32_t N, const int32_t* ref_index,
                       float* q_out, void* stream) {
     return forward_group("vtq_forward_group", e, false, patches_ref, patches_dist, pos_ref, pos_dist, scales_ref, scales_dist, G, M, N, ref_index,
-                         q_out, stream);
+                         q_out, nullptr, stream);
 }
 
 int vtq_forward_group_tokens(vtq_handle e, const float* feats_ref, const float* feats_dist, const float* pos_ref, const float* pos_dist,
                              const float* scales_ref, const float* scales_dist, int32_t G, int32_t M, int32_t N, const int32_t* ref_index,
                              float* q_out, void* stream) {
     return forward_group("vtq_forward_group_tokens", e, true, feats_ref, feats_dist, pos_ref, pos_dist, scales_ref, scales_dist, G, M, N, ref_index,
-                         q_out, stream);
+                         q_out, nullptr, stream);
+}
+
+// The rollout forms: rollout_out [G + M][S], last_attention_out [G + M][h][S], the references first
+int vtq_forward_group_rollout(vtq_handle e, const float* patches_ref, const float* patches_dist, const float* pos_ref, const float* pos_dist,
+                              const float* scales_ref, const float* scales_dist, int32_t G, int32_t M, int32_t N, const int32_t* ref_index,
+                              float* q_out, float* rollout_out, float* last_attention_out, void* stream) {
+    const RolloutOut ro{rollout_out, last_attention_out};
+    return forward_group("vtq_forward_group_rollout", e, false, patches_ref, patches_dist, pos_ref, pos_dist, scales_ref, scales_dist, G, M, N,
+                         ref_index, q_out, &ro, stream);
+}
+
+int vtq_forward_group_rollout_tokens(vtq_handle e, const float* feats_ref, const float* feats_dist, const float* pos_ref, const float* pos_dist,
+                                     const float* scales_ref, const float* scales_dist, int32_t G, int32_t M, int32_t N, const int32_t* ref_index,
+                                     float* q_out, float* rollout_out, float* last_attention_out, void* stream) {
+    const RolloutOut ro{rollout_out, last_attention_out};
+    return forward_group("vtq_forward_group_rollout_tokens", e, true, feats_ref, feats_dist, pos_ref, pos_dist, scales_ref, scales_dist, G, M, N,
+                         ref_index, q_out, &ro, stream);
+}
+
+static int encode_reference(const char* who, vtq_handle e, const float* in, int32_t tokens_in, const float* pos, const float* scales, int32_t G,
+                            int32_t N, float* ref_rows, const RolloutOut* ro, void* stream) {
+    if (check_group(who, G, 1, N, nullptr, false) || check_rollout_out(who, ro) || check_group_handle(who, e)) return 1;
+    if (!in || !pos) return fail("%s: null tensor", who);
+    if (!ref_rows) return fail("%s: null output", who);
+    if (check_rollout_handle(who, e, ro, G)) return 1;
+    Call c = call_single(who, tokens_in, in, pos, scales, G, N, nullptr);
+    c.rg = RefGroup{REF_ENCODE, G, nullptr, ref_rows};
+    set_rollout(c, ro);
+    return forward_uniform(e, c, stream);
 }
 
 int vtq_encode_reference(vtq_handle e, const float* in, int32_t tokens_in, const float* pos, const float* scales, int32_t G, int32_t N,
                          float* ref_rows, void* stream) {
-    const char* who = "vtq_encode_reference";
-    if (check_group(who, G, 1, N, nullptr, false) || check_group_handle(who, e)) return 1;
-    if (!in || !pos) return fail("%s: null tensor", who);
-    if (!ref_rows) return fail("%s: null output", who);
-    Call c = call_single(who, tokens_in, in, pos, scales, G, N, nullptr);
-    c.rg = RefGroup{REF_ENCODE, G, nullptr, ref_rows};
+    return encode_reference("vtq_encode_reference", e, in, tokens_in, pos, scales, G, N, ref_rows, nullptr, stream);
+}
+
+int vtq_encode_reference_rollout(vtq_handle e, const float* in, int32_t tokens_in, const float* pos, const float* scales, int32_t G, int32_t N,
+                                 float* ref_rows, float* rollout_out, float* last_attention_out, void* stream) {
+    const RolloutOut ro{rollout_out, last_attention_out};
+    return encode_reference("vtq_encode_reference_rollout", e, in, tokens_in, pos, scales, G, N, ref_rows, &ro, stream);
+}
+
+static int forward_cached(const char* who, vtq_handle e, const float* ref_rows, int32_t G, const float* in, int32_t tokens_in, const float* pos,
+                          const float* scales, int32_t M, int32_t N, const int32_t* ref_index, float* q_out, const RolloutOut* ro, void* stream) {
+    if (check_group(who, G, M, N, ref_index, true) || check_rollout_out(who, ro) || check_group_handle(who, e)) return 1;
+    if (!ref_rows || !in || !pos) return fail("%s: null tensor", who);
+    if (!q_out) return fail("%s: null output", who);
+    if (check_rollout_handle(who, e, ro, M)) return 1;
+    Call c = call_single(who, tokens_in, in, pos, scales, M, N, q_out);
+    c.rg = RefGroup{REF_CACHED, G, ref_index, const_cast<float*>(ref_rows)};
+    set_rollout(c, ro);
     return forward_uniform(e, c, stream);
 }
 
 int vtq_forward_cached(vtq_handle e, const float* ref_rows, int32_t G, const float* in, int32_t tokens_in, const float* pos, const float* scales,
                        int32_t M, int32_t N, const int32_t* ref_index, float* q_out, void* stream) {
-    const char* who = "vtq_forward_cached";
-    if (check_group(who, G, M, N, ref_index, true) || check_group_handle(who, e)) return 1;
-    if (!ref_rows || !in || !pos) return fail("%s: null tensor", who);
-    if (!q_out) return fail("%s: null output", who);
-    Call c = call_single(who, tokens_in, in, pos, scales, M, N, q_out);
-    c.rg = RefGroup{REF_CACHED, G, ref_index, const_cast<float*>(ref_rows)};
-    return forward_uniform(e, c, stream);
+    return forward_cached("vtq_forward_cached", e, ref_rows, G, in, tokens_in, pos, scales, M, N, ref_index, q_out, nullptr, stream);
+}
+
+// the M distorted sequences' maps only: the cached references' come from vtq_encode_reference_rollout
+int vtq_forward_cached_rollout(vtq_handle e, const float* ref_rows, int32_t G, const float* in, int32_t tokens_in, const float* pos,
+                               const float* scales, int32_t M, int32_t N, const int32_t* ref_index, float* q_out, float* rollout_out,
+                               float* last_attention_out, void* stream) {
+    const RolloutOut ro{rollout_out, last_attention_out};
+    return forward_cached("vtq_forward_cached_rollout", e, ref_rows, G, in, tokens_in, pos, scales, M, N, ref_index, q_out, &ro, stream);
 }
 
 // ---- one-to-many scoring on images of different patch counts (include/vtamiq_hip.h) ------------------------------------------------------
@@ -1502,49 +1590,94 @@ static int check_group_varlen(const char* who, int32_t G, int32_t M, const int32
     return 0;
 }
 
-int vtq_forward_group_varlen(vtq_handle e, const float* patches_ref, const float* patches_dist, const float* pos_ref, const float* pos_dist,
-                             const float* scales_ref, const float* scales_dist, int32_t G, int32_t M, const int32_t* n_ref, const int32_t* n_dist,
-                             const int32_t* ref_index, float* q_out, void* stream) {
-    const char* who = "vtq_forward_group_varlen";
+static int forward_group_varlen(const char* who, vtq_handle e, const float* patches_ref, const float* patches_dist, const float* pos_ref,
+                                const float* pos_dist, const float* scales_ref, const float* scales_dist, int32_t G, int32_t M, const int32_t* n_ref,
+                                const int32_t* n_dist, const int32_t* ref_index, float* q_out, const RolloutOut* ro, void* stream) {
     if (!n_ref) return fail("%s: null n_ref", who);
     if (!n_dist) return fail("%s: null n_dist", who);
     if (check_group_varlen(who, G, M, ref_index, true) || check_counts(who, "n_ref", n_ref, G) || check_counts(who, "n_dist", n_dist, M)) return 1;
-    if (check_group_handle(who, e)) return 1;
+    if (check_rollout_out(who, ro) || check_group_handle(who, e)) return 1;
     if (!patches_ref || !patches_dist || !pos_ref || !pos_dist) return fail("%s: null tensor", who);
     if (!q_out) return fail("%s: null output", who);
+    if (check_rollout_handle(who, e, ro, (int64_t)G + M)) return 1;
     Call c = call_pair(who, false, patches_ref, patches_dist, pos_ref, pos_dist, scales_ref, scales_dist, M, 0, q_out);
     c.rg = RefGroup{REF_GROUP, G, ref_index, nullptr};
     c.n_img[0] = n_ref;
     c.n_img[1] = n_dist;
+    set_rollout(c, ro);
+    return forward_ragged(e, c, stream);
+}
+
+int vtq_forward_group_varlen(vtq_handle e, const float* patches_ref, const float* patches_dist, const float* pos_ref, const float* pos_dist,
+                             const float* scales_ref, const float* scales_dist, int32_t G, int32_t M, const int32_t* n_ref, const int32_t* n_dist,
+                             const int32_t* ref_index, float* q_out, void* stream) {
+    return forward_group_varlen("vtq_forward_group_varlen", e, patches_ref, patches_dist, pos_ref, pos_dist, scales_ref, scales_dist, G, M, n_ref,
+                                n_dist, ref_index, q_out, nullptr, stream);
+}
+
+// the rollout forms: both outputs packed over the call's sequences in call order (here: the G references, then the M distorted images)
+int vtq_forward_group_varlen_rollout(vtq_handle e, const float* patches_ref, const float* patches_dist, const float* pos_ref, const float* pos_dist,
+                                     const float* scales_ref, const float* scales_dist, int32_t G, int32_t M, const int32_t* n_ref,
+                                     const int32_t* n_dist, const int32_t* ref_index, float* q_out, float* rollout_out, float* last_attention_out,
+                                     void* stream) {
+    const RolloutOut ro{rollout_out, last_attention_out};
+    return forward_group_varlen("vtq_forward_group_varlen_rollout", e, patches_ref, patches_dist, pos_ref, pos_dist, scales_ref, scales_dist, G, M,
+                                n_ref, n_dist, ref_index, q_out, &ro, stream);
+}
+
+static int encode_reference_varlen(const char* who, vtq_handle e, const float* patches, const float* pos, const float* scales, int32_t G,
+                                   const int32_t* n_patches, float* ref_rows, const RolloutOut* ro, void* stream) {
+    if (!n_patches) return fail("%s: null n_patches", who);
+    if (check_group_varlen(who, G, 1, nullptr, false) || check_counts(who, "n_patches", n_patches, G)) return 1;
+    if (check_rollout_out(who, ro) || check_group_handle(who, e)) return 1;
+    if (!patches || !pos) return fail("%s: null tensor", who);
+    if (!ref_rows) return fail("%s: null output", who);
+    if (check_rollout_handle(who, e, ro, G)) return 1;
+    Call c = call_single(who, 0, patches, pos, scales, G, 0, nullptr);
+    c.rg = RefGroup{REF_ENCODE, G, nullptr, ref_rows};
+    c.n_img[0] = n_patches;
+    set_rollout(c, ro);
     return forward_ragged(e, c, stream);
 }
 
 int vtq_encode_reference_varlen(vtq_handle e, const float* patches, const float* pos, const float* scales, int32_t G, const int32_t* n_patches,
                                 float* ref_rows, void* stream) {
-    const char* who = "vtq_encode_reference_varlen";
+    return encode_reference_varlen("vtq_encode_reference_varlen", e, patches, pos, scales, G, n_patches, ref_rows, nullptr, stream);
+}
+
+int vtq_encode_reference_varlen_rollout(vtq_handle e, const float* patches, const float* pos, const float* scales, int32_t G,
+                                        const int32_t* n_patches, float* ref_rows, float* rollout_out, float* last_attention_out, void* stream) {
+    const RolloutOut ro{rollout_out, last_attention_out};
+    return encode_reference_varlen("vtq_encode_reference_varlen_rollout", e, patches, pos, scales, G, n_patches, ref_rows, &ro, stream);
+}
+
+static int forward_cached_varlen(const char* who, vtq_handle e, const float* ref_rows, int32_t G, const float* patches, const float* pos,
+                                 const float* scales, int32_t M, const int32_t* n_patches, const int32_t* ref_index, float* q_out,
+                                 const RolloutOut* ro, void* stream) {
     if (!n_patches) return fail("%s: null n_patches", who);
-    if (check_group_varlen(who, G, 1, nullptr, false) || check_counts(who, "n_patches", n_patches, G)) return 1;
-    if (check_group_handle(who, e)) return 1;
-    if (!patches || !pos) return fail("%s: null tensor", who);
-    if (!ref_rows) return fail("%s: null output", who);
-    Call c = call_single(who, 0, patches, pos, scales, G, 0, nullptr);
-    c.rg = RefGroup{REF_ENCODE, G, nullptr, ref_rows};
+    if (check_group_varlen(who, G, M, ref_index, true) || check_counts(who, "n_patches", n_patches, M)) return 1;
+    if (check_rollout_out(who, ro) || check_group_handle(who, e)) return 1;
+    if (!ref_rows || !patches || !pos) return fail("%s: null tensor", who);
+    if (!q_out) return fail("%s: null output", who);
+    if (check_rollout_handle(who, e, ro, M)) return 1;
+    Call c = call_single(who, 0, patches, pos, scales, M, 0, q_out);
+    c.rg = RefGroup{REF_CACHED, G, ref_index, const_cast<float*>(ref_rows)};
     c.n_img[0] = n_patches;
+    set_rollout(c, ro);
     return forward_ragged(e, c, stream);
 }
 
 int vtq_forward_cached_varlen(vtq_handle e, const float* ref_rows, int32_t G, const float* patches, const float* pos, const float* scales, int32_t M,
                               const int32_t* n_patches, const int32_t* ref_index, float* q_out, void* stream) {
-    const char* who = "vtq_forward_cached_varlen";
-    if (!n_patches) return fail("%s: null n_patches", who);
-    if (check_group_varlen(who, G, M, ref_index, true) || check_counts(who, "n_patches", n_patches, M)) return 1;
-    if (check_group_handle(who, e)) return 1;
-    if (!ref_rows || !patches || !pos) return fail("%s: null tensor", who);
-    if (!q_out) return fail("%s: null output", who);
-    Call c = call_single(who, 0, patches, pos, scales, M, 0, q_out);
-    c.rg = RefGroup{REF_CACHED, G, ref_index, const_cast<float*>(ref_rows)};
-    c.n_img[0] = n_patches;
-    return forward_ragged(e, c, stream);
+    return forward_cached_varlen("vtq_forward_cached_varlen", e, ref_rows, G, patches, pos, scales, M, n_patches, ref_index, q_out, nullptr, stream);
+}
+
+int vtq_forward_cached_varlen_rollout(vtq_handle e, const float* ref_rows, int32_t G, const float* patches, const float* pos, const float* scales,
+                                      int32_t M, const int32_t* n_patches, const int32_t* ref_index, float* q_out, float* rollout_out,
+                                      float* last_attention_out, void* stream) {
+    const RolloutOut ro{rollout_out, last_attention_out};
+    return forward_cached_varlen("vtq_forward_cached_varlen_rollout", e, ref_rows, G, patches, pos, scales, M, n_patches, ref_index, q_out, &ro,
+                                 stream);
 }
 
 int vtq_input_errors(vtq_handle e, int32_t* flags, void* stream) {
@@ -1690,6 +1823,41 @@ int vtq_k_rollout_step(const void* qkv, int64_t plane, const float* r_in, float*
     if (!qkv || !r_in || !r_out || !part || nseq < 1 || nseq > 65535 || S < 1 || S_pad < S || H < 64 || H % 64) return fail("vtq_k_rollout_step: bad argument");
     if (q_log2 && nm.terms != 3) return fail("vtq_k_rollout_step: q_log2 applies to the 3-term formats only");
     HIP_TRY(launch_rollout_step(qkv, plane, r_in, 0, part, r_out, nullptr, nseq, S, S_pad, H, nm, (hipStream_t)stream, q_log2 != 0));
+    return 0;
+}
+
+int vtq_vl_rollout_step(const void* qkv, int64_t plane, const float* r_in, float* r_out, float* part, int32_t nseq, const int32_t* seq_len,
+                        int32_t H, int32_t num, int32_t q_log2, void* stream) {
+    const Num nm = num_from_code(num);
+    if (!num_valid(nm) || nm.terms == 2 || nm.f16 > 1) return fail("vtq_vl_rollout_step: operand format code %d", num);
+    if (!qkv || !r_in || !r_out || !part || !seq_len) return fail("vtq_vl_rollout_step: null argument");
+    if (q_log2 && nm.terms != 3) return fail("vtq_vl_rollout_step: q_log2 applies to the 3-term formats only");
+    if (nseq > 65535) return fail("vtq_vl_rollout_step: nseq=%d (at most 65535)", (int)nseq);
+    const std::vector<int> blocks = vl_blocks_checked(nseq, seq_len, H);
+    const int nblocks = (int)(blocks.size() / 4);
+    if (nblocks < 1) return fail("vtq_vl_rollout_step: nseq=%d, H=%d or a sequence length < 1", (int)nseq, (int)H);
+    // the call's tables as forward() lays them out (Table): row offsets, lengths, then the block table
+    const Table tb(nseq);
+    std::vector<int> t((size_t)tb.blk + blocks.size(), 0);
+    int64_t rows = 0;
+    int smax = 0;
+    for (int j = 0; j < nseq; ++j) {
+        t[j] = (int)rows; t[tb.len + j] = seq_len[j];
+        rows += seq_len[j];
+        if (seq_len[j] > smax) smax = seq_len[j];
+    }
+    t[nseq] = (int)rows;
+    memcpy(t.data() + tb.blk, blocks.data(), blocks.size() * sizeof(int));
+    hipStream_t s = (hipStream_t)stream;
+    int* dev = nullptr;
+    HIP_TRY(hipMalloc((void**)&dev, t.size() * sizeof(int)));
+    hipError_t err = hipMemcpyAsync(dev, t.data(), t.size() * sizeof(int), hipMemcpyHostToDevice, s);
+    if (err == hipSuccess)
+        err = launch_rollout_step_varlen(qkv, plane, r_in, 0, part, r_out, nullptr, dev + tb.blk, nblocks, dev, dev + tb.len, nseq, smax, rows, H, nm,
+                                         s, q_log2 != 0);
+    const hipError_t err2 = hipStreamSynchronize(s);        // the table is a temporary of this call
+    (void)hipFree(dev);
+    if (err != hipSuccess || err2 != hipSuccess) return fail("vtq_vl_rollout_step: %s", hipGetErrorString(err != hipSuccess ? err : err2));
     return 0;
 }
 

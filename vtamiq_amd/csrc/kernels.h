@@ -161,6 +161,13 @@ hipError_t launch_attention_probs(const void* qkv, int64_t plane, float* probs, 
 // [seq * S_pad, seq * S_pad + S) of each sequence only.  A sequence's result depends on its own rows and S alone.
 hipError_t launch_rollout_step(const void* qkv, int64_t plane, const float* r, int token, float* part, float* out, float* heads_out, int nseq,
                                int S, int S_pad, int H, Num num, hipStream_t s, bool q_log2 = false);
+// The same step over nseq sequences of different lengths packed back to back (R rows in all, the longest S_max): `blocks` = DEVICE copy of
+// attention_varlen_blocks(), row0 / len = DEVICE row offsets and lengths.  r, out: fp32 [R], packed like the rows; heads_out (may be NULL):
+// sequence j's [H / 64][S_j] block at (H / 64) * row0[j]; part: workspace fp32 [H / 64][ceil(S_max / 128)][R].  Sequence j's result has the bits
+// launch_rollout_step gives that sequence alone (nseq = 1, S = S_pad = S_j): the two forms share the step's body.
+hipError_t launch_rollout_step_varlen(const void* qkv, int64_t plane, const float* r, int token, float* part, float* out, float* heads_out,
+                                      const int* blocks, int nblocks, const int* row0, const int* len, int nseq, int S_max, int64_t R, int H,
+                                      Num num, hipStream_t s, bool q_log2 = false);
 
 // zero the rows of the residual stream that belong to no token: per-sequence pads, per-part tails, and everything up to rows_total
 hipError_t launch_zero_pad_rows(float* x, int nseq, int S, SeqMap sm, int H, int rows_total, hipStream_t s);

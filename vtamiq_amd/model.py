@@ -49,9 +49,24 @@ class Rollout(NamedTuple):
     """What VTAMIQ.forward_rollout returns beside the scores (index 0 = reference image, 1 = distorted image of each pair):
       rollout         (2, B, S) fp32: attention rollout of the token the score is read from, over the S = T + N tokens of each image
                       (the T = 1 + num_extra_tokens tokens first, then the N patches in input order); > 0, each row sums to 1
-      last_attention  (2, B, num_heads, S) fp32: the last layer's attention row of that token, per head"""
+      last_attention  (2, B, num_heads, S) fp32: the last layer's attention row of that token, per head
+    The other entries return the same two fields over the images THEY encode (see each docstring): forward_group (ref (G, S), dist (M, S)) and
+    ((G, h, S), (M, h, S)); encode_reference (G, S) / (G, h, S); forward_cached (M, S) / (M, h, S).  With `lengths=` every (n, S) tensor
+    becomes a list of n tensors (S_i,) and every (n, h, S) tensor a list of (h, S_i): views into one flat allocation per field."""
     rollout: torch.Tensor
     last_attention: torch.Tensor
+
+
+def _ragged_maps(roll, last, lens, T: int, nh: int):
+    """The packed outputs of a variable-length rollout call as per-image views, no copies: `roll` holds the images' S_i = lens[i] + T values
+    back to back, `last` image i's (nh, S_i) block at nh times its offset.  Returns (list of (S_i,), list of (nh, S_i))."""
+    maps, heads, o = [], [], 0
+    for n in lens:
+        S = n + T
+        maps.append(roll[o:o + S])
+        heads.append(last[nh * o:nh * (o + S)].view(nh, S))
+        o += S
+    return maps, heads
 
 
 class StaleReferenceError(ValueError):
@@ -686,7 +701,7 @@ class VTAMIQ(nn.Module):
             self._launch_checked(device, launch)
         return q, None
 
-    def forward_rollout(self, patches, pos, scales):
+    def forward_rollout(self, patches, pos, scales, *, lengths=None):
         """forward() plus, in the same call, which patches each score looked at: attention rollout (Abnar & Zuidema) of the token the score
         is read from (`token_num`), and that token's last-layer attention row per head.  With P_l the (S, S) attention matrices
         forward_vit(return_attention) reports, A_l = (I + mean over heads of P_l) / 2:
@@ -698,14 +713,35 @@ class VTAMIQ(nn.Module):
         Returns (q, Rollout): q (B,) fp32 with the bits of forward(); Rollout.rollout (2, B, S), Rollout.last_attention (2, B, num_heads, S),
         fp32 on the input device.  A pair's values do not depend on the batch it is in.  The input / range policy ("auto", validate_inputs,
         check_inputs) is forward()'s: a position outside [0, 1) raises IndexError, an fp16 overflow switches to bf16x3 and repeats the whole call.
-        The call keeps num_layers extra QKV buffers in the engine (rollout_workspace_bytes).  forward_varlen, forward_group,
-        forward_cached and forward_pairwise have no rollout variant."""
+        The call keeps num_layers extra QKV buffers in the engine (rollout_workspace_bytes).
+          lengths  None, or B integers >= 1: pairs of DIFFERENT patch counts, inputs as in forward_varlen (concatenated (sum(lengths), ...)
+                   tensors or lists of per-pair tensors, 5-D patches only).  q has the bits of forward_varlen; Rollout.rollout is then
+                   (ref, dist), each a list of B tensors (S_b,), S_b = T + lengths[b], and Rollout.last_attention (ref, dist) of lists of
+                   (num_heads, S_b) -- views into one flat allocation per field.  Pair b's maps have the bits of forward_rollout on pair b
+                   alone; equal lengths give the bits of the call without lengths.
+        The one-to-many entries take `rollout=True` for the same maps (forward_group, encode_reference, forward_cached, with or without
+        their `lengths=`); forward_varlen's maps are this call's `lengths=` form; forward_pairwise has no rollout variant."""
         if self.training:
             raise NotImplementedError(_TRAIN_MSG)
         if self._FP8_EXPERIMENT:
             raise NotImplementedError("forward_rollout is not available for the fp8 experiment's model")
         if len(patches) != 2:
             raise ValueError("forward_rollout expects patches = (p_ref, p_dist)")
+        if lengths is not None:
+            device, B, lens, (pr, pd), (qr, qd), (sr, sdist) = self._varlen_inputs("forward_rollout", patches, pos, scales, lengths)
+            T, nh = self.spec.num_tokens, self.spec.num_heads
+            R = sum(lens) + B * T                     # token rows of one image's B sequences
+            with torch.cuda.device(device):
+                q = torch.empty(B, device=device, dtype=torch.float32)
+                roll = torch.empty(2 * R, device=device, dtype=torch.float32)
+                last = torch.empty(2 * R * nh, device=device, dtype=torch.float32)
+                n_arr = (C.c_int32 * B)(*lens)
+                stream = torch.cuda.current_stream(device).cuda_stream
+                self._launch_checked(device, lambda lib: self._check(lib.vtq_forward_varlen_rollout(
+                    self._engine, pr.data_ptr(), pd.data_ptr(), qr.data_ptr(), qd.data_ptr(), _ptr(sr), _ptr(sdist), B, n_arr, q.data_ptr(),
+                    roll.data_ptr(), last.data_ptr(), stream)))
+            maps, heads = _ragged_maps(roll, last, lens + lens, T, nh)          # all reference sequences, then all distorted ones
+            return q, Rollout((maps[:B], maps[B:]), (heads[:B], heads[B:]))
         device, B, N, tokens_in, (pr, pd), (qr, qd), (sr, sdist) = self._inputs(tuple(patches), pos, scales)
         S, nh = N + self.spec.num_tokens, self.spec.num_heads
         with torch.cuda.device(device):
@@ -734,6 +770,18 @@ class VTAMIQ(nn.Module):
             raise NotImplementedError(_TRAIN_MSG)
         if self._FP8_EXPERIMENT:
             raise NotImplementedError("forward_varlen is not available for the fp8 experiment's model")
+        device, B, lens, (pr, pd), (qr, qd), (sr, sdist) = self._varlen_inputs("forward_varlen", patches, pos, scales, lengths)
+        with torch.cuda.device(device):
+            q = torch.empty(B, device=device, dtype=torch.float32)
+            n_arr = (C.c_int32 * B)(*lens)
+            stream = torch.cuda.current_stream(device).cuda_stream
+            self._launch_checked(device, lambda lib: self._check(lib.vtq_forward_varlen(
+                self._engine, pr.data_ptr(), pd.data_ptr(), qr.data_ptr(), qd.data_ptr(), _ptr(sr), _ptr(sdist), B, n_arr, q.data_ptr(), stream)))
+        return q, None
+
+    def _varlen_inputs(self, what, patches, pos, scales, lengths):
+        """The host checks and input preparation of a batch of pairs with different patch counts (forward_varlen, forward_rollout(lengths=)):
+        (device, B, lengths as ints, (p_ref, p_dist), (pos_ref, pos_dist), (scales_ref, scales_dist)), the tensors concatenated, fp32, contiguous."""
         if isinstance(lengths, torch.Tensor):
             if lengths.device.type != "cpu":
                 raise ValueError("lengths must be a sequence of ints or a CPU integer tensor: a CUDA tensor would force a device synchronisation")
@@ -766,18 +814,12 @@ class VTAMIQ(nn.Module):
         P = self.spec.patch_size
         first = patches[0][0] if isinstance(patches[0], (list, tuple)) else patches[0]
         if first.dim() != 4:
-            raise ValueError(f"forward_varlen takes patches as (sum(lengths), 3, {P}, {P}) tensors (pre-embedded input is not offered), got {tuple(first.shape)}")
+            raise ValueError(f"{what} takes patches as (sum(lengths), 3, {P}, {P}) tensors (pre-embedded input is not offered), got {tuple(first.shape)}")
         pt = joined(patches, "patches", tuple(first.shape[1:]))
         ps = joined(pos, "pos", (2,)) if self.spec.use_pos_embedding else pos
         sc = joined(scales, "scales", ()) if self.spec.use_scale_embedding else None
-        device, _, _, _, (pr, pd), (qr, qd), (sr, sdist) = self._inputs(pt, ps, sc)
-        with torch.cuda.device(device):
-            q = torch.empty(B, device=device, dtype=torch.float32)
-            n_arr = (C.c_int32 * B)(*lens)
-            stream = torch.cuda.current_stream(device).cuda_stream
-            self._launch_checked(device, lambda lib: self._check(lib.vtq_forward_varlen(
-                self._engine, pr.data_ptr(), pd.data_ptr(), qr.data_ptr(), qd.data_ptr(), _ptr(sr), _ptr(sdist), B, n_arr, q.data_ptr(), stream)))
-        return q, None
+        device, _, _, _, pt, ps, sc = self._inputs(pt, ps, sc)
+        return device, B, lens, pt, ps, sc
 
     # ---- one-to-many scoring: every reference encoded once ----------------------------------------------------------------
     def _group_guard(self, what):
@@ -809,7 +851,7 @@ class VTAMIQ(nn.Module):
         device, _, _, _, (pt,), (ps,), (sc,) = self._inputs((pt,), (ps,), (sc,))
         return device, pt, ps, sc
 
-    def forward_group(self, patches, pos, scales, ref_index, *, lengths=None):
+    def forward_group(self, patches, pos, scales, ref_index, *, lengths=None, rollout=False):
         """M distorted images over G references in ONE call, every reference encoded once: G + M sequences where forward() on the expanded
         pairs encodes 2 M.
           patches    (p_ref, p_dist): (G, N, 3, P, P) and (M, N, 3, P, P) -- or both pre-embedded, (G | M, N, H), as in forward()
@@ -822,7 +864,11 @@ class VTAMIQ(nn.Module):
                      CPU integer tensor.  patches / pos / scales are then per image the concatenated tensors, (sum, 3, P, P) / (sum, 2) /
                      (sum,), or lists of per-image tensors, as in forward_varlen (5-D patches only).  A distorted image's count need not be
                      its reference's.  q[m] has the bits of encode_reference on reference i alone followed by forward_cached on image m
-                     alone -- with equal counts, of `self(...)` on the pair; all counts equal give the bits of the call without lengths."""
+                     alone -- with equal counts, of `self(...)` on the pair; all counts equal give the bits of the call without lengths.
+          rollout    True: returns (q, Rollout) with forward_rollout's maps of every image the call encodes, each once: Rollout.rollout =
+                     (ref (G, S), dist (M, S)), Rollout.last_attention = ((G, h, S), (M, h, S)) -- views of one allocation per field; with
+                     lengths, lists of (S_i,) / (h, S_i) tensors instead.  q keeps its bits; an image's maps have the bits of forward_rollout
+                     on any single pair holding it (reference side for a reference, distorted side for a distorted image)."""
         self._group_guard("forward_group")
         if len(patches) != 2:
             raise ValueError("forward_group expects patches = (p_ref, p_dist)")
@@ -840,10 +886,20 @@ class VTAMIQ(nn.Module):
             device_d, pd, qd, sdist = self._ragged_inputs("forward_group", *dist, None)
             if device_d != device:
                 raise ValueError("forward_group: references and distorted images must live on one device")
+            T, nh = self.spec.num_tokens, self.spec.num_heads
             with torch.cuda.device(device):
                 q = torch.empty(M, device=device, dtype=torch.float32)
                 nr, nd, arr = (C.c_int32 * G)(*lr), (C.c_int32 * M)(*ld), (C.c_int32 * M)(*idx)
                 stream = torch.cuda.current_stream(device).cuda_stream
+                if rollout:
+                    R = sum(lr) + sum(ld) + (G + M) * T
+                    roll = torch.empty(R, device=device, dtype=torch.float32)
+                    last = torch.empty(R * nh, device=device, dtype=torch.float32)
+                    self._launch_checked(device, lambda lib: self._check(lib.vtq_forward_group_varlen_rollout(
+                        self._engine, pr.data_ptr(), pd.data_ptr(), qr.data_ptr(), qd.data_ptr(), _ptr(sr), _ptr(sdist), G, M, nr, nd, arr,
+                        q.data_ptr(), roll.data_ptr(), last.data_ptr(), stream)))
+                    maps, heads = _ragged_maps(roll, last, lr + ld, T, nh)
+                    return q, Rollout((maps[:G], maps[G:]), (heads[:G], heads[G:]))
                 self._launch_checked(device, lambda lib: self._check(lib.vtq_forward_group_varlen(
                     self._engine, pr.data_ptr(), pd.data_ptr(), qr.data_ptr(), qd.data_ptr(), _ptr(sr), _ptr(sdist), G, M, nr, nd, arr,
                     q.data_ptr(), stream)))
@@ -861,17 +917,29 @@ class VTAMIQ(nn.Module):
             q = torch.empty(M, device=device, dtype=torch.float32)
             arr = (C.c_int32 * M)(*idx)
             stream = torch.cuda.current_stream(device).cuda_stream
+            if rollout:
+                S, nh = N + self.spec.num_tokens, self.spec.num_heads
+                roll = torch.empty(G + M, S, device=device, dtype=torch.float32)
+                last = torch.empty(G + M, nh, S, device=device, dtype=torch.float32)
+                self._launch_checked(device, lambda lib: self._check(
+                    (lib.vtq_forward_group_rollout_tokens if tokens_in else lib.vtq_forward_group_rollout)(
+                        self._engine, pr.data_ptr(), pd.data_ptr(), qr.data_ptr(), qd.data_ptr(), _ptr(sr), _ptr(sdist), G, M, N, arr, q.data_ptr(),
+                        roll.data_ptr(), last.data_ptr(), stream)))
+                return q, Rollout((roll[:G], roll[G:]), (last[:G], last[G:]))
             self._launch_checked(device, lambda lib: self._check((lib.vtq_forward_group_tokens if tokens_in else lib.vtq_forward_group)(
                 self._engine, pr.data_ptr(), pd.data_ptr(), qr.data_ptr(), qd.data_ptr(), _ptr(sr), _ptr(sdist), G, M, N, arr, q.data_ptr(), stream)))
         return q, None
 
-    def encode_reference(self, patches, pos, scales=None, *, lengths=None) -> ReferenceFeatures:
+    def encode_reference(self, patches, pos, scales=None, *, lengths=None, rollout=False):
         """Encode G reference images once, for forward_cached(): (G, N, 3, P, P) patches (or pre-embedded (G, N, H)), pos (G, N, 2), scales
         (G, N) or None.  Returns a ReferenceFeatures whose `.rows` (G, H) are an ordinary tensor of the caller's.  The input / range policy is
         forward()'s; check_inputs() raises FloatingPointError for a non-finite row.
           lengths  None, or G integers >= 1 (a sequence or a CPU integer tensor): references of DIFFERENT patch counts, patches / pos / scales
                    the concatenated (sum(lengths), ...) tensors or lists of per-image tensors, as forward_group(lengths=...).  Row g has the
-                   bits of encode_reference on reference g alone."""
+                   bits of encode_reference on reference g alone.
+          rollout  True: returns (ReferenceFeatures, Rollout) with forward_rollout's maps of the G references: Rollout.rollout (G, S),
+                   Rollout.last_attention (G, h, S); with lengths, lists of (S_g,) / (h, S_g).  The rows keep their bits; the maps have the
+                   bits forward_group(rollout=True) gives for the same references."""
         self._group_guard("encode_reference")
         if lengths is not None:
             lens = _lengths(lengths, "lengths")
@@ -881,6 +949,15 @@ class VTAMIQ(nn.Module):
                 rows = torch.empty(G, self.spec.hidden_size, device=device, dtype=torch.float32)
                 n_arr = (C.c_int32 * G)(*lens)
                 stream = torch.cuda.current_stream(device).cuda_stream
+                if rollout:
+                    T, nh = self.spec.num_tokens, self.spec.num_heads
+                    R = sum(lens) + G * T
+                    roll = torch.empty(R, device=device, dtype=torch.float32)
+                    last = torch.empty(R * nh, device=device, dtype=torch.float32)
+                    self._launch_checked(device, lambda lib: self._check(lib.vtq_encode_reference_varlen_rollout(
+                        self._engine, pt.data_ptr(), pp.data_ptr(), _ptr(ps), G, n_arr, rows.data_ptr(), roll.data_ptr(), last.data_ptr(), stream)))
+                    return (ReferenceFeatures(rows, self.engine_precision, self._token(), self.engine_options, self._signature()),
+                            Rollout(*_ragged_maps(roll, last, lens, T, nh)))
                 self._launch_checked(device, lambda lib: self._check(lib.vtq_encode_reference_varlen(
                     self._engine, pt.data_ptr(), pp.data_ptr(), _ptr(ps), G, n_arr, rows.data_ptr(), stream)))
             return ReferenceFeatures(rows, self.engine_precision, self._token(), self.engine_options, self._signature())
@@ -888,10 +965,19 @@ class VTAMIQ(nn.Module):
         with torch.cuda.device(device):
             rows = torch.empty(G, self.spec.hidden_size, device=device, dtype=torch.float32)
             stream = torch.cuda.current_stream(device).cuda_stream
-            self._launch_checked(device, lambda lib: self._check(lib.vtq_encode_reference(
-                self._engine, pt.data_ptr(), int(tokens_in), pp.data_ptr(), _ptr(ps), G, N, rows.data_ptr(), stream)))
+            maps = None
+            if rollout:
+                S, nh = N + self.spec.num_tokens, self.spec.num_heads
+                maps = Rollout(torch.empty(G, S, device=device, dtype=torch.float32), torch.empty(G, nh, S, device=device, dtype=torch.float32))
+                self._launch_checked(device, lambda lib: self._check(lib.vtq_encode_reference_rollout(
+                    self._engine, pt.data_ptr(), int(tokens_in), pp.data_ptr(), _ptr(ps), G, N, rows.data_ptr(), maps.rollout.data_ptr(),
+                    maps.last_attention.data_ptr(), stream)))
+            else:
+                self._launch_checked(device, lambda lib: self._check(lib.vtq_encode_reference(
+                    self._engine, pt.data_ptr(), int(tokens_in), pp.data_ptr(), _ptr(ps), G, N, rows.data_ptr(), stream)))
         # read AFTER the launch: "auto" may have switched the model to bf16x3 and repeated the call -- the rows are that run's
-        return ReferenceFeatures(rows, self.engine_precision, self._token(), self.engine_options, self._signature())
+        ref = ReferenceFeatures(rows, self.engine_precision, self._token(), self.engine_options, self._signature())
+        return (ref, maps) if rollout else ref
 
     def _stale(self, ref: ReferenceFeatures):
         now = (self.engine_precision, self._token(), self.engine_options)
@@ -901,7 +987,7 @@ class VTAMIQ(nn.Module):
             return "the model's weights are not the ones that encoded them (another model, load_state_dict, .to(), an optimizer step)"
         return None
 
-    def forward_cached(self, ref: ReferenceFeatures, patches_dist, pos_dist, scales_dist=None, ref_index=None, *, lengths=None):
+    def forward_cached(self, ref: ReferenceFeatures, patches_dist, pos_dist, scales_dist=None, ref_index=None, *, lengths=None, rollout=False):
         """Score M distorted images against references encoded earlier (encode_reference): M sequences are encoded, nothing of the references.
           ref           ReferenceFeatures of G references, made by THIS model in its present state (else StaleReferenceError, a ValueError)
           patches_dist  (M, N, 3, P, P) or pre-embedded (M, N, H); pos_dist (M, N, 2); scales_dist (M, N) or None.  N need not be the
@@ -911,7 +997,10 @@ class VTAMIQ(nn.Module):
         the call then raises StaleReferenceError: the cached rows are fp16x3 rows; encode the references again.
           lengths       None, or M integers >= 1 (a sequence or a CPU integer tensor): distorted images of DIFFERENT patch counts, the
                         tensors concatenated or lists of per-image tensors, as forward_group(lengths=...).  q[m] has the bits of
-                        forward_cached on image m alone against the same rows."""
+                        forward_cached on image m alone against the same rows.
+          rollout       True: returns (q, Rollout) with forward_rollout's maps of the M distorted images alone (the cached references are not
+                        encoded here: their maps come from encode_reference(rollout=True)): Rollout.rollout (M, S), Rollout.last_attention
+                        (M, h, S); with lengths, lists of (S_m,) / (h, S_m).  The bits are forward_group(rollout=True)'s distorted side."""
         self._group_guard("forward_cached")
         if not isinstance(ref, ReferenceFeatures):
             raise TypeError("forward_cached takes the ReferenceFeatures of encode_reference as its first argument")
@@ -932,17 +1021,32 @@ class VTAMIQ(nn.Module):
             q = torch.empty(M, device=device, dtype=torch.float32)
             arr = (C.c_int32 * M)(*idx)
             stream = torch.cuda.current_stream(device).cuda_stream
-            if lens is not None:
+            T, nh, maps = self.spec.num_tokens, self.spec.num_heads, None
+            if lens is not None and rollout:
+                n_arr = (C.c_int32 * M)(*lens)
+                R = sum(lens) + M * T
+                roll = torch.empty(R, device=device, dtype=torch.float32)
+                last = torch.empty(R * nh, device=device, dtype=torch.float32)
+                self._launch_checked(device, lambda lib: self._check(lib.vtq_forward_cached_varlen_rollout(
+                    self._engine, rows.data_ptr(), G, pt.data_ptr(), pp.data_ptr(), _ptr(ps), M, n_arr, arr, q.data_ptr(), roll.data_ptr(),
+                    last.data_ptr(), stream)))
+                maps = Rollout(*_ragged_maps(roll, last, lens, T, nh))
+            elif lens is not None:
                 n_arr = (C.c_int32 * M)(*lens)
                 self._launch_checked(device, lambda lib: self._check(lib.vtq_forward_cached_varlen(
                     self._engine, rows.data_ptr(), G, pt.data_ptr(), pp.data_ptr(), _ptr(ps), M, n_arr, arr, q.data_ptr(), stream)))
+            elif rollout:
+                maps = Rollout(torch.empty(M, N + T, device=device, dtype=torch.float32), torch.empty(M, nh, N + T, device=device, dtype=torch.float32))
+                self._launch_checked(device, lambda lib: self._check(lib.vtq_forward_cached_rollout(
+                    self._engine, rows.data_ptr(), G, pt.data_ptr(), int(tokens_in), pp.data_ptr(), _ptr(ps), M, N, arr, q.data_ptr(),
+                    maps.rollout.data_ptr(), maps.last_attention.data_ptr(), stream)))
             else:
                 self._launch_checked(device, lambda lib: self._check(lib.vtq_forward_cached(
                     self._engine, rows.data_ptr(), G, pt.data_ptr(), int(tokens_in), pp.data_ptr(), _ptr(ps), M, N, arr, q.data_ptr(), stream)))
         if self.engine_precision != ref.precision:
             raise StaleReferenceError(f"forward_cached: an operand left the fp16 range and the model now runs {self.engine_precision!r}; the cached "
                                       f"rows are {ref.precision!r} rows: encode_reference again")
-        return q, None
+        return q, maps
 
     def forward_pairwise(self, patches, pos, scales):
         """Pairwise items: `patches = (p_ref, p_dist1, p_dist2)` etc.  Returns (q1, q2) == what two calls
