@@ -111,7 +111,11 @@ int  vtq_reserve(vtq_handle h, int32_t B, int32_t N);
 /* Replaces VTAMIQ.forward (vtamiq.py:94-119): q_out[B] = score of each (ref, dist) pair.
  *   patches_* : [B, N, 3, 16, 16] fp32 contiguous      pos_* : [B, N, 2] fp32 in [0,1)
  *   scales_*  : [B, N] fp32-cast scale ids, or NULL when the model has no scale embedding
- *               (NULL with num_scales > 1 is an error, as in transformer.py:547-548). */
+ *               (NULL with num_scales > 1 is an error, as in transformer.py:547-548).
+ * Every scoring entry of this header (vtq_forward*, vtq_encode_reference*, vtq_forward_cached*) refuses a bad call with no launch, with text
+ * that names the entry, and checks in one order: the batch description, which needs no handle (a NULL count array or ref_index, the extents,
+ * a count < 1, a ref_index out of range, a NULL rollout_out); the handle (NULL, the fp8 experiment's, a set token trace); NULL tensors and
+ * outputs; what a rollout form adds; the scale rule and the weights.  A call that is wrong twice is refused for the earlier reason. */
 int  vtq_forward(vtq_handle h,
                  const float* patches_ref, const float* patches_dist,
                  const float* pos_ref, const float* pos_dist,

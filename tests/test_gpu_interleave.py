@@ -18,7 +18,7 @@ What of the engine (vtamiq_amd/csrc/engine.hip) or of the model (vtamiq_amd/mode
   test_one_poisoned_pair                  masked keys of a NaN neighbour sequence: healthy pairs of the same call keep their bits in every output
   test_after_a_refused_call               a rollout call refused by the shared path's checks, or behind a trace: the calls behind it never write into
                                           the refused call's output buffers (the outputs belong to the call, not to the handle), trace.
-                                          The varlen refusal is the model's ValueError and never enters the engine; the group refusal is check_group's,
+                                          The varlen refusal is the model's ValueError and never enters the engine; the group refusal is submit()'s,
                                           ahead of upload_table: both show that a refusal leaves nothing behind, neither reaches vl_tab / vl_host
   test_a_vit_call_refused_behind_its_switches   the same for a vtq_forward_vit call refused by the shared path's checks: its `out` and `states`
   test_after_an_out_of_range_position_under_auto   the error word and _launch_checked behind an IndexError, for rollout, group and varlen

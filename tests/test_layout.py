@@ -351,6 +351,46 @@ def test_abi_rejects_bad_arguments_without_touching_a_gpu():
     assert lib.vtq_k_gemm_schedule(256, 100, 768, 1, None, 0) == -1
 
 
+def test_every_scoring_entry_names_itself_and_checks_in_one_order():
+    """All scoring entries end in one argument check: on a NULL handle, fake never-dereferenced pointers and an otherwise well-formed batch
+    description each is refused as `<its own name>: null handle`; a call that is wrong in its description as well is refused for the
+    description, whichever family it belongs to.  The names come from _lib.SIGNATURES: a new entry without a row here fails."""
+    import ctypes as C
+    from vtamiq_amd import _lib
+    lib = _lib.load()
+    fake = C.c_void_p(0x1000)
+    arr = lambda *v: (C.c_int32 * len(v))(*v)
+    pair = (fake,) * 4 + (None, None)
+    trip = (C.c_void_p * 3)(0x1000, 0x1000, 0x1000)
+    idx, n2, n3 = arr(0, 1, 1), arr(8, 8), arr(8, 8, 8)
+    families = {      # base entry -> its arguments between the handle and the stream: B = G = 2, M = 3, N = 8, counts of 8
+        "vtq_forward": (*pair, 2, 8, fake),
+        "vtq_forward_varlen": (*pair, 2, n2, fake),
+        "vtq_forward_pairwise": (trip, trip, None, 2, 8, fake),
+        "vtq_forward_vit": (fake, 0, fake, None, 2, 8, 0, fake, None, None),
+        "vtq_forward_group": (*pair, 2, 3, 8, idx, fake),
+        "vtq_encode_reference": (fake, 0, fake, None, 2, 8, fake),
+        "vtq_forward_cached": (fake, 2, fake, 0, fake, None, 3, 8, idx, fake),
+        "vtq_forward_group_varlen": (*pair, 2, 3, n2, n3, idx, fake),
+        "vtq_encode_reference_varlen": (fake, fake, None, 2, n2, fake),
+        "vtq_forward_cached_varlen": (fake, 2, fake, fake, None, 3, n3, idx, fake),
+    }
+    names = [n for n in _lib.SIGNATURES if n.startswith(("vtq_forward", "vtq_encode_reference"))]
+    assert len(names) == 23
+    for name in names:
+        base = name.replace("_tokens", "")
+        rollout = base.endswith("_rollout")
+        args = families[base[:-len("_rollout")] if rollout else base] + ((fake, None) if rollout else ())
+        assert len(args) + 2 == len(_lib.SIGNATURES[name][1]), name
+        assert getattr(lib, name)(None, *args, None) != 0, name
+        assert (name + ": null handle").encode() in lib.vtq_last_error(), (name, lib.vtq_last_error())
+    # wrong twice, one per family that used to look at the handle first: the batch description is refused
+    assert lib.vtq_forward(None, *pair, 0, 8, fake, None) != 0 and b"vtq_forward: B=0 N=8" in lib.vtq_last_error()
+    assert lib.vtq_forward_pairwise(None, trip, trip, None, 2, 0, fake, None) != 0 and b"vtq_forward_pairwise: B=2 N=0" in lib.vtq_last_error()
+    assert lib.vtq_forward_vit(None, fake, 0, fake, None, 0, 8, 0, fake, None, None, None) != 0
+    assert b"vtq_forward_vit: B=0 N=8" in lib.vtq_last_error()
+
+
 def test_missing_pretrained_checkpoint_raises(monkeypatch, tmp_path):
     """pretrained=True (the reference's default, backbone.py:25) with no checkpoint file: FileNotFoundError like np.load in the
     reference (transformer.py:622-624), not silently random weights; VTAMIQ_ALLOW_MISSING_WEIGHTS=1 is the explicit opt-out."""

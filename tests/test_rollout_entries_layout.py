@@ -163,6 +163,8 @@ def test_python_argument_checks_raise_before_any_library_call():
         with pytest.raises(ValueError, match="lengths"):
             m.forward_rollout((no, no), (no, no), None, lengths=bad)
     for bad in ([], [8, 0], [4.0, 4.0], [True, 7], torch.tensor([4.0, 4.0]), torch.tensor([4, 4], device="meta")):
+        with pytest.raises(ValueError, match="lengths"):                         # one parser of lengths= for every entry
+            m.forward_rollout((no, no), (no, no), None, lengths=bad)
         with pytest.raises(ValueError, match="lengths"):
             m.encode_reference(no, no, lengths=bad, rollout=True)
         with pytest.raises(ValueError, match="lengths"):

@@ -99,6 +99,10 @@ def test_forward_varlen_refuses_bad_lengths_on_the_host():
     for bad in ([], [8, 0], [4, -4, 8], torch.tensor([4.0, 4.0])):
         with pytest.raises(ValueError, match="lengths"):
             m.forward_varlen((p, p), (pos, pos), (None, None), bad)
+    no = "not a tensor"                                                # integers only, as every other lengths=; checked before a tensor is looked at
+    for bad in ([4.0, 4.0], [True, 7]):
+        with pytest.raises(ValueError, match="lengths"):
+            m.forward_varlen((no, no), (no, no), (None, None), bad)
     with pytest.raises(ValueError, match="sum\\(lengths\\)"):
         m.forward_varlen((p, p), (pos, pos), (None, None), [3, 4])
     with pytest.raises(RuntimeError, match="MI355X"):                  # well-formed: the next refusal is forward()'s own (CPU tensors)

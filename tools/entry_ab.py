@@ -2,7 +2,7 @@
 """A/B of the engine's host code: does another build of the library compute and launch exactly what this one does?
 
     entry_ab.py hashes OUT.json [--config NAME ...] [--fp8]
-        Every entry of tests/interleave.py's catalogue on a fresh model, in every configuration below: the sha256 of each output tensor's
+        Every entry of tests/interleave.py's catalogue and every form of added_forms() on a fresh model, in every configuration below: the sha256 of each output tensor's
         bytes (or the text of the exception, where the call is refused), and vtq_workspace_bytes / vtq_rollout_workspace_bytes for the
         capacity the entry reserves.  --fp8 adds the fp8 experiment: forward_small twice on one VTAMIQFp8 (the calibrating call, then the
         next one), both scores and the chosen scales.  Run it once per library (VTQ_LIB_PATH / VTQ_LIB_PATH_FP8) and compare the files.
@@ -28,8 +28,51 @@ CAPACITY = {
 }
 
 
+# The forms the catalogue does not hold (`lengths=` on the one-to-many entries and on forward_rollout, `rollout=True`), on the same small
+# model: G = 2 references, M = 3 distorted images; the ragged patch counts straddle the 128-row attention block edge, the uniform N is 40
+LR, LD, LP, INDEX, N_UNIFORM = [5, 130], [130, 40, 5], [5, 130, 40], [1, 0, 1], 40
+
+
 def sha(t):
     return hashlib.sha256(t.detach().contiguous().cpu().numpy().tobytes()).hexdigest()
+
+
+def flat(x):
+    """Every tensor of what a call returned, in order: tuples, Rollout fields and the list members of the ragged maps included."""
+    if isinstance(x, (list, tuple)):
+        return [t for y in x for t in flat(y)]
+    return [] if x is None else [x.rows] if hasattr(x, "rows") else [x]
+
+
+def added_forms(il):
+    """name -> ((sequence pairs, patches) the form reserves, call(model) -> what it returns)."""
+    import numpy as np, torch
+    from vtamiq_amd import synth
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(il.DEV)
+
+    def ragged(lens, seed, image):                                   # one image list: patches (sum(lens), 3, P, P), pos (sum(lens), 2)
+        pa, po, _ = synth.make_inputs(il.spec(), 1, sum(lens), seed)
+        return dev(pa[0, image]), dev(po[0, image])
+    r, d = {True: ragged(LR, 1201, 0)}, {True: ragged(LD, 1202, 1)}
+    (p0, q0), (p1, q1) = ragged(LP, 1203, 0), ragged(LP, 1203, 1)
+    u = il._group(2, 3, N_UNIFORM, INDEX)(1204)
+    r[False], d[False] = (dev(u["p"][0]), dev(u["pos"][0])), (dev(u["p"][1]), dev(u["pos"][1]))
+
+    def group(lengths, rollout):
+        (pr, qr), (pd, qd), kw = r[lengths], d[lengths], dict(lengths=(LR, LD)) if lengths else {}
+        return lambda m: m.forward_group((pr, pd), (qr, qd), None, INDEX, rollout=rollout, **kw)
+
+    def cached(lengths, rollout):
+        def call(m):
+            ref = m.encode_reference(*r[lengths], None, lengths=LR if lengths else None, rollout=rollout)
+            return ref, m.forward_cached(ref[0] if rollout else ref, *d[lengths], None, INDEX, lengths=LD if lengths else None, rollout=rollout)
+        return call
+    return {
+        "group_lengths": ((3, 130), group(True, False)), "cached_lengths": ((2, 130), cached(True, False)),
+        "rollout_lengths": ((3, 130), lambda m: m.forward_rollout((p0, p1), (q0, q1), None, lengths=LP)),
+        "group_rollout": ((3, 40), group(False, True)), "cached_rollout": ((2, 40), cached(False, True)),
+        "group_lengths_rollout": ((3, 130), group(True, True)), "cached_lengths_rollout": ((2, 130), cached(True, True)),
+    }
 
 
 def hashes(a):
@@ -38,6 +81,7 @@ def hashes(a):
     from vtamiq_amd import _lib
     assert set(CAPACITY) == set(il.CATALOGUE)
     out = {"library": {"abi": int(_lib.load().vtq_abi_version())}}
+    forms = added_forms(il)
     for cname in a.config or CONFIGS:
         precision, options, token = CONFIGS[cname]
         m = il.build_model(precision, options, token)
@@ -50,8 +94,17 @@ def hashes(a):
             except Exception as ex:                                  # a refusal: its text is part of the record
                 rec["refused"] = f"{type(ex).__name__}: {ex}"
             out[f"{cname}/{name}"] = rec
+        for name, ((B, N), call) in forms.items():
+            rec = {"workspace_bytes": m.workspace_bytes(B, N), "rollout_workspace_bytes": m.rollout_workspace_bytes(B, N)}
+            try:
+                torch.cuda.synchronize()
+                with torch.no_grad():
+                    rec["outputs"] = [sha(t) for t in flat(call(il.build_model(precision, options, token)))]
+            except Exception as ex:
+                rec["refused"] = f"{type(ex).__name__}: {ex}"
+            out[f"{cname}/{name}"] = rec
         del m
-        print(f"{cname}: {len(il.CATALOGUE)} entries", flush=True)
+        print(f"{cname}: {len(il.CATALOGUE)} + {len(forms)} entries", flush=True)
     if a.fp8:
         from vtamiq_amd.experimental_fp8 import VTAMIQFp8
         m = VTAMIQFp8(**json.loads(json.dumps(il.KW)))

@@ -42,8 +42,36 @@ class VtqTensorDesc(C.Structure):
     _fields_ = [("name", C.c_char_p), ("data", C.c_void_p), ("numel", C.c_int64)]
 
 
+# The scoring entries' argument lists, from their parts: handle, inputs, extents or host count arrays, ref_index, outputs, stream
+_P, _I, _IP = C.c_void_p, C.c_int32, C.POINTER(C.c_int32)
+_PAIR, _TRIPLET = [_P] * 6, [C.POINTER(_P)] * 3     # patches | feats, pos, scales of (ref, dist) -- of (ref, dist1, dist2), three pointers each
+_SINGLE, _RAGGED, _CACHE = [_P, _I, _P, _P], [_P] * 3, [_P, _I]     # in, tokens_in, pos, scales -- patches, pos, scales (5-D only) -- ref_rows, G
+_entry = lambda *parts: (C.c_int, [_P] + [t for part in parts for t in part] + [_P])
+_rollout = lambda base: (base[0], base[1][:-1] + [_P, _P] + base[1][-1:])      # rollout_out, last_attention_out in front of the stream
+_PAIRS = _entry(_PAIR, [_I, _I], [_P])                                # B, N, q_out
+_VARLEN = _entry(_PAIR, [_I, _IP], [_P])                              # B, n_patches
+_PAIRWISE = _entry(_TRIPLET, [_I, _I], [_P])
+_GROUP = _entry(_PAIR, [_I, _I, _I], [_IP], [_P])                     # G, M, N, ref_index
+_ENCODE = _entry(_SINGLE, [_I, _I], [_P])                             # G, N, ref_rows
+_CACHED = _entry(_CACHE, _SINGLE, [_I, _I], [_IP], [_P])              # M, N, ref_index
+_GROUP_VARLEN = _entry(_PAIR, [_I, _I], [_IP, _IP], [_IP], [_P])      # G, M, n_ref, n_dist, ref_index
+_ENCODE_VARLEN = _entry(_RAGGED, [_I], [_IP], [_P])
+_CACHED_VARLEN = _entry(_CACHE, _RAGGED, [_I], [_IP], [_IP], [_P])
+
 # name -> (restype, argtypes): every symbol include/vtamiq_hip.h declares
 SIGNATURES = {
+    "vtq_forward": _PAIRS, "vtq_forward_tokens": _PAIRS,
+    "vtq_forward_rollout": _rollout(_PAIRS), "vtq_forward_rollout_tokens": _rollout(_PAIRS),
+    "vtq_forward_varlen": _VARLEN, "vtq_forward_varlen_rollout": _rollout(_VARLEN),
+    "vtq_forward_pairwise": _PAIRWISE, "vtq_forward_pairwise_tokens": _PAIRWISE,
+    "vtq_forward_vit": _entry(_SINGLE, [_I, _I, _I], [_P, _P, _P]),   # B, N, all_tokens; out, states, probs
+    "vtq_forward_group": _GROUP, "vtq_forward_group_tokens": _GROUP,
+    "vtq_forward_group_rollout": _rollout(_GROUP), "vtq_forward_group_rollout_tokens": _rollout(_GROUP),
+    "vtq_encode_reference": _ENCODE, "vtq_encode_reference_rollout": _rollout(_ENCODE),
+    "vtq_forward_cached": _CACHED, "vtq_forward_cached_rollout": _rollout(_CACHED),
+    "vtq_forward_group_varlen": _GROUP_VARLEN, "vtq_forward_group_varlen_rollout": _rollout(_GROUP_VARLEN),
+    "vtq_encode_reference_varlen": _ENCODE_VARLEN, "vtq_encode_reference_varlen_rollout": _rollout(_ENCODE_VARLEN),
+    "vtq_forward_cached_varlen": _CACHED_VARLEN, "vtq_forward_cached_varlen_rollout": _rollout(_CACHED_VARLEN),
     "vtq_abi_version": (C.c_int, []),
     "vtq_last_error": (C.c_char_p, []),
     "vtq_create": (C.c_int, [C.POINTER(VtqConfig), C.POINTER(C.c_void_p)]),
@@ -51,44 +79,7 @@ SIGNATURES = {
     "vtq_load_weights": (C.c_int, [C.c_void_p, C.POINTER(VtqTensorDesc), C.c_int32, C.c_void_p]),
     "vtq_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int32, C.c_int32]),
     "vtq_reserve": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
-    "vtq_forward": (C.c_int, [C.c_void_p] + [C.c_void_p] * 6 + [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
-    "vtq_forward_varlen": (C.c_int, [C.c_void_p] + [C.c_void_p] * 6 + [C.c_int32, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]),
-    "vtq_forward_tokens": (C.c_int, [C.c_void_p] + [C.c_void_p] * 6 + [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
-    "vtq_forward_rollout": (C.c_int, [C.c_void_p] + [C.c_void_p] * 6 + [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "vtq_forward_rollout_tokens": (C.c_int, [C.c_void_p] + [C.c_void_p] * 6 + [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vtq_rollout_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int32, C.c_int32]),
-    "vtq_forward_pairwise": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int32,
-                                       C.c_int32, C.c_void_p, C.c_void_p]),
-    "vtq_forward_pairwise_tokens": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int32,
-                                              C.c_int32, C.c_void_p, C.c_void_p]),
-    "vtq_forward_vit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
-                                  C.c_void_p, C.c_void_p, C.c_void_p]),
-    "vtq_forward_group": (C.c_int, [C.c_void_p] + [C.c_void_p] * 6 + [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]),
-    "vtq_forward_group_tokens": (C.c_int, [C.c_void_p] + [C.c_void_p] * 6 + [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_void_p,
-                                           C.c_void_p]),
-    "vtq_encode_reference": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
-    "vtq_forward_cached": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
-                                     C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]),
-    # the same on images of different patch counts: host count arrays in place of N
-    "vtq_forward_group_varlen": (C.c_int, [C.c_void_p] + [C.c_void_p] * 6 + [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
-                                           C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]),
-    "vtq_encode_reference_varlen": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]),
-    "vtq_forward_cached_varlen": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32),
-                                            C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]),
-    # the rollout forms: the base entry's arguments with rollout_out, last_attention_out before the stream
-    "vtq_forward_varlen_rollout": (C.c_int, [C.c_void_p] + [C.c_void_p] * 6 + [C.c_int32, C.POINTER(C.c_int32)] + [C.c_void_p] * 4),
-    "vtq_forward_group_rollout": (C.c_int, [C.c_void_p] + [C.c_void_p] * 6 + [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)] + [C.c_void_p] * 4),
-    "vtq_forward_group_rollout_tokens": (C.c_int, [C.c_void_p] + [C.c_void_p] * 6 + [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]
-                                         + [C.c_void_p] * 4),
-    "vtq_encode_reference_rollout": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 4),
-    "vtq_forward_cached_rollout": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
-                                             C.POINTER(C.c_int32)] + [C.c_void_p] * 4),
-    "vtq_forward_group_varlen_rollout": (C.c_int, [C.c_void_p] + [C.c_void_p] * 6 + [C.c_int32, C.c_int32, C.POINTER(C.c_int32),
-                                                   C.POINTER(C.c_int32), C.POINTER(C.c_int32)] + [C.c_void_p] * 4),
-    "vtq_encode_reference_varlen_rollout": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
-                                            + [C.c_void_p] * 4),
-    "vtq_forward_cached_varlen_rollout": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
-                                                    C.POINTER(C.c_int32), C.POINTER(C.c_int32)] + [C.c_void_p] * 4),
     "vtq_set_token_trace": (C.c_int, [C.c_void_p, C.c_void_p]),
     "vtq_set_iqa_token": (C.c_int, [C.c_void_p, C.c_int32]),
     "vtq_debug_stop_after": (C.c_int, [C.c_void_p, C.c_int32]),
@@ -149,7 +140,7 @@ ROLLOUT_SIGNATURES = {
 # the fp8 experiment (include/vtamiq_hip_fp8.h): exported only by a library built with -DVTQ_WITH_FP8 (python -m vtamiq_amd.build --fp8 ->
 # LIB_PATH_FP8, load_fp8()); bound when present
 FP8_SIGNATURES = {
-    "vtq_fp8_calibrate": (C.c_int, [C.c_void_p] + [C.c_void_p] * 6 + [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "vtq_fp8_calibrate": _PAIRS,                                      # vtq_forward's arguments
     "vtq_fp8_get_scales": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_int32]),
     "vtq_fp8_set_scales": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_int32]),
     "vtq_k_quant_rows_fp8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),

@@ -533,6 +533,7 @@ struct Call {
     bool tokens_in = false;                    // `in` holds (B, N, H) feature rows (transformer.py:534-535), not 5-D patches
     const float *in[3] = {}, *pos[3] = {}, *scales[3] = {};      // per image (the embedding launches read slot 1 with nimg = 1 too: NULL)
     int B = 0, N = 0;                          // B items of N patches per image, or
+    bool varlen = false;                       //   variable length (a NULL count array is refused by submit(), so the entry says which it is)
     const int32_t* n_img[2] = {};              //   variable length (HOST arrays): item i of image k has n_img[k][i] patches -- image 0 holds rg.G
     int64_t sumN[2] = {};                      //   items with REF_GROUP, else B; vtq_forward_varlen passes ONE array for both images.  Their sums
     int maxN = 0;                              //   per image and the maximum over all
@@ -540,7 +541,9 @@ struct Call {
     // vtq_forward_vit: encoder_norm of `rows` rows per image; per-layer residual rows and attention probabilities (optional)
     float *out = nullptr, *states = nullptr, *probs = nullptr;
     int rows = 0;
-    float *rollout_out = nullptr, *last_attention_out = nullptr;   // vtq_forward_rollout ("rollout on" = rollout_out != NULL)
+    bool rollout = false;                      // the caller asked for the maps (the *_rollout* entries): rollout_out [+ last_attention_out]
+    float *rollout_out = nullptr, *last_attention_out = nullptr;
+    bool null_arrays = false;                  // the triplet entries: a pointer array itself was NULL
     RefGroup rg{REF_PAIRS, 0, nullptr, nullptr};
     bool calibrating = false;                  // fp8 mode: this forward chooses the activation scales (set by forward(), see kSPatch)
 };
@@ -595,7 +598,7 @@ int run_encoder(vtq_engine* e, const Call& call, const Geometry& g, hipStream_t 
     auto lnv = [&](int ld) { return View{e->lnbuf, e->ln_plane, ld}; };
     auto bigv = [&](int ld) { return View{e->big, e->big_plane, ld}; };
     // layer i's QKV planes: in `big`, or (vtq_forward_rollout) in a buffer of the layer's own, where Q and K survive the forward
-    const bool rollout = call.rollout_out != nullptr;
+    const bool rollout = call.rollout;
     auto qkvv = [&](int i) { return rollout ? View{e->ro_qkv[i], e->ro_plane, 3 * H} : bigv(3 * H); };
     float *xcls = e->xcls, *lncls = e->lncls, *qcls = e->qcls;
     const int64_t trace_stride = (int64_t)g.nseq * T * H;
@@ -830,6 +833,8 @@ int all_loaded(const vtq_engine* e, const char* who) {
     return 0;
 }
 
+int null_handle(const char* who) { return fail("%s: null handle", who); }
+
 }  // namespace
 
 extern "C" {
@@ -961,13 +966,13 @@ int vtq_reserve(vtq_handle e, int32_t B, int32_t N) {
 }
 
 int vtq_set_token_trace(vtq_handle e, float* buf) {
-    if (!e) return fail("null handle");
+    if (!e) return null_handle("vtq_set_token_trace");
     e->trace = buf;
     return 0;
 }
 
 int vtq_set_iqa_token(vtq_handle e, int32_t token) {
-    if (!e) return fail("null handle");
+    if (!e) return null_handle("vtq_set_iqa_token");
     if (token < 0 || token > e->cfg.num_extra_tokens)
         return fail("vtq_set_iqa_token: token %d outside [0, %d] (CLS + num_extra_tokens register tokens)", (int)token, (int)e->cfg.num_extra_tokens);
     e->iqa_token = token;
@@ -975,7 +980,7 @@ int vtq_set_iqa_token(vtq_handle e, int32_t token) {
 }
 
 int vtq_debug_stop_after(vtq_handle e, int32_t stage) {
-    if (!e) return fail("null handle");
+    if (!e) return null_handle("vtq_debug_stop_after");
     e->dbg_stop = stage;
     return 0;
 }
@@ -1043,7 +1048,7 @@ int vtq_debug_mfma_stream(int32_t f16, int32_t data, double warm_s, double timed
 }
 
 int vtq_profile_enable(vtq_handle e, uint32_t mask) {
-    if (!e) return fail("null handle");
+    if (!e) return null_handle("vtq_profile_enable");
     e->prof_mask = mask;
     return 0;
 }
@@ -1110,7 +1115,7 @@ static int finish(vtq_engine* e, const Call& c, const Geometry& g, hipStream_t s
         const int* row0 = prune ? nullptr : vl.row0;
         if (mode == REF_ENCODE) {
             HIP_TRY(launch_export_rows(rows, stride, c.rg.rows, B, H, s, e->err_flag, row0));
-            return c.rollout_out ? run_rollout(e, c, g, s, vl) : 0;
+            return c.rollout ? run_rollout(e, c, g, s, vl) : 0;
         }
         if (mode == REF_GROUP)
             HIP_TRY(launch_group_diff(rows, stride, rows + (row0 ? 0 : B0 * stride), stride, vl.ref_index, B, e->encw, e->encb, gamma, d, H, hp, s, e->err_flag,
@@ -1121,17 +1126,17 @@ static int finish(vtq_engine* e, const Call& c, const Geometry& g, hipStream_t s
         else HIP_TRY(launch_final_diff(e->x + (int64_t)e->iqa_token * H, e->encw, e->encb, gamma, d, B, ndist, g.sm, H, hp, s, e->err_flag, vl.row0));
         if (run_head(e, d, HB, c.q_out, s, true)) return 1;
     }
-    if (c.rollout_out && run_rollout(e, c, g, s, vl)) return 1;
+    if (c.rollout && run_rollout(e, c, g, s, vl)) return 1;
     if (c.calibrating) e->fp8_calibrated = true;
     return 0;
 }
 
-// THE forward path: every entry checks its own arguments, describes its batch as a Call and ends here.  Each step is stated once; what
+// THE forward path: every entry describes its batch as a Call, submit() refuses what has to be refused, and the call ends here.  Each step is stated once; what
 // differs between the entries is read off the Call where it differs.
 //   REF_GROUP: image 0 holds rg.G sequences instead of B;  the variable-length entries (n_img[0] != NULL): every sequence at its own length
 static int forward(vtq_engine* e, Call c, void* stream) {
     const vtq_config& cfg = e->cfg;
-    const bool varlen = c.n_img[0] != nullptr, rollout = c.rollout_out != nullptr, tokens_in = c.tokens_in, use_scales = cfg.num_scales > 1;
+    const bool varlen = c.n_img[0] != nullptr, rollout = c.rollout, tokens_in = c.tokens_in, use_scales = cfg.num_scales > 1;
     const int nimg = c.nimg, B = c.B, mode = c.rg.mode, H = e->H, T = e->T;
     const int B0 = mode == REF_GROUP ? c.rg.G : B;           // sequences of image 0
     const int nseq = B0 + (nimg - 1) * B;
@@ -1234,18 +1239,68 @@ static int forward(vtq_engine* e, Call c, void* stream) {
     return finish(e, c, g, s, prune, vl);
 }
 
-// The uniform entries (every image B -- image 0 of REF_GROUP: rg.G -- sequences of N patches): the checks they share, behind their own
-static int forward_uniform(vtq_handle e, const Call& c, void* stream) {
-    if (!e) return fail("vtq_forward: null handle");
-    if (c.tokens_in && e->fp8) return fail("vtq_forward_tokens: the fp8 experiment has no pre-embedded input path");
+// What stands between a scoring entry and forward(): every refusal, stated once.  Which of them apply is read off the Call; the order is
+//   1. the batch description (it needs no handle): a NULL count array, a NULL ref_index, the extents, a count < 1, a ref_index out of range,
+//      a rollout asked for with a NULL rollout_out
+//   2. the handle: NULL, the fp8 experiment's engine, a set token trace
+//   3. a NULL tensor, a NULL output
+//   4. rollout calls: vtq_debug_stop_after, the sequence cap (the combine launch's grid)
+//   5. variable-length calls: the sums and the maximum of the counts, the kernels' 32-bit row index
+//   6. the scale rule, the weights -- then forward()
+static int submit(vtq_handle e, Call c, void* stream) {
+    const char* who = c.who;
+    const int mode = c.rg.mode, B = c.B, G = c.rg.G, N = c.N;
+    const bool pairs = mode == REF_PAIRS, group = mode == REF_GROUP, indexed = group || mode == REF_CACHED;
+    const int B0 = group ? G : B, M = mode == REF_ENCODE ? 1 : B, lists = group ? 2 : 1;       // vtq_forward_varlen: ONE count array
+    const char* const counts[2] = {group ? "n_ref" : "n_patches", "n_dist"};
+    // ---- 1
+    for (int k = 0; c.varlen && k < lists; ++k)
+        if (!c.n_img[k]) return fail("%s: null %s", who, counts[k]);
+    if (indexed && !c.rg.ref_index) return fail("%s: null ref_index", who);
+    if (pairs && (B < 1 || (!c.varlen && N < 1))) return c.varlen ? fail("%s: B=%d", who, B) : fail("%s: B=%d N=%d", who, B, N);
+    if (!pairs && (G < 1 || M < 1 || (!c.varlen && N < 1)))
+        return c.varlen ? fail("%s: G=%d M=%d", who, G, M) : fail("%s: G=%d M=%d N=%d", who, G, M, N);
+    for (int k = 0; c.varlen && k < lists; ++k)
+        for (int i = 0, n = k == 0 ? B0 : B; i < n; ++i)
+            if (c.n_img[k][i] < 1)
+                return fail("%s: %s[%d] = %d (every %s needs at least one patch)", who, counts[k], i, (int)c.n_img[k][i], pairs ? "pair" : "image");
+    for (int m = 0; indexed && m < B; ++m)
+        if (c.rg.ref_index[m] < 0 || c.rg.ref_index[m] >= G) return fail("%s: ref_index[%d] = %d outside [0, %d)", who, m, (int)c.rg.ref_index[m], G);
+    if (c.rollout && !c.rollout_out) return fail("%s: null rollout_out", who);
+    // ---- 2.  The fp8 experiment scores (ref, dist) pairs and triplets of patches, nothing else
+    if (!e) return null_handle(who);
+    if (e->fp8 && (!pairs || c.nimg == 1 || c.varlen || c.rollout)) return fail("%s: not available for the fp8 experiment's engine", who);
+    if (e->fp8 && c.tokens_in) return fail("%s: the fp8 experiment has no pre-embedded input path", who);
+    if (e->trace && (c.rollout || c.varlen || !pairs))
+        return fail("%s: a token trace buffer is set (vtq_set_token_trace): %s", who, !pairs ? "the trace layout is per batch of pairs"
+                    : c.varlen ? "the trace layout is per uniform batch" : "the trace tap runs the last layer in another form");
+    // ---- 3
+    const bool vit = pairs && c.nimg == 1;
+    if (c.null_arrays) return fail("%s: null argument", who);
     for (int k = 0; k < c.nimg; ++k)
-        if (!c.in[k] || !c.pos[k]) return fail("vtq_forward: null tensor");
-    if (!c.q_out && (c.nimg > 1 || c.rg.mode == REF_CACHED)) return fail("vtq_forward: null output");
-    if (c.B < 1 || c.N < 1) return fail("vtq_forward: B=%d N=%d", c.B, c.N);
+        if (!c.in[k] || !c.pos[k]) return fail(vit ? "%s: null input" : "%s: null tensor", who);
+    if (mode == REF_CACHED && !c.rg.rows) return fail("%s: null tensor", who);
+    if (!(vit ? c.out : mode == REF_ENCODE ? c.rg.rows : c.q_out)) return fail("%s: null output", who);
+    // ---- 4
+    const int64_t nseq = B0 + (int64_t)(c.nimg - 1) * B;
+    if (c.rollout && e->dbg_stop >= 0) return fail("%s: vtq_debug_stop_after is set", who);
+    if (c.rollout && nseq > 65535) return fail("%s: %lld sequences (a rollout call takes at most 65535)", who, (long long)nseq);
+    // ---- 5
+    if (c.varlen) {
+        for (int k = 0; k < c.nimg; ++k)
+            for (int i = 0, n = k == 0 ? B0 : B; i < n; ++i) {
+                c.sumN[k] += c.n_img[k][i];
+                if (c.n_img[k][i] > c.maxN) c.maxN = c.n_img[k][i];
+            }
+        const int64_t rows = c.sumN[0] + c.sumN[1] + nseq * e->T;
+        if (rows + 512 > INT32_MAX / 4 || nseq * (c.maxN + e->T) + 512 > INT32_MAX / 4)
+            return fail("%s: %lld token rows exceed the 32-bit row index of the kernels", who, (long long)rows);
+    }
+    // ---- 6
     if (e->cfg.num_scales > 1)
         for (int k = 0; k < c.nimg; ++k)
             if (!c.scales[k]) return fail("Model uses scale embedding but scales is passed as None.");   // transformer.py:547-548
-    if (all_loaded(e, "vtq_forward")) return 1;
+    if (all_loaded(e, who)) return 1;
     return forward(e, c, stream);
 }
 
@@ -1314,370 +1369,197 @@ int vtq_fp8_reset(vtq_handle e) {
 }
 #endif
 
+// ---- the scoring entries (include/vtamiq_hip.h): each describes its request as a Call -- the constructors above and below, plus the few
+// fields that differ -- and hands it to submit()
+static Call call_triplet(const char* who, bool tokens_in, const float* const* in, const float* const* pos, const float* const* scales, int32_t B,
+                         int32_t N, float* q_out) {
+    static const float* const none[3] = {};
+    Call c = call_images(who, tokens_in, 3, in ? in : none, pos ? pos : none, scales, B, N, q_out);
+    c.null_arrays = !in || !pos;
+    return c;
+}
+// one-to-many scoring, every reference encoded once: G references + M distorted images in one batch; G references alone, their rows to the
+// caller's cache; M distorted images against the cached rows
+static Call call_group(const char* who, bool tokens_in, const float* in_ref, const float* in_dist, const float* pos_ref, const float* pos_dist,
+                       const float* scales_ref, const float* scales_dist, int32_t G, int32_t M, int32_t N, const int32_t* ref_index, float* q_out) {
+    Call c = call_pair(who, tokens_in, in_ref, in_dist, pos_ref, pos_dist, scales_ref, scales_dist, M, N, q_out);
+    c.rg = RefGroup{REF_GROUP, G, ref_index, nullptr};
+    return c;
+}
+static Call call_encode(const char* who, int32_t tokens_in, const float* in, const float* pos, const float* scales, int32_t G, int32_t N,
+                        float* ref_rows) {
+    Call c = call_single(who, tokens_in, in, pos, scales, G, N, nullptr);
+    c.rg = RefGroup{REF_ENCODE, G, nullptr, ref_rows};
+    return c;
+}
+static Call call_cached(const char* who, const float* ref_rows, int32_t G, int32_t tokens_in, const float* in, const float* pos,
+                        const float* scales, int32_t M, int32_t N, const int32_t* ref_index, float* q_out) {
+    Call c = call_single(who, tokens_in, in, pos, scales, M, N, q_out);
+    c.rg = RefGroup{REF_CACHED, G, ref_index, const_cast<float*>(ref_rows)};
+    return c;
+}
+// Images of different patch counts: host count arrays in place of N.  Sequences are packed back to back at their own length, image 0's, then
+// image 1's, the packed patch rows likewise (image, item, patch).  Every kernel is row- or sequence-independent and the GEMMs are bitwise
+// independent of M, so a sequence has the bits of the uniform entry on that item alone.
+static Call with_counts(Call c, const int32_t* n0, const int32_t* n1) {
+    c.varlen = true; c.n_img[0] = n0; c.n_img[1] = n1;
+    return c;
+}
+// The rollout forms: the maps of every sequence the call encodes, in call order (image 0's, then image 1's); last_attention_out may be NULL
+static Call with_rollout(Call c, float* rollout_out, float* last_attention_out) {
+    c.rollout = true; c.rollout_out = rollout_out; c.last_attention_out = last_attention_out;
+    return c;
+}
+
 int vtq_forward(vtq_handle e, const float* patches_ref, const float* patches_dist, const float* pos_ref, const float* pos_dist,
                 const float* scales_ref, const float* scales_dist, int32_t B, int32_t N, float* q_out, void* stream) {
-    return forward_uniform(e, call_pair("vtq_forward", false, patches_ref, patches_dist, pos_ref, pos_dist, scales_ref, scales_dist, B, N, q_out), stream);
+    return submit(e, call_pair("vtq_forward", false, patches_ref, patches_dist, pos_ref, pos_dist, scales_ref, scales_dist, B, N, q_out), stream);
 }
 
 int vtq_forward_tokens(vtq_handle e, const float* feats_ref, const float* feats_dist, const float* pos_ref, const float* pos_dist,
                        const float* scales_ref, const float* scales_dist, int32_t B, int32_t N, float* q_out, void* stream) {
-    return forward_uniform(e, call_pair("vtq_forward_tokens", true, feats_ref, feats_dist, pos_ref, pos_dist, scales_ref, scales_dist, B, N, q_out), stream);
-}
-
-// vtq_forward with the attention rollout of the consumed token (include/vtamiq_hip.h).  What it does not offer is refused before any launch
-static int forward_rollout(const char* who, vtq_handle e, bool tokens_in, const float* in_ref, const float* in_dist, const float* pos_ref,
-                           const float* pos_dist, const float* scales_ref, const float* scales_dist, int32_t B, int32_t N, float* q_out,
-                           float* rollout_out, float* last_attention_out, void* stream) {
-    if (!e) return fail("%s: null handle", who);
-    if (e->fp8) return fail("%s: not available for the fp8 experiment's engine", who);
-    if (e->trace) return fail("%s: a token trace buffer is set (vtq_set_token_trace): the trace tap runs the last layer in another form", who);
-    if (!rollout_out) return fail("%s: null rollout_out", who);
-    if (B < 1 || N < 1 || B > 32767) return fail("%s: B=%d N=%d", who, (int)B, (int)N);
-    if (e->dbg_stop >= 0) return fail("%s: vtq_debug_stop_after is set", who);
-    Call c = call_pair(who, tokens_in, in_ref, in_dist, pos_ref, pos_dist, scales_ref, scales_dist, B, N, q_out);
-    c.rollout_out = rollout_out;
-    c.last_attention_out = last_attention_out;
-    return forward_uniform(e, c, stream);
+    return submit(e, call_pair("vtq_forward_tokens", true, feats_ref, feats_dist, pos_ref, pos_dist, scales_ref, scales_dist, B, N, q_out), stream);
 }
 
 int vtq_forward_rollout(vtq_handle e, const float* patches_ref, const float* patches_dist, const float* pos_ref, const float* pos_dist,
                         const float* scales_ref, const float* scales_dist, int32_t B, int32_t N, float* q_out, float* rollout_out,
                         float* last_attention_out, void* stream) {
-    return forward_rollout("vtq_forward_rollout", e, false, patches_ref, patches_dist, pos_ref, pos_dist, scales_ref, scales_dist, B, N, q_out,
-                           rollout_out, last_attention_out, stream);
+    return submit(e, with_rollout(call_pair("vtq_forward_rollout", false, patches_ref, patches_dist, pos_ref, pos_dist, scales_ref, scales_dist, B, N,
+                                            q_out), rollout_out, last_attention_out), stream);
 }
 
 int vtq_forward_rollout_tokens(vtq_handle e, const float* feats_ref, const float* feats_dist, const float* pos_ref, const float* pos_dist,
                                const float* scales_ref, const float* scales_dist, int32_t B, int32_t N, float* q_out, float* rollout_out,
                                float* last_attention_out, void* stream) {
-    return forward_rollout("vtq_forward_rollout_tokens", e, true, feats_ref, feats_dist, pos_ref, pos_dist, scales_ref, scales_dist, B, N, q_out,
-                           rollout_out, last_attention_out, stream);
-}
-
-// The rollout form of the variable-length and one-to-many entries: the caller's two outputs (last_attention may be NULL); the base entries
-// pass no RolloutOut.  What a rollout form refuses beyond its base entry, with no launch: a NULL rollout_out -- checked with the batch
-// description, ahead of the handle -- and, with the handle, vtq_debug_stop_after and more sequences than the combine launch's grid takes.
-// (The fp8 engine and a token trace are refused by every one of these entries anyway.)
-struct RolloutOut { float *rollout, *last_attention; };
-static int check_rollout_out(const char* who, const RolloutOut* ro) { return ro && !ro->rollout ? fail("%s: null rollout_out", who) : 0; }
-static int check_rollout_handle(const char* who, vtq_handle e, const RolloutOut* ro, int64_t nseq) {
-    if (!ro) return 0;
-    if (e->dbg_stop >= 0) return fail("%s: vtq_debug_stop_after is set", who);
-    if (nseq > 65535) return fail("%s: %lld sequences (a rollout call takes at most 65535)", who, (long long)nseq);
-    return 0;
-}
-static void set_rollout(Call& c, const RolloutOut* ro) {
-    if (ro) { c.rollout_out = ro->rollout; c.last_attention_out = ro->last_attention; }
+    return submit(e, with_rollout(call_pair("vtq_forward_rollout_tokens", true, feats_ref, feats_dist, pos_ref, pos_dist, scales_ref, scales_dist, B,
+                                            N, q_out), rollout_out, last_attention_out), stream);
 }
 
 size_t vtq_rollout_workspace_bytes(vtq_handle e, int32_t B, int32_t N) { return (e && B >= 1 && N >= 1) ? ws_bytes(rollout_workspace(e, B, N)) : 0; }
 
-// The variable-length entries (n_img set, every count checked >= 1): what they share behind their own argument checks -- the sums and the
-// maximum of the counts, the kernels' 32-bit row index, the scale rule, the weights
-static int forward_ragged(vtq_handle e, Call c, void* stream) {
-    const int B0 = c.rg.mode == REF_GROUP ? c.rg.G : c.B, nseq = B0 + (c.nimg - 1) * c.B;
-    for (int k = 0; k < c.nimg; ++k)
-        for (int i = 0, n = k == 0 ? B0 : c.B; i < n; ++i) {
-            c.sumN[k] += c.n_img[k][i];
-            if (c.n_img[k][i] > c.maxN) c.maxN = c.n_img[k][i];
-        }
-    const int64_t rows = c.sumN[0] + c.sumN[1] + (int64_t)nseq * e->T;
-    if (rows + 512 > INT32_MAX / 4 || (int64_t)nseq * (c.maxN + e->T) + 512 > INT32_MAX / 4)
-        return fail("%s: %lld token rows exceed the 32-bit row index of the kernels", c.who, (long long)rows);
-    if (e->cfg.num_scales > 1)
-        for (int k = 0; k < c.nimg; ++k)
-            if (!c.scales[k]) return fail("Model uses scale embedding but scales is passed as None.");   // transformer.py:547-548
-    if (all_loaded(e, c.who)) return 1;
-    return forward(e, c, stream);
-}
-
-// B pairs of different patch counts through one launch sequence (include/vtamiq_hip.h).  Layout: sequences packed back to back at their
-// own length, all reference sequences, then all distorted ones; the packed patch rows likewise (image, pair, patch).  Every kernel is
-// row- or sequence-independent and the GEMMs are bitwise independent of M, so pair b's score has the bits of a B = 1 call on pair b.
-static int forward_varlen(const char* who, vtq_handle e, const float* patches_ref, const float* patches_dist, const float* pos_ref,
-                          const float* pos_dist, const float* scales_ref, const float* scales_dist, int32_t B, const int32_t* n_patches, float* q_out,
-                          const RolloutOut* ro, void* stream) {
-    // the batch description first (it needs no handle), then the handle, then what the handle decides
-    if (!n_patches) return fail("%s: null n_patches", who);
-    if (B < 1) return fail("%s: B=%d", who, (int)B);
-    for (int b = 0; b < B; ++b)
-        if (n_patches[b] < 1) return fail("%s: n_patches[%d] = %d (every pair needs at least one patch)", who, b, (int)n_patches[b]);
-    if (check_rollout_out(who, ro)) return 1;
-    if (!e) return fail("%s: null handle", who);
-    if (e->fp8) return fail("%s: not available for the fp8 experiment's engine", who);
-    if (!patches_ref || !patches_dist || !pos_ref || !pos_dist) return fail("%s: null tensor", who);
-    if (!q_out) return fail("%s: null output", who);
-    if (e->trace) return fail("%s: a token trace buffer is set (vtq_set_token_trace): the trace layout is per uniform batch", who);
-    if (check_rollout_handle(who, e, ro, 2 * (int64_t)B)) return 1;
-    Call c = call_pair(who, false, patches_ref, patches_dist, pos_ref, pos_dist, scales_ref, scales_dist, B, 0, q_out);
-    c.n_img[0] = c.n_img[1] = n_patches;
-    set_rollout(c, ro);
-    return forward_ragged(e, c, stream);
-}
-
 int vtq_forward_varlen(vtq_handle e, const float* patches_ref, const float* patches_dist, const float* pos_ref, const float* pos_dist,
                        const float* scales_ref, const float* scales_dist, int32_t B, const int32_t* n_patches, float* q_out, void* stream) {
-    return forward_varlen("vtq_forward_varlen", e, patches_ref, patches_dist, pos_ref, pos_dist, scales_ref, scales_dist, B, n_patches, q_out, nullptr,
-                          stream);
+    return submit(e, with_counts(call_pair("vtq_forward_varlen", false, patches_ref, patches_dist, pos_ref, pos_dist, scales_ref, scales_dist, B, 0,
+                                           q_out), n_patches, n_patches), stream);
 }
 
-// The same with the attention rollout of every sequence, packed in call order: all reference sequences, then all distorted ones
 int vtq_forward_varlen_rollout(vtq_handle e, const float* patches_ref, const float* patches_dist, const float* pos_ref, const float* pos_dist,
                                const float* scales_ref, const float* scales_dist, int32_t B, const int32_t* n_patches, float* q_out,
                                float* rollout_out, float* last_attention_out, void* stream) {
-    const RolloutOut ro{rollout_out, last_attention_out};
-    return forward_varlen("vtq_forward_varlen_rollout", e, patches_ref, patches_dist, pos_ref, pos_dist, scales_ref, scales_dist, B, n_patches, q_out,
-                          &ro, stream);
-}
-
-static int forward_triplet(vtq_handle e, const char* who, bool tokens_in, const float* const* in, const float* const* pos,
-                           const float* const* scales, int32_t B, int32_t N, float* q_out, void* stream) {
-    if (!in || !pos) return fail("%s: null argument", who);
-    return forward_uniform(e, call_images(who, tokens_in, 3, in, pos, scales, B, N, q_out), stream);
+    return submit(e, with_rollout(with_counts(call_pair("vtq_forward_varlen_rollout", false, patches_ref, patches_dist, pos_ref, pos_dist, scales_ref,
+                                                        scales_dist, B, 0, q_out), n_patches, n_patches), rollout_out, last_attention_out), stream);
 }
 
 int vtq_forward_pairwise(vtq_handle e, const float* const* patches, const float* const* pos, const float* const* scales, int32_t B,
                          int32_t N, float* q_out, void* stream) {
-    return forward_triplet(e, "vtq_forward_pairwise", false, patches, pos, scales, B, N, q_out, stream);
+    return submit(e, call_triplet("vtq_forward_pairwise", false, patches, pos, scales, B, N, q_out), stream);
 }
 
 int vtq_forward_pairwise_tokens(vtq_handle e, const float* const* feats, const float* const* pos, const float* const* scales, int32_t B,
                                 int32_t N, float* q_out, void* stream) {
-    return forward_triplet(e, "vtq_forward_pairwise_tokens", true, feats, pos, scales, B, N, q_out, stream);
+    return submit(e, call_triplet("vtq_forward_pairwise_tokens", true, feats, pos, scales, B, N, q_out), stream);
 }
 
 int vtq_forward_vit(vtq_handle e, const float* in, int32_t tokens_in, const float* pos, const float* scales, int32_t B, int32_t N,
                     int32_t all_tokens, float* out, float* states, float* probs, void* stream) {
-    if (!e) return fail("vtq_forward_vit: null handle");
-    if (e->fp8) return fail("vtq_forward_vit: not available for the fp8 experiment's engine");
-    if (!in || !pos) return fail("vtq_forward_vit: null input");
-    if (!out) return fail("vtq_forward_vit: null output");
-    if (B < 1 || N < 1) return fail("vtq_forward_vit: B=%d N=%d", (int)B, (int)N);
     Call c = call_single("vtq_forward_vit", tokens_in, in, pos, scales, B, N, nullptr);
     c.out = out;
     c.states = states;
     c.probs = probs;
-    c.rows = all_tokens ? N + e->T : e->T;
-    return forward_uniform(e, c, stream);
-}
-
-// ---- one-to-many scoring: every reference encoded once (include/vtamiq_hip.h) ---------------------------------------------------------
-// The batch description first (it needs no handle), then the handle, then what the handle decides -- as vtq_forward_varlen
-static int check_group(const char* who, int32_t G, int32_t M, int32_t N, const int32_t* ref_index, bool need_index) {
-    if (need_index && !ref_index) return fail("%s: null ref_index", who);
-    if (G < 1 || M < 1 || N < 1) return fail("%s: G=%d M=%d N=%d", who, (int)G, (int)M, (int)N);
-    if (ref_index)
-        for (int m = 0; m < M; ++m)
-            if (ref_index[m] < 0 || ref_index[m] >= G) return fail("%s: ref_index[%d] = %d outside [0, %d)", who, m, (int)ref_index[m], (int)G);
-    return 0;
-}
-
-static int check_group_handle(const char* who, vtq_handle e) {
-    if (!e) return fail("%s: null handle", who);
-    if (e->fp8) return fail("%s: not available for the fp8 experiment's engine", who);
-    if (e->trace) return fail("%s: a token trace buffer is set (vtq_set_token_trace): the trace layout is per batch of pairs", who);
-    return 0;
-}
-
-static int forward_group(const char* who, vtq_handle e, bool tokens_in, const float* in_ref, const float* in_dist, const float* pos_ref,
-                         const float* pos_dist, const float* scales_ref, const float* scales_dist, int32_t G, int32_t M, int32_t N,
-                         const int32_t* ref_index, float* q_out, const RolloutOut* ro, void* stream) {
-    if (check_group(who, G, M, N, ref_index, true) || check_rollout_out(who, ro) || check_group_handle(who, e)) return 1;
-    if (!in_ref || !in_dist || !pos_ref || !pos_dist) return fail("%s: null tensor", who);
-    if (!q_out) return fail("%s: null output", who);
-    if (check_rollout_handle(who, e, ro, (int64_t)G + M)) return 1;
-    Call c = call_pair(who, tokens_in, in_ref, in_dist, pos_ref, pos_dist, scales_ref, scales_dist, M, N, q_out);
-    c.rg = RefGroup{REF_GROUP, G, ref_index, nullptr};
-    set_rollout(c, ro);
-    return forward_uniform(e, c, stream);
+    c.rows = e ? (all_tokens ? N + e->T : e->T) : 0;          // (a NULL handle is refused by submit())
+    return submit(e, c, stream);
 }
 
 int vtq_forward_group(vtq_handle e, const float* patches_ref, const float* patches_dist, const float* pos_ref, const float* pos_dist,
                       const float* scales_ref, const float* scales_dist, int32_t G, int32_t M, int32_t N, const int32_t* ref_index,
                       float* q_out, void* stream) {
-    return forward_group("vtq_forward_group", e, false, patches_ref, patches_dist, pos_ref, pos_dist, scales_ref, scales_dist, G, M, N, ref_index,
-                         q_out, nullptr, stream);
+    return submit(e, call_group("vtq_forward_group", false, patches_ref, patches_dist, pos_ref, pos_dist, scales_ref, scales_dist, G, M, N, ref_index,
+                                q_out), stream);
 }
 
 int vtq_forward_group_tokens(vtq_handle e, const float* feats_ref, const float* feats_dist, const float* pos_ref, const float* pos_dist,
                              const float* scales_ref, const float* scales_dist, int32_t G, int32_t M, int32_t N, const int32_t* ref_index,
                              float* q_out, void* stream) {
-    return forward_group("vtq_forward_group_tokens", e, true, feats_ref, feats_dist, pos_ref, pos_dist, scales_ref, scales_dist, G, M, N, ref_index,
-                         q_out, nullptr, stream);
+    return submit(e, call_group("vtq_forward_group_tokens", true, feats_ref, feats_dist, pos_ref, pos_dist, scales_ref, scales_dist, G, M, N, ref_index,
+                                q_out), stream);
 }
 
-// The rollout forms: rollout_out [G + M][S], last_attention_out [G + M][h][S], the references first
 int vtq_forward_group_rollout(vtq_handle e, const float* patches_ref, const float* patches_dist, const float* pos_ref, const float* pos_dist,
                               const float* scales_ref, const float* scales_dist, int32_t G, int32_t M, int32_t N, const int32_t* ref_index,
                               float* q_out, float* rollout_out, float* last_attention_out, void* stream) {
-    const RolloutOut ro{rollout_out, last_attention_out};
-    return forward_group("vtq_forward_group_rollout", e, false, patches_ref, patches_dist, pos_ref, pos_dist, scales_ref, scales_dist, G, M, N,
-                         ref_index, q_out, &ro, stream);
+    return submit(e, with_rollout(call_group("vtq_forward_group_rollout", false, patches_ref, patches_dist, pos_ref, pos_dist, scales_ref, scales_dist,
+                                             G, M, N, ref_index, q_out), rollout_out, last_attention_out), stream);
 }
 
 int vtq_forward_group_rollout_tokens(vtq_handle e, const float* feats_ref, const float* feats_dist, const float* pos_ref, const float* pos_dist,
                                      const float* scales_ref, const float* scales_dist, int32_t G, int32_t M, int32_t N, const int32_t* ref_index,
                                      float* q_out, float* rollout_out, float* last_attention_out, void* stream) {
-    const RolloutOut ro{rollout_out, last_attention_out};
-    return forward_group("vtq_forward_group_rollout_tokens", e, true, feats_ref, feats_dist, pos_ref, pos_dist, scales_ref, scales_dist, G, M, N,
-                         ref_index, q_out, &ro, stream);
-}
-
-static int encode_reference(const char* who, vtq_handle e, const float* in, int32_t tokens_in, const float* pos, const float* scales, int32_t G,
-                            int32_t N, float* ref_rows, const RolloutOut* ro, void* stream) {
-    if (check_group(who, G, 1, N, nullptr, false) || check_rollout_out(who, ro) || check_group_handle(who, e)) return 1;
-    if (!in || !pos) return fail("%s: null tensor", who);
-    if (!ref_rows) return fail("%s: null output", who);
-    if (check_rollout_handle(who, e, ro, G)) return 1;
-    Call c = call_single(who, tokens_in, in, pos, scales, G, N, nullptr);
-    c.rg = RefGroup{REF_ENCODE, G, nullptr, ref_rows};
-    set_rollout(c, ro);
-    return forward_uniform(e, c, stream);
+    return submit(e, with_rollout(call_group("vtq_forward_group_rollout_tokens", true, feats_ref, feats_dist, pos_ref, pos_dist, scales_ref, scales_dist,
+                                             G, M, N, ref_index, q_out), rollout_out, last_attention_out), stream);
 }
 
 int vtq_encode_reference(vtq_handle e, const float* in, int32_t tokens_in, const float* pos, const float* scales, int32_t G, int32_t N,
                          float* ref_rows, void* stream) {
-    return encode_reference("vtq_encode_reference", e, in, tokens_in, pos, scales, G, N, ref_rows, nullptr, stream);
+    return submit(e, call_encode("vtq_encode_reference", tokens_in, in, pos, scales, G, N, ref_rows), stream);
 }
 
 int vtq_encode_reference_rollout(vtq_handle e, const float* in, int32_t tokens_in, const float* pos, const float* scales, int32_t G, int32_t N,
                                  float* ref_rows, float* rollout_out, float* last_attention_out, void* stream) {
-    const RolloutOut ro{rollout_out, last_attention_out};
-    return encode_reference("vtq_encode_reference_rollout", e, in, tokens_in, pos, scales, G, N, ref_rows, &ro, stream);
-}
-
-static int forward_cached(const char* who, vtq_handle e, const float* ref_rows, int32_t G, const float* in, int32_t tokens_in, const float* pos,
-                          const float* scales, int32_t M, int32_t N, const int32_t* ref_index, float* q_out, const RolloutOut* ro, void* stream) {
-    if (check_group(who, G, M, N, ref_index, true) || check_rollout_out(who, ro) || check_group_handle(who, e)) return 1;
-    if (!ref_rows || !in || !pos) return fail("%s: null tensor", who);
-    if (!q_out) return fail("%s: null output", who);
-    if (check_rollout_handle(who, e, ro, M)) return 1;
-    Call c = call_single(who, tokens_in, in, pos, scales, M, N, q_out);
-    c.rg = RefGroup{REF_CACHED, G, ref_index, const_cast<float*>(ref_rows)};
-    set_rollout(c, ro);
-    return forward_uniform(e, c, stream);
+    return submit(e, with_rollout(call_encode("vtq_encode_reference_rollout", tokens_in, in, pos, scales, G, N, ref_rows), rollout_out,
+                                  last_attention_out), stream);
 }
 
 int vtq_forward_cached(vtq_handle e, const float* ref_rows, int32_t G, const float* in, int32_t tokens_in, const float* pos, const float* scales,
                        int32_t M, int32_t N, const int32_t* ref_index, float* q_out, void* stream) {
-    return forward_cached("vtq_forward_cached", e, ref_rows, G, in, tokens_in, pos, scales, M, N, ref_index, q_out, nullptr, stream);
+    return submit(e, call_cached("vtq_forward_cached", ref_rows, G, tokens_in, in, pos, scales, M, N, ref_index, q_out), stream);
 }
 
 // the M distorted sequences' maps only: the cached references' come from vtq_encode_reference_rollout
 int vtq_forward_cached_rollout(vtq_handle e, const float* ref_rows, int32_t G, const float* in, int32_t tokens_in, const float* pos,
                                const float* scales, int32_t M, int32_t N, const int32_t* ref_index, float* q_out, float* rollout_out,
                                float* last_attention_out, void* stream) {
-    const RolloutOut ro{rollout_out, last_attention_out};
-    return forward_cached("vtq_forward_cached_rollout", e, ref_rows, G, in, tokens_in, pos, scales, M, N, ref_index, q_out, &ro, stream);
-}
-
-// ---- one-to-many scoring on images of different patch counts (include/vtamiq_hip.h) ------------------------------------------------------
-// Packed as vtq_forward_varlen packs: all G reference sequences, then all M distorted ones, each at its own length; the patch rows likewise.
-// Every kernel is row- or sequence-independent, so a sequence has the bits of the uniform entry on that image alone.
-static int check_counts(const char* who, const char* name, const int32_t* n, int32_t count) {
-    for (int i = 0; i < count; ++i)
-        if (n[i] < 1) return fail("%s: %s[%d] = %d (every image needs at least one patch)", who, name, i, (int)n[i]);
-    return 0;
-}
-
-// the batch description (it needs no handle): G references, M distorted images, ref_index where one is taken
-static int check_group_varlen(const char* who, int32_t G, int32_t M, const int32_t* ref_index, bool need_index) {
-    if (need_index && !ref_index) return fail("%s: null ref_index", who);
-    if (G < 1 || M < 1) return fail("%s: G=%d M=%d", who, (int)G, (int)M);
-    if (ref_index)
-        for (int m = 0; m < M; ++m)
-            if (ref_index[m] < 0 || ref_index[m] >= G) return fail("%s: ref_index[%d] = %d outside [0, %d)", who, m, (int)ref_index[m], (int)G);
-    return 0;
-}
-
-static int forward_group_varlen(const char* who, vtq_handle e, const float* patches_ref, const float* patches_dist, const float* pos_ref,
-                                const float* pos_dist, const float* scales_ref, const float* scales_dist, int32_t G, int32_t M, const int32_t* n_ref,
-                                const int32_t* n_dist, const int32_t* ref_index, float* q_out, const RolloutOut* ro, void* stream) {
-    if (!n_ref) return fail("%s: null n_ref", who);
-    if (!n_dist) return fail("%s: null n_dist", who);
-    if (check_group_varlen(who, G, M, ref_index, true) || check_counts(who, "n_ref", n_ref, G) || check_counts(who, "n_dist", n_dist, M)) return 1;
-    if (check_rollout_out(who, ro) || check_group_handle(who, e)) return 1;
-    if (!patches_ref || !patches_dist || !pos_ref || !pos_dist) return fail("%s: null tensor", who);
-    if (!q_out) return fail("%s: null output", who);
-    if (check_rollout_handle(who, e, ro, (int64_t)G + M)) return 1;
-    Call c = call_pair(who, false, patches_ref, patches_dist, pos_ref, pos_dist, scales_ref, scales_dist, M, 0, q_out);
-    c.rg = RefGroup{REF_GROUP, G, ref_index, nullptr};
-    c.n_img[0] = n_ref;
-    c.n_img[1] = n_dist;
-    set_rollout(c, ro);
-    return forward_ragged(e, c, stream);
+    return submit(e, with_rollout(call_cached("vtq_forward_cached_rollout", ref_rows, G, tokens_in, in, pos, scales, M, N, ref_index, q_out),
+                                  rollout_out, last_attention_out), stream);
 }
 
 int vtq_forward_group_varlen(vtq_handle e, const float* patches_ref, const float* patches_dist, const float* pos_ref, const float* pos_dist,
                              const float* scales_ref, const float* scales_dist, int32_t G, int32_t M, const int32_t* n_ref, const int32_t* n_dist,
                              const int32_t* ref_index, float* q_out, void* stream) {
-    return forward_group_varlen("vtq_forward_group_varlen", e, patches_ref, patches_dist, pos_ref, pos_dist, scales_ref, scales_dist, G, M, n_ref,
-                                n_dist, ref_index, q_out, nullptr, stream);
+    return submit(e, with_counts(call_group("vtq_forward_group_varlen", false, patches_ref, patches_dist, pos_ref, pos_dist, scales_ref, scales_dist, G,
+                                            M, 0, ref_index, q_out), n_ref, n_dist), stream);
 }
 
-// the rollout forms: both outputs packed over the call's sequences in call order (here: the G references, then the M distorted images)
 int vtq_forward_group_varlen_rollout(vtq_handle e, const float* patches_ref, const float* patches_dist, const float* pos_ref, const float* pos_dist,
                                      const float* scales_ref, const float* scales_dist, int32_t G, int32_t M, const int32_t* n_ref,
                                      const int32_t* n_dist, const int32_t* ref_index, float* q_out, float* rollout_out, float* last_attention_out,
                                      void* stream) {
-    const RolloutOut ro{rollout_out, last_attention_out};
-    return forward_group_varlen("vtq_forward_group_varlen_rollout", e, patches_ref, patches_dist, pos_ref, pos_dist, scales_ref, scales_dist, G, M,
-                                n_ref, n_dist, ref_index, q_out, &ro, stream);
-}
-
-static int encode_reference_varlen(const char* who, vtq_handle e, const float* patches, const float* pos, const float* scales, int32_t G,
-                                   const int32_t* n_patches, float* ref_rows, const RolloutOut* ro, void* stream) {
-    if (!n_patches) return fail("%s: null n_patches", who);
-    if (check_group_varlen(who, G, 1, nullptr, false) || check_counts(who, "n_patches", n_patches, G)) return 1;
-    if (check_rollout_out(who, ro) || check_group_handle(who, e)) return 1;
-    if (!patches || !pos) return fail("%s: null tensor", who);
-    if (!ref_rows) return fail("%s: null output", who);
-    if (check_rollout_handle(who, e, ro, G)) return 1;
-    Call c = call_single(who, 0, patches, pos, scales, G, 0, nullptr);
-    c.rg = RefGroup{REF_ENCODE, G, nullptr, ref_rows};
-    c.n_img[0] = n_patches;
-    set_rollout(c, ro);
-    return forward_ragged(e, c, stream);
+    return submit(e, with_rollout(with_counts(call_group("vtq_forward_group_varlen_rollout", false, patches_ref, patches_dist, pos_ref, pos_dist,
+                                                         scales_ref, scales_dist, G, M, 0, ref_index, q_out), n_ref, n_dist),
+                                  rollout_out, last_attention_out), stream);
 }
 
 int vtq_encode_reference_varlen(vtq_handle e, const float* patches, const float* pos, const float* scales, int32_t G, const int32_t* n_patches,
                                 float* ref_rows, void* stream) {
-    return encode_reference_varlen("vtq_encode_reference_varlen", e, patches, pos, scales, G, n_patches, ref_rows, nullptr, stream);
+    return submit(e, with_counts(call_encode("vtq_encode_reference_varlen", 0, patches, pos, scales, G, 0, ref_rows), n_patches, nullptr), stream);
 }
 
 int vtq_encode_reference_varlen_rollout(vtq_handle e, const float* patches, const float* pos, const float* scales, int32_t G,
                                         const int32_t* n_patches, float* ref_rows, float* rollout_out, float* last_attention_out, void* stream) {
-    const RolloutOut ro{rollout_out, last_attention_out};
-    return encode_reference_varlen("vtq_encode_reference_varlen_rollout", e, patches, pos, scales, G, n_patches, ref_rows, &ro, stream);
-}
-
-static int forward_cached_varlen(const char* who, vtq_handle e, const float* ref_rows, int32_t G, const float* patches, const float* pos,
-                                 const float* scales, int32_t M, const int32_t* n_patches, const int32_t* ref_index, float* q_out,
-                                 const RolloutOut* ro, void* stream) {
-    if (!n_patches) return fail("%s: null n_patches", who);
-    if (check_group_varlen(who, G, M, ref_index, true) || check_counts(who, "n_patches", n_patches, M)) return 1;
-    if (check_rollout_out(who, ro) || check_group_handle(who, e)) return 1;
-    if (!ref_rows || !patches || !pos) return fail("%s: null tensor", who);
-    if (!q_out) return fail("%s: null output", who);
-    if (check_rollout_handle(who, e, ro, M)) return 1;
-    Call c = call_single(who, 0, patches, pos, scales, M, 0, q_out);
-    c.rg = RefGroup{REF_CACHED, G, ref_index, const_cast<float*>(ref_rows)};
-    c.n_img[0] = n_patches;
-    set_rollout(c, ro);
-    return forward_ragged(e, c, stream);
+    return submit(e, with_rollout(with_counts(call_encode("vtq_encode_reference_varlen_rollout", 0, patches, pos, scales, G, 0, ref_rows), n_patches,
+                                              nullptr), rollout_out, last_attention_out), stream);
 }
 
 int vtq_forward_cached_varlen(vtq_handle e, const float* ref_rows, int32_t G, const float* patches, const float* pos, const float* scales, int32_t M,
                               const int32_t* n_patches, const int32_t* ref_index, float* q_out, void* stream) {
-    return forward_cached_varlen("vtq_forward_cached_varlen", e, ref_rows, G, patches, pos, scales, M, n_patches, ref_index, q_out, nullptr, stream);
+    return submit(e, with_counts(call_cached("vtq_forward_cached_varlen", ref_rows, G, 0, patches, pos, scales, M, 0, ref_index, q_out), n_patches,
+                                 nullptr), stream);
 }
 
 int vtq_forward_cached_varlen_rollout(vtq_handle e, const float* ref_rows, int32_t G, const float* patches, const float* pos, const float* scales,
                                       int32_t M, const int32_t* n_patches, const int32_t* ref_index, float* q_out, float* rollout_out,
                                       float* last_attention_out, void* stream) {
-    const RolloutOut ro{rollout_out, last_attention_out};
-    return forward_cached_varlen("vtq_forward_cached_varlen_rollout", e, ref_rows, G, patches, pos, scales, M, n_patches, ref_index, q_out, &ro,
-                                 stream);
+    return submit(e, with_rollout(with_counts(call_cached("vtq_forward_cached_varlen_rollout", ref_rows, G, 0, patches, pos, scales, M, 0, ref_index,
+                                                          q_out), n_patches, nullptr), rollout_out, last_attention_out), stream);
 }
 
 int vtq_input_errors(vtq_handle e, int32_t* flags, void* stream) {

@@ -45,6 +45,36 @@ def _ptr(t):
     return None if t is None else t.data_ptr()
 
 
+def _i32(v):
+    return (C.c_int32 * len(v))(*v)
+
+
+def _image_args(ts, tokens_in):
+    """(patches, pos, scales) of one list of single images as the single-image entries take them; tokens_in None: the `lengths=` forms,
+    which have no such flag."""
+    pt, pp, ps = ts
+    return (pt.data_ptr(), pp.data_ptr(), _ptr(ps)) if tokens_in is None else (pt.data_ptr(), int(tokens_in), pp.data_ptr(), _ptr(ps))
+
+
+# The C entry of each Python method, by (lengths given, rollout, pre-embedded input); a form the library does not offer has no key.  (The
+# single-image entries take pre-embedded input as a flag, not as an entry of its own.)
+_F, _T = False, True
+_ENTRIES = {
+    "pairs": {(_F, _F, _F): "vtq_forward", (_F, _F, _T): "vtq_forward_tokens", (_F, _T, _F): "vtq_forward_rollout",
+              (_F, _T, _T): "vtq_forward_rollout_tokens", (_T, _F, _F): "vtq_forward_varlen", (_T, _T, _F): "vtq_forward_varlen_rollout"},
+    "pairwise": {(_F, _F, _F): "vtq_forward_pairwise", (_F, _F, _T): "vtq_forward_pairwise_tokens"},
+    "group": {(_F, _F, _F): "vtq_forward_group", (_F, _F, _T): "vtq_forward_group_tokens", (_F, _T, _F): "vtq_forward_group_rollout",
+              (_F, _T, _T): "vtq_forward_group_rollout_tokens", (_T, _F, _F): "vtq_forward_group_varlen",
+              (_T, _T, _F): "vtq_forward_group_varlen_rollout"},
+    "encode": {(_F, _F, _F): "vtq_encode_reference", (_F, _F, _T): "vtq_encode_reference", (_F, _T, _F): "vtq_encode_reference_rollout",
+               (_F, _T, _T): "vtq_encode_reference_rollout", (_T, _F, _F): "vtq_encode_reference_varlen",
+               (_T, _T, _F): "vtq_encode_reference_varlen_rollout"},
+    "cached": {(_F, _F, _F): "vtq_forward_cached", (_F, _F, _T): "vtq_forward_cached", (_F, _T, _F): "vtq_forward_cached_rollout",
+               (_F, _T, _T): "vtq_forward_cached_rollout", (_T, _F, _F): "vtq_forward_cached_varlen",
+               (_T, _T, _F): "vtq_forward_cached_varlen_rollout"},
+}
+
+
 class Rollout(NamedTuple):
     """What VTAMIQ.forward_rollout returns beside the scores (index 0 = reference image, 1 = distorted image of each pair):
       rollout         (2, B, S) fp32: attention rollout of the token the score is read from, over the S = T + N tokens of each image
@@ -144,15 +174,16 @@ def _lengths(lengths, what: str):
     return [int(v) for v in lengths]
 
 
-def _ragged(t, lens, what: str, tail):
-    """One image's tensor of a `lengths=` call -- the images' rows concatenated, (sum(lengths), *tail), or a list of per-image (n_i, *tail)
-    tensors, concatenated here on their device -- as the one "batch" of sum(lengths) rows VTAMIQ._inputs checks.  None stays None."""
+def _ragged(t, lens, what: str, tail, noun: str = "image"):
+    """One image's tensor of a `lengths=` call -- the items' rows concatenated, (sum(lengths), *tail), or a list of per-item (n_i, *tail)
+    tensors, concatenated here on their device -- as the one "batch" of sum(lengths) rows VTAMIQ._inputs checks.  None stays None.  `noun`:
+    what an item is in the message (an image of the one-to-many entries, a pair of forward_varlen)."""
     if t is None:
         return None
     total = sum(lens)
     if isinstance(t, (list, tuple)):
         if len(t) != len(lens) or any(u.shape[0] != n for u, n in zip(t, lens)):
-            raise ValueError(f"{what}: a list must hold one tensor per image with lengths[i] rows each")
+            raise ValueError(f"{what}: a list must hold one tensor per {noun} with lengths[i] rows each")
         t = torch.cat([u.reshape(u.shape[0], *tail) for u in t], 0)
     if t.shape[0] != total or t.numel() != total * math.prod(tail):
         raise ValueError(f"{what}: {tuple(t.shape)} does not hold sum(lengths) = {total} rows of shape {tuple(tail)}")
@@ -681,8 +712,7 @@ class VTAMIQ(nn.Module):
             return device, B, N, tokens_in, prep(patches), prep(pos), prep(scales)
 
     def forward(self, patches, pos, scales, _trace: Optional[torch.Tensor] = None):
-        if self.training:
-            raise NotImplementedError(_TRAIN_MSG)
+        self._guard()
         patches_ref, patches_dist = patches
         device, B, N, tokens_in, (pr, pd), (qr, qd), (sr, sdist) = self._inputs((patches_ref, patches_dist), pos, scales)
         with torch.cuda.device(device):
@@ -693,7 +723,7 @@ class VTAMIQ(nn.Module):
                 if _trace is not None:
                     self._check(lib.vtq_set_token_trace(self._engine, _trace.data_ptr()))
                 try:
-                    self._check((lib.vtq_forward_tokens if tokens_in else lib.vtq_forward)(
+                    self._check(getattr(lib, _ENTRIES["pairs"][False, False, tokens_in])(
                         self._engine, pr.data_ptr(), pd.data_ptr(), qr.data_ptr(), qd.data_ptr(), _ptr(sr), _ptr(sdist), B, N, q.data_ptr(), stream))
                 finally:
                     if _trace is not None:
@@ -718,41 +748,14 @@ class VTAMIQ(nn.Module):
                    tensors or lists of per-pair tensors, 5-D patches only).  q has the bits of forward_varlen; Rollout.rollout is then
                    (ref, dist), each a list of B tensors (S_b,), S_b = T + lengths[b], and Rollout.last_attention (ref, dist) of lists of
                    (num_heads, S_b) -- views into one flat allocation per field.  Pair b's maps have the bits of forward_rollout on pair b
-                   alone; equal lengths give the bits of the call without lengths.
+                   alone; equal lengths give the bits of the call without lengths.  Integers only, as forward_varlen: floats with
+                   integral values and bools are refused.
         The one-to-many entries take `rollout=True` for the same maps (forward_group, encode_reference, forward_cached, with or without
         their `lengths=`); forward_varlen's maps are this call's `lengths=` form; forward_pairwise has no rollout variant."""
-        if self.training:
-            raise NotImplementedError(_TRAIN_MSG)
-        if self._FP8_EXPERIMENT:
-            raise NotImplementedError("forward_rollout is not available for the fp8 experiment's model")
+        self._guard("forward_rollout")
         if len(patches) != 2:
             raise ValueError("forward_rollout expects patches = (p_ref, p_dist)")
-        if lengths is not None:
-            device, B, lens, (pr, pd), (qr, qd), (sr, sdist) = self._varlen_inputs("forward_rollout", patches, pos, scales, lengths)
-            T, nh = self.spec.num_tokens, self.spec.num_heads
-            R = sum(lens) + B * T                     # token rows of one image's B sequences
-            with torch.cuda.device(device):
-                q = torch.empty(B, device=device, dtype=torch.float32)
-                roll = torch.empty(2 * R, device=device, dtype=torch.float32)
-                last = torch.empty(2 * R * nh, device=device, dtype=torch.float32)
-                n_arr = (C.c_int32 * B)(*lens)
-                stream = torch.cuda.current_stream(device).cuda_stream
-                self._launch_checked(device, lambda lib: self._check(lib.vtq_forward_varlen_rollout(
-                    self._engine, pr.data_ptr(), pd.data_ptr(), qr.data_ptr(), qd.data_ptr(), _ptr(sr), _ptr(sdist), B, n_arr, q.data_ptr(),
-                    roll.data_ptr(), last.data_ptr(), stream)))
-            maps, heads = _ragged_maps(roll, last, lens + lens, T, nh)          # all reference sequences, then all distorted ones
-            return q, Rollout((maps[:B], maps[B:]), (heads[:B], heads[B:]))
-        device, B, N, tokens_in, (pr, pd), (qr, qd), (sr, sdist) = self._inputs(tuple(patches), pos, scales)
-        S, nh = N + self.spec.num_tokens, self.spec.num_heads
-        with torch.cuda.device(device):
-            q = torch.empty(B, device=device, dtype=torch.float32)
-            roll = torch.empty(2, B, S, device=device, dtype=torch.float32)
-            last = torch.empty(2, B, nh, S, device=device, dtype=torch.float32)
-            stream = torch.cuda.current_stream(device).cuda_stream
-            self._launch_checked(device, lambda lib: self._check((lib.vtq_forward_rollout_tokens if tokens_in else lib.vtq_forward_rollout)(
-                self._engine, pr.data_ptr(), pd.data_ptr(), qr.data_ptr(), qd.data_ptr(), _ptr(sr), _ptr(sdist), B, N, q.data_ptr(),
-                roll.data_ptr(), last.data_ptr(), stream)))
-        return q, Rollout(roll, last)
+        return self._pairs("forward_rollout", patches, pos, scales, lengths, True)
 
     def rollout_workspace_bytes(self, B, N):
         """Bytes of engine workspace a forward_rollout call of (B pairs, N patches) holds beside workspace_bytes(B, N)."""
@@ -763,76 +766,50 @@ class VTAMIQ(nn.Module):
           patches  (ref, dist): each the pairs' patches concatenated, (sum(lengths), 3, P, P) -- or a list of B per-pair (n_b, 3, P, P) tensors,
                    concatenated here on the device
           pos      (ref, dist) of (sum(lengths), 2), scales (ref, dist) of (sum(lengths),) or None as in forward(); lists likewise
-          lengths  a sequence of ints or a CPU integer tensor (a CUDA tensor is refused: reading it would synchronise the stream)
+          lengths  a sequence of ints or a CPU integer tensor (a CUDA tensor is refused: reading it would synchronise the stream).  Integers
+                   only, as every other `lengths=`: floats with integral values and bools are refused
         Returns (q, None), q (B,) fp32: q[b] has the bits `self((ref_b, dist_b), ...)` gives for pair b alone, in every precision; equal
         lengths give the bits of forward().  The input / range policy ("auto", validate_inputs, check_inputs) is forward()'s."""
-        if self.training:
-            raise NotImplementedError(_TRAIN_MSG)
-        if self._FP8_EXPERIMENT:
-            raise NotImplementedError("forward_varlen is not available for the fp8 experiment's model")
-        device, B, lens, (pr, pd), (qr, qd), (sr, sdist) = self._varlen_inputs("forward_varlen", patches, pos, scales, lengths)
+        self._guard("forward_varlen")
+        return self._pairs("forward_varlen", patches, pos, scales, lengths, False)
+
+    def _pairs(self, what, patches, pos, scales, lengths, rollout):
+        """forward_varlen and forward_rollout: B (ref, dist) pairs -- with `lengths`, of lengths[b] patches each -- and their maps where asked for."""
+        lens = _lengths(lengths, "lengths") if lengths is not None else None
+        if lens is not None:
+            for name, ts in (("patches", patches), ("pos", pos), ("scales", scales)):
+                if ts is not None and len(ts) != 2:
+                    raise ValueError(f"{name} must be a (ref, dist) pair")
+            pos = pos if pos is not None else (None, None)
+            scales = scales if scales is not None else (None, None)
+            ref, dist = (self._ragged_image(what, patches[k], pos[k], scales[k], lens, "pair") for k in (0, 1))
+            patches, pos, scales = zip(ref, dist)
+        device, B, N, tokens_in, (pr, pd), (qr, qd), (sr, sdist) = self._inputs(tuple(patches), pos, scales)
+        B = B if lens is None else len(lens)
         with torch.cuda.device(device):
             q = torch.empty(B, device=device, dtype=torch.float32)
-            n_arr = (C.c_int32 * B)(*lens)
-            stream = torch.cuda.current_stream(device).cuda_stream
-            self._launch_checked(device, lambda lib: self._check(lib.vtq_forward_varlen(
-                self._engine, pr.data_ptr(), pd.data_ptr(), qr.data_ptr(), qd.data_ptr(), _ptr(sr), _ptr(sdist), B, n_arr, q.data_ptr(), stream)))
-        return q, None
+            # (all reference sequences, then all distorted ones)
+            outs, maps = self._rollout_outputs(device, lens + lens if lens is not None else 2 * B, N) if rollout else ((), None)
+            args = (pr.data_ptr(), pd.data_ptr(), qr.data_ptr(), qd.data_ptr(), _ptr(sr), _ptr(sdist), B, _i32(lens) if lens is not None else N,
+                    q.data_ptr(), *outs, torch.cuda.current_stream(device).cuda_stream)
+            name = _ENTRIES["pairs"][lens is not None, rollout, tokens_in]
+            self._launch_checked(device, lambda lib: self._check(getattr(lib, name)(self._engine, *args)))
+        if maps and lens is None:
+            return q, Rollout(*(m.view(2, B, *m.shape[1:]) for m in maps))
+        return q, maps and Rollout(*((m[:B], m[B:]) for m in maps))
 
-    def _varlen_inputs(self, what, patches, pos, scales, lengths):
-        """The host checks and input preparation of a batch of pairs with different patch counts (forward_varlen, forward_rollout(lengths=)):
-        (device, B, lengths as ints, (p_ref, p_dist), (pos_ref, pos_dist), (scales_ref, scales_dist)), the tensors concatenated, fp32, contiguous."""
-        if isinstance(lengths, torch.Tensor):
-            if lengths.device.type != "cpu":
-                raise ValueError("lengths must be a sequence of ints or a CPU integer tensor: a CUDA tensor would force a device synchronisation")
-            if lengths.dtype.is_floating_point or lengths.dtype.is_complex or lengths.dtype == torch.bool or lengths.dim() != 1:
-                raise ValueError("lengths must be a 1-D integer tensor")
-            lengths = lengths.tolist()
-        lens = [int(v) for v in lengths]
-        if not lens or any(v < 1 for v in lens) or any(int(v) != v for v in lengths):
-            raise ValueError(f"lengths must hold at least one pair and only integers >= 1, got {list(lengths)}")
-        B, total = len(lens), sum(lens)
-
-        def joined(ts, what, tail):                 # per-pair tensors -> the concatenated tensor, as one "batch" of sum(lengths) rows for _inputs
-            if ts is None:
-                return None
-            if len(ts) != 2:
-                raise ValueError(f"{what} must be a (ref, dist) pair")
-            out = []
-            for t in ts:
-                if t is None:
-                    out.append(None)
-                    continue
-                if isinstance(t, (list, tuple)):
-                    if len(t) != B or any(u.shape[0] != n for u, n in zip(t, lens)):
-                        raise ValueError(f"{what}: a list must hold one tensor per pair with lengths[b] rows each")
-                    t = torch.cat([u.reshape(u.shape[0], *tail) for u in t], 0)
-                if t.shape[0] != total or t.numel() != total * math.prod(tail):
-                    raise ValueError(f"{what}: {tuple(t.shape)} does not hold sum(lengths) = {total} rows of shape {tuple(tail)}")
-                out.append(t.reshape(1, total, *tail))
-            return tuple(out)
-        P = self.spec.patch_size
-        first = patches[0][0] if isinstance(patches[0], (list, tuple)) else patches[0]
-        if first.dim() != 4:
-            raise ValueError(f"{what} takes patches as (sum(lengths), 3, {P}, {P}) tensors (pre-embedded input is not offered), got {tuple(first.shape)}")
-        pt = joined(patches, "patches", tuple(first.shape[1:]))
-        ps = joined(pos, "pos", (2,)) if self.spec.use_pos_embedding else pos
-        sc = joined(scales, "scales", ()) if self.spec.use_scale_embedding else None
-        device, _, _, _, pt, ps, sc = self._inputs(pt, ps, sc)
-        return device, B, lens, pt, ps, sc
-
-    # ---- one-to-many scoring: every reference encoded once ----------------------------------------------------------------
-    def _group_guard(self, what):
+    def _guard(self, what=None):
+        """Eval only -- and, where `what` names the method, not for the fp8 experiment's model (it scores pairs and triplets only)."""
         if self.training:
             raise NotImplementedError(_TRAIN_MSG)
-        if self._FP8_EXPERIMENT:
+        if what and self._FP8_EXPERIMENT:
             raise NotImplementedError(f"{what} is not available for the fp8 experiment's model")
 
     def _token(self) -> int:
         t = int(self.token_num)
         return t + self.spec.num_tokens if t < 0 else t
 
-    def _ragged_image(self, what, patches, pos, scales, lens):
+    def _ragged_image(self, what, patches, pos, scales, lens, noun="image"):
         """One image's (patches, pos, scales) of a `lengths=` call as the one-item batches _inputs takes, their row counts checked against
         sum(lengths) -- before any device is looked at."""
         P = self.spec.patch_size
@@ -840,17 +817,34 @@ class VTAMIQ(nn.Module):
         if first.dim() != 4:
             raise ValueError(f"{what}: with lengths, patches are (sum(lengths), 3, {P}, {P}) tensors (pre-embedded input is not offered), "
                              f"got {tuple(first.shape)}")
-        pt = _ragged(patches, lens, "patches", tuple(first.shape[1:]))
-        ps = _ragged(pos, lens, "pos", (2,)) if self.spec.use_pos_embedding else pos
-        sc = _ragged(scales, lens, "scales", ()) if self.spec.use_scale_embedding else None
+        pt = _ragged(patches, lens, "patches", tuple(first.shape[1:]), noun)
+        ps = _ragged(pos, lens, "pos", (2,), noun) if self.spec.use_pos_embedding else pos
+        sc = _ragged(scales, lens, "scales", (), noun) if self.spec.use_scale_embedding else None
         return pt, ps, sc
 
-    def _ragged_inputs(self, what, patches, pos, scales, lens):
-        """_ragged_image through _inputs: (device, patches, pos, scales), each the concatenated tensor, fp32 and contiguous."""
-        pt, ps, sc = self._ragged_image(what, patches, pos, scales, lens) if lens is not None else (patches, pos, scales)
-        device, _, _, _, (pt,), (ps,), (sc,) = self._inputs((pt,), (ps,), (sc,))
-        return device, pt, ps, sc
+    def _single(self, what, patches, pos, scales, lens):
+        """One list of single images through _inputs: (device, n, N, tokens_in, (patches, pos, scales)), the tensors fp32 and contiguous.  With
+        lens (`lengths=`) they are the concatenated tensors, n = len(lens) and tokens_in is None: those entries take 5-D patches only."""
+        if lens is not None:
+            patches, pos, scales = self._ragged_image(what, patches, pos, scales, lens)
+        device, n, N, tokens_in, (pt,), (ps,), (sc,) = self._inputs((patches,), (pos,), (scales,))
+        return (device, n, N, tokens_in, (pt, ps, sc)) if lens is None else (device, len(lens), N, None, (pt, ps, sc))
 
+    def _rollout_outputs(self, device, lens, N):
+        """The two outputs of a rollout call, allocated: ((rollout_out, last_attention_out) pointers, (maps, heads)).  lens an int: that many
+        sequences of N patches, dense (n, S) and (n, h, S) tensors; lens a list (`lengths=`): per-sequence patch counts in call order, one
+        flat allocation per field and _ragged_maps' views.  Either way [:k] / [k:] of both are the first k sequences' maps and the rest's."""
+        T, nh = self.spec.num_tokens, self.spec.num_heads
+        if isinstance(lens, int):
+            roll = torch.empty(lens, N + T, device=device, dtype=torch.float32)
+            last = torch.empty(lens, nh, N + T, device=device, dtype=torch.float32)
+            return (roll.data_ptr(), last.data_ptr()), (roll, last)
+        R = sum(lens) + len(lens) * T                   # token rows of the call's sequences
+        roll = torch.empty(R, device=device, dtype=torch.float32)
+        last = torch.empty(R * nh, device=device, dtype=torch.float32)
+        return (roll.data_ptr(), last.data_ptr()), _ragged_maps(roll, last, lens, T, nh)
+
+    # ---- one-to-many scoring: every reference encoded once ----------------------------------------------------------------
     def forward_group(self, patches, pos, scales, ref_index, *, lengths=None, rollout=False):
         """M distorted images over G references in ONE call, every reference encoded once: G + M sequences where forward() on the expanded
         pairs encodes 2 M.
@@ -869,66 +863,38 @@ class VTAMIQ(nn.Module):
                      (ref (G, S), dist (M, S)), Rollout.last_attention = ((G, h, S), (M, h, S)) -- views of one allocation per field; with
                      lengths, lists of (S_i,) / (h, S_i) tensors instead.  q keeps its bits; an image's maps have the bits of forward_rollout
                      on any single pair holding it (reference side for a reference, distorted side for a distorted image)."""
-        self._group_guard("forward_group")
+        self._guard("forward_group")
         if len(patches) != 2:
             raise ValueError("forward_group expects patches = (p_ref, p_dist)")
-        if lengths is not None:
+        ragged = lengths is not None
+        if ragged:
             if isinstance(lengths, torch.Tensor) or len(lengths) != 2 or lengths[0] is None or lengths[1] is None:
                 raise ValueError("forward_group: lengths must be (lengths_ref, lengths_dist), one entry per image of each")
             lr, ld = _lengths(lengths[0], "lengths[0]"), _lengths(lengths[1], "lengths[1]")
             G, M = len(lr), len(ld)
-            idx = _ref_index(ref_index, G, M)
-            pos = pos if pos is not None else (None, None)
-            scales = scales if scales is not None else (None, None)
-            ref = self._ragged_image("forward_group", patches[0], pos[0], scales[0], lr)
-            dist = self._ragged_image("forward_group", patches[1], pos[1], scales[1], ld)
-            device, pr, qr, sr = self._ragged_inputs("forward_group", *ref, None)
-            device_d, pd, qd, sdist = self._ragged_inputs("forward_group", *dist, None)
-            if device_d != device:
-                raise ValueError("forward_group: references and distorted images must live on one device")
-            T, nh = self.spec.num_tokens, self.spec.num_heads
-            with torch.cuda.device(device):
-                q = torch.empty(M, device=device, dtype=torch.float32)
-                nr, nd, arr = (C.c_int32 * G)(*lr), (C.c_int32 * M)(*ld), (C.c_int32 * M)(*idx)
-                stream = torch.cuda.current_stream(device).cuda_stream
-                if rollout:
-                    R = sum(lr) + sum(ld) + (G + M) * T
-                    roll = torch.empty(R, device=device, dtype=torch.float32)
-                    last = torch.empty(R * nh, device=device, dtype=torch.float32)
-                    self._launch_checked(device, lambda lib: self._check(lib.vtq_forward_group_varlen_rollout(
-                        self._engine, pr.data_ptr(), pd.data_ptr(), qr.data_ptr(), qd.data_ptr(), _ptr(sr), _ptr(sdist), G, M, nr, nd, arr,
-                        q.data_ptr(), roll.data_ptr(), last.data_ptr(), stream)))
-                    maps, heads = _ragged_maps(roll, last, lr + ld, T, nh)
-                    return q, Rollout((maps[:G], maps[G:]), (heads[:G], heads[G:]))
-                self._launch_checked(device, lambda lib: self._check(lib.vtq_forward_group_varlen(
-                    self._engine, pr.data_ptr(), pd.data_ptr(), qr.data_ptr(), qd.data_ptr(), _ptr(sr), _ptr(sdist), G, M, nr, nd, arr,
-                    q.data_ptr(), stream)))
-            return q, None
-        G, M = int(patches[0].shape[0]), int(patches[1].shape[0])
+        else:
+            G, M = int(patches[0].shape[0]), int(patches[1].shape[0])
         idx = _ref_index(ref_index, G, M)
         pos = pos if pos is not None else (None, None)
         scales = scales if scales is not None else (None, None)
-        device, _, N, tokens_in, (pr,), (qr,), (sr,) = self._inputs((patches[0],), (pos[0],), (scales[0],))
-        device_d, _, N_d, tokens_d, (pd,), (qd,), (sdist,) = self._inputs((patches[1],), (pos[1],), (scales[1],))
-        if device_d != device or N_d != N or tokens_d != tokens_in:
+        ref, dist = (patches[0], pos[0], scales[0]), (patches[1], pos[1], scales[1])
+        if ragged:                                  # both images' row counts, before a device is looked at
+            ref, dist = self._ragged_image("forward_group", *ref, lr), self._ragged_image("forward_group", *dist, ld)
+        device, _, N, tokens_in, (pr, qr, sr) = self._single("forward_group", *ref, None)
+        device_d, _, N_d, tokens_d, (pd, qd, sdist) = self._single("forward_group", *dist, None)
+        if ragged and device_d != device:
+            raise ValueError("forward_group: references and distorted images must live on one device")
+        if not ragged and (device_d != device or N_d != N or tokens_d != tokens_in):
             raise ValueError(f"forward_group: references and distorted images must agree in device, patch count and input form, got "
                              f"{tuple(patches[0].shape)} / {tuple(patches[1].shape)}")
         with torch.cuda.device(device):
             q = torch.empty(M, device=device, dtype=torch.float32)
-            arr = (C.c_int32 * M)(*idx)
-            stream = torch.cuda.current_stream(device).cuda_stream
-            if rollout:
-                S, nh = N + self.spec.num_tokens, self.spec.num_heads
-                roll = torch.empty(G + M, S, device=device, dtype=torch.float32)
-                last = torch.empty(G + M, nh, S, device=device, dtype=torch.float32)
-                self._launch_checked(device, lambda lib: self._check(
-                    (lib.vtq_forward_group_rollout_tokens if tokens_in else lib.vtq_forward_group_rollout)(
-                        self._engine, pr.data_ptr(), pd.data_ptr(), qr.data_ptr(), qd.data_ptr(), _ptr(sr), _ptr(sdist), G, M, N, arr, q.data_ptr(),
-                        roll.data_ptr(), last.data_ptr(), stream)))
-                return q, Rollout((roll[:G], roll[G:]), (last[:G], last[G:]))
-            self._launch_checked(device, lambda lib: self._check((lib.vtq_forward_group_tokens if tokens_in else lib.vtq_forward_group)(
-                self._engine, pr.data_ptr(), pd.data_ptr(), qr.data_ptr(), qd.data_ptr(), _ptr(sr), _ptr(sdist), G, M, N, arr, q.data_ptr(), stream)))
-        return q, None
+            outs, maps = self._rollout_outputs(device, lr + ld if ragged else G + M, N) if rollout else ((), None)
+            args = (pr.data_ptr(), pd.data_ptr(), qr.data_ptr(), qd.data_ptr(), _ptr(sr), _ptr(sdist), G, M, *((_i32(lr), _i32(ld)) if ragged else (N,)),
+                    _i32(idx), q.data_ptr(), *outs, torch.cuda.current_stream(device).cuda_stream)
+            name = _ENTRIES["group"][ragged, bool(rollout), tokens_in]
+            self._launch_checked(device, lambda lib: self._check(getattr(lib, name)(self._engine, *args)))
+        return q, maps and Rollout(*((m[:G], m[G:]) for m in maps))                  # the references first
 
     def encode_reference(self, patches, pos, scales=None, *, lengths=None, rollout=False):
         """Encode G reference images once, for forward_cached(): (G, N, 3, P, P) patches (or pre-embedded (G, N, H)), pos (G, N, 2), scales
@@ -940,44 +906,19 @@ class VTAMIQ(nn.Module):
           rollout  True: returns (ReferenceFeatures, Rollout) with forward_rollout's maps of the G references: Rollout.rollout (G, S),
                    Rollout.last_attention (G, h, S); with lengths, lists of (S_g,) / (h, S_g).  The rows keep their bits; the maps have the
                    bits forward_group(rollout=True) gives for the same references."""
-        self._group_guard("encode_reference")
-        if lengths is not None:
-            lens = _lengths(lengths, "lengths")
-            G = len(lens)
-            device, pt, pp, ps = self._ragged_inputs("encode_reference", patches, pos, scales, lens)
-            with torch.cuda.device(device):
-                rows = torch.empty(G, self.spec.hidden_size, device=device, dtype=torch.float32)
-                n_arr = (C.c_int32 * G)(*lens)
-                stream = torch.cuda.current_stream(device).cuda_stream
-                if rollout:
-                    T, nh = self.spec.num_tokens, self.spec.num_heads
-                    R = sum(lens) + G * T
-                    roll = torch.empty(R, device=device, dtype=torch.float32)
-                    last = torch.empty(R * nh, device=device, dtype=torch.float32)
-                    self._launch_checked(device, lambda lib: self._check(lib.vtq_encode_reference_varlen_rollout(
-                        self._engine, pt.data_ptr(), pp.data_ptr(), _ptr(ps), G, n_arr, rows.data_ptr(), roll.data_ptr(), last.data_ptr(), stream)))
-                    return (ReferenceFeatures(rows, self.engine_precision, self._token(), self.engine_options, self._signature()),
-                            Rollout(*_ragged_maps(roll, last, lens, T, nh)))
-                self._launch_checked(device, lambda lib: self._check(lib.vtq_encode_reference_varlen(
-                    self._engine, pt.data_ptr(), pp.data_ptr(), _ptr(ps), G, n_arr, rows.data_ptr(), stream)))
-            return ReferenceFeatures(rows, self.engine_precision, self._token(), self.engine_options, self._signature())
-        device, G, N, tokens_in, (pt,), (pp,), (ps,) = self._inputs((patches,), (pos,), (scales,))
+        self._guard("encode_reference")
+        lens = _lengths(lengths, "lengths") if lengths is not None else None
+        device, G, N, tokens_in, ts = self._single("encode_reference", patches, pos, scales, lens)
         with torch.cuda.device(device):
             rows = torch.empty(G, self.spec.hidden_size, device=device, dtype=torch.float32)
-            stream = torch.cuda.current_stream(device).cuda_stream
-            maps = None
-            if rollout:
-                S, nh = N + self.spec.num_tokens, self.spec.num_heads
-                maps = Rollout(torch.empty(G, S, device=device, dtype=torch.float32), torch.empty(G, nh, S, device=device, dtype=torch.float32))
-                self._launch_checked(device, lambda lib: self._check(lib.vtq_encode_reference_rollout(
-                    self._engine, pt.data_ptr(), int(tokens_in), pp.data_ptr(), _ptr(ps), G, N, rows.data_ptr(), maps.rollout.data_ptr(),
-                    maps.last_attention.data_ptr(), stream)))
-            else:
-                self._launch_checked(device, lambda lib: self._check(lib.vtq_encode_reference(
-                    self._engine, pt.data_ptr(), int(tokens_in), pp.data_ptr(), _ptr(ps), G, N, rows.data_ptr(), stream)))
+            outs, maps = self._rollout_outputs(device, lens if lens is not None else G, N) if rollout else ((), None)
+            args = (*_image_args(ts, tokens_in), G, _i32(lens) if lens is not None else N, rows.data_ptr(), *outs,
+                    torch.cuda.current_stream(device).cuda_stream)
+            name = _ENTRIES["encode"][lens is not None, bool(rollout), bool(tokens_in)]
+            self._launch_checked(device, lambda lib: self._check(getattr(lib, name)(self._engine, *args)))
         # read AFTER the launch: "auto" may have switched the model to bf16x3 and repeated the call -- the rows are that run's
         ref = ReferenceFeatures(rows, self.engine_precision, self._token(), self.engine_options, self._signature())
-        return (ref, maps) if rollout else ref
+        return (ref, Rollout(*maps)) if rollout else ref
 
     def _stale(self, ref: ReferenceFeatures):
         now = (self.engine_precision, self._token(), self.engine_options)
@@ -1001,7 +942,7 @@ class VTAMIQ(nn.Module):
           rollout       True: returns (q, Rollout) with forward_rollout's maps of the M distorted images alone (the cached references are not
                         encoded here: their maps come from encode_reference(rollout=True)): Rollout.rollout (M, S), Rollout.last_attention
                         (M, h, S); with lengths, lists of (S_m,) / (h, S_m).  The bits are forward_group(rollout=True)'s distorted side."""
-        self._group_guard("forward_cached")
+        self._guard("forward_cached")
         if not isinstance(ref, ReferenceFeatures):
             raise TypeError("forward_cached takes the ReferenceFeatures of encode_reference as its first argument")
         lens = _lengths(lengths, "lengths") if lengths is not None else None
@@ -1010,50 +951,27 @@ class VTAMIQ(nn.Module):
         why = self._stale(ref)
         if why:
             raise StaleReferenceError(f"forward_cached: the reference features are stale: {why}; encode_reference again")
-        if lens is not None:
-            device, pt, pp, ps = self._ragged_inputs("forward_cached", patches_dist, pos_dist, scales_dist, lens)
-        else:
-            device, _, N, tokens_in, (pt,), (pp,), (ps,) = self._inputs((patches_dist,), (pos_dist,), (scales_dist,))
+        device, _, N, tokens_in, ts = self._single("forward_cached", patches_dist, pos_dist, scales_dist, lens)
         rows = ref.rows
         if rows.device != device or rows.dtype != torch.float32 or tuple(rows.shape) != (G, self.spec.hidden_size) or not rows.is_contiguous():
             raise ValueError(f"forward_cached: ref.rows must be a contiguous fp32 (G, {self.spec.hidden_size}) tensor on {device}")
         with torch.cuda.device(device):
             q = torch.empty(M, device=device, dtype=torch.float32)
-            arr = (C.c_int32 * M)(*idx)
-            stream = torch.cuda.current_stream(device).cuda_stream
-            T, nh, maps = self.spec.num_tokens, self.spec.num_heads, None
-            if lens is not None and rollout:
-                n_arr = (C.c_int32 * M)(*lens)
-                R = sum(lens) + M * T
-                roll = torch.empty(R, device=device, dtype=torch.float32)
-                last = torch.empty(R * nh, device=device, dtype=torch.float32)
-                self._launch_checked(device, lambda lib: self._check(lib.vtq_forward_cached_varlen_rollout(
-                    self._engine, rows.data_ptr(), G, pt.data_ptr(), pp.data_ptr(), _ptr(ps), M, n_arr, arr, q.data_ptr(), roll.data_ptr(),
-                    last.data_ptr(), stream)))
-                maps = Rollout(*_ragged_maps(roll, last, lens, T, nh))
-            elif lens is not None:
-                n_arr = (C.c_int32 * M)(*lens)
-                self._launch_checked(device, lambda lib: self._check(lib.vtq_forward_cached_varlen(
-                    self._engine, rows.data_ptr(), G, pt.data_ptr(), pp.data_ptr(), _ptr(ps), M, n_arr, arr, q.data_ptr(), stream)))
-            elif rollout:
-                maps = Rollout(torch.empty(M, N + T, device=device, dtype=torch.float32), torch.empty(M, nh, N + T, device=device, dtype=torch.float32))
-                self._launch_checked(device, lambda lib: self._check(lib.vtq_forward_cached_rollout(
-                    self._engine, rows.data_ptr(), G, pt.data_ptr(), int(tokens_in), pp.data_ptr(), _ptr(ps), M, N, arr, q.data_ptr(),
-                    maps.rollout.data_ptr(), maps.last_attention.data_ptr(), stream)))
-            else:
-                self._launch_checked(device, lambda lib: self._check(lib.vtq_forward_cached(
-                    self._engine, rows.data_ptr(), G, pt.data_ptr(), int(tokens_in), pp.data_ptr(), _ptr(ps), M, N, arr, q.data_ptr(), stream)))
+            outs, maps = self._rollout_outputs(device, lens if lens is not None else M, N) if rollout else ((), None)
+            args = (rows.data_ptr(), G, *_image_args(ts, tokens_in), M, _i32(lens) if lens is not None else N, _i32(idx), q.data_ptr(), *outs,
+                    torch.cuda.current_stream(device).cuda_stream)
+            name = _ENTRIES["cached"][lens is not None, bool(rollout), bool(tokens_in)]
+            self._launch_checked(device, lambda lib: self._check(getattr(lib, name)(self._engine, *args)))
         if self.engine_precision != ref.precision:
             raise StaleReferenceError(f"forward_cached: an operand left the fp16 range and the model now runs {self.engine_precision!r}; the cached "
                                       f"rows are {ref.precision!r} rows: encode_reference again")
-        return q, maps
+        return q, maps and Rollout(*maps)
 
     def forward_pairwise(self, patches, pos, scales):
         """Pairwise items: `patches = (p_ref, p_dist1, p_dist2)` etc.  Returns (q1, q2) == what two calls
         `self((p_ref, p_dist1), ...)[0]`, `self((p_ref, p_dist2), ...)[0]` give (train.py:286-287), bit for bit, with the
         reference image encoded once: 3B sequences instead of 4B."""
-        if self.training:
-            raise NotImplementedError("the MI355X engine implements the eval/no-grad forward only: call model.eval()")
+        self._guard()
         if len(patches) != 3 or (self.spec.use_pos_embedding and len(pos) != 3):
             raise ValueError("forward_pairwise expects (ref, dist1, dist2) triplets")
         device, B, N, tokens_in, pt, ps, sc = self._inputs(patches, pos, scales, warn_grad=False)
@@ -1061,8 +979,8 @@ class VTAMIQ(nn.Module):
             q = torch.empty(2 * B, device=device, dtype=torch.float32)
             arr = lambda ts: (C.c_void_p * 3)(*[t.data_ptr() for t in ts])
             stream = torch.cuda.current_stream(device).cuda_stream
-            self._launch_checked(device, lambda lib: self._check((lib.vtq_forward_pairwise_tokens if tokens_in else lib.vtq_forward_pairwise)(
-                self._engine, arr(pt), arr(ps), arr(sc) if sc[0] is not None else None, B, N, q.data_ptr(), stream)))
+            args = (arr(pt), arr(ps), arr(sc) if sc[0] is not None else None, B, N, q.data_ptr(), stream)
+            self._launch_checked(device, lambda lib: self._check(getattr(lib, _ENTRIES["pairwise"][False, False, tokens_in])(self._engine, *args)))
         return q[:B], q[B:]
 
     def forward_vit(self, patches, patches_pos, patches_scale, tokens_only=True, adapter_num=None):
@@ -1073,10 +991,7 @@ class VTAMIQ(nn.Module):
                          embedding output is not one of them), sliced to [:, :T] when tokens_only; else []
           attn_weights   transformer.encoder.return_attention: L (B, num_heads, S, S) softmax probabilities; else []
         All fp32 on the input device.  The flags are read at every call, so setting them after construction takes effect."""
-        if self.training:
-            raise NotImplementedError(_TRAIN_MSG)
-        if self._FP8_EXPERIMENT:
-            raise NotImplementedError("forward_vit is not available for the fp8 experiment's model (it scores pairs only)")
+        self._guard("forward_vit")
         if adapter_num is not None and adapter_num >= 1 and self.spec.num_adapters > 0:
             # backbone.py:55-57: None / negative selects pair 0 when the model has adapters; a model without adapters ignores the number
             # (transformer.py:277-278), as the engine does
