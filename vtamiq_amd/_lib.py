@@ -137,6 +137,12 @@ ROLLOUT_SIGNATURES = {
                                       C.c_int32, C.c_int32, C.c_void_p]),
 }
 
+# include/vtamiq_hip_images.h: the image front end for images of different sizes (vtamiq_amd.patches.extract_patches_varlen)
+IMAGE_SIGNATURES = {
+    "vtq_k_gather_patches_u8": (C.c_int, [_P, C.c_int64, _P, _P, C.POINTER(C.c_int64), _IP, _IP, _IP, _I, _P, _P, _P, C.POINTER(C.c_float),
+                                          C.POINTER(C.c_float), _P, _P, _P, _I, _I, _P]),
+}
+
 # the fp8 experiment (include/vtamiq_hip_fp8.h): exported only by a library built with -DVTQ_WITH_FP8 (python -m vtamiq_amd.build --fp8 ->
 # LIB_PATH_FP8, load_fp8()); bound when present
 FP8_SIGNATURES = {
@@ -171,7 +177,7 @@ def load(path: str | None = None) -> C.CDLL:
     # VTQ_LIB_PATH selects WHICH build is loaded (e.g. a build of another tree, for an A/B); it does not relax any check.  An A/B
     # build of an OLDER tree (different ABI: argument layouts may differ) loads only with VTQ_ALLOW_ABI_MISMATCH=1, with a warning.
     relaxed = os.environ.get("VTQ_ALLOW_ABI_MISMATCH") == "1"
-    for name, (res, args) in list(SIGNATURES.items()) + list(ROLLOUT_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(ROLLOUT_SIGNATURES.items()) + list(IMAGE_SIGNATURES.items()):
         if relaxed and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)          # AttributeError if a declared symbol is not exported

@@ -19,6 +19,7 @@
 #include "../../include/vtamiq_hip.h"
 #include "../../include/vtamiq_hip_fp8.h"
 #include "../../include/vtamiq_hip_rollout.h"
+#include "../../include/vtamiq_hip_images.h"
 #include "kernels.h"
 
 using namespace vtq;
@@ -1820,6 +1821,34 @@ int vtq_k_gather_patches(const float* const* levels, const int32_t* hs, const in
     if (!levels || !hs || !ws || !samples || !patches || !pos) return fail("vtq_k_gather_patches: null argument");
     if (patch_size != 16 && patch_size != 8) return fail("vtq_k_gather_patches: patch_size %d (16 or 8)", patch_size);
     HIP_TRY(launch_gather_patches(levels, hs, ws, nlevels, samples, scale_ids, patches, pos, scales, NI, N, (hipStream_t)stream, patch_size));
+    return 0;
+}
+
+// include/vtamiq_hip_images.h: every check reads HOST arrays only, so a refusal touches no device memory and launches nothing
+int vtq_k_gather_patches_u8(const uint8_t* images, int64_t image_bytes, const int32_t* tab, const int32_t* patch_img, const int64_t* img_off,
+                            const int32_t* H, const int32_t* W, const int32_t* row0, int32_t NI, const int32_t* samples,
+                            const int32_t* scale_ids, const int32_t* flips, const float* mean, const float* std_, float* patches, float* pos,
+                            float* scales, int32_t patch_size, int32_t num_scales, void* stream) {
+    if (!images || !tab || !patch_img || !img_off || !H || !W || !row0 || !samples || !mean || !std_ || !patches || !pos)
+        return fail("vtq_k_gather_patches_u8: null argument");
+    if ((uintptr_t)tab % 16) return fail("vtq_k_gather_patches_u8: tab is not 16-byte aligned");
+    if (NI < 1) return fail("vtq_k_gather_patches_u8: NI=%d (at least 1)", (int)NI);
+    if (patch_size != 16 && patch_size != 8) return fail("vtq_k_gather_patches_u8: patch_size %d (16 or 8)", (int)patch_size);
+    if (num_scales < 1 || num_scales > 4) return fail("vtq_k_gather_patches_u8: num_scales=%d (1 .. 4)", (int)num_scales);
+    if (!scale_ids && num_scales > 1) return fail("vtq_k_gather_patches_u8: scale_ids are required when num_scales > 1");
+    if (row0[0] != 0) return fail("vtq_k_gather_patches_u8: row0[0]=%d (0 required)", (int)row0[0]);
+    for (int32_t i = 0; i < NI; ++i) {
+        if (row0[i + 1] < row0[i]) return fail("vtq_k_gather_patches_u8: row0 decreases at image %d", (int)i);
+        if (H[i] < patch_size || W[i] < patch_size)
+            return fail("vtq_k_gather_patches_u8: image %d (%d x %d) is smaller than one %d x %d patch", (int)i, (int)H[i], (int)W[i],
+                        (int)patch_size, (int)patch_size);
+        if (img_off[i] < 0 || image_bytes < 0 || img_off[i] > image_bytes || (int64_t)3 * H[i] * W[i] > image_bytes - img_off[i])
+            return fail("vtq_k_gather_patches_u8: image %d (%d x %d at byte %lld) leaves the buffer of %lld bytes", (int)i, (int)H[i], (int)W[i],
+                        (long long)img_off[i], (long long)image_bytes);
+    }
+    if (row0[NI] < 1) return fail("vtq_k_gather_patches_u8: no patches (row0[NI]=%d)", (int)row0[NI]);
+    HIP_TRY(launch_gather_patches_u8(images, tab, patch_img, samples, scale_ids, flips, patches, pos, scales, row0[NI], mean, std_, patch_size,
+                                     num_scales, (hipStream_t)stream));
     return 0;
 }
 

@@ -246,6 +246,11 @@ hipError_t launch_image_normalize(const uint8_t* in, float* out, int NI, int H, 
 hipError_t launch_avgpool2(const float* in, float* out, int NC, int H, int W, hipStream_t s);
 hipError_t launch_gather_patches(const float* const* levels, const int* hs, const int* ws, int nlevels, const int* samples,
                                  const int* scale_ids, float* patches, float* pos, float* scales, int NI, int N, hipStream_t s, int P = 16);
+// patches_ragged.hip: images of different sizes packed in one byte buffer, no fp32 intermediate (include/vtamiq_hip_images.h);
+// tab int32 [NI][4] = (img_off low, high, H, W), patch_img int32 [total], both on the device
+hipError_t launch_gather_patches_u8(const uint8_t* images, const int* tab, const int* patch_img, const int* samples, const int* scale_ids,
+                                    const int* flips, float* patches, float* pos, float* scales, int64_t total, const float* mean,
+                                    const float* sd, int P, int num_scales, hipStream_t s);
 
 // ---- measurement: the matrix pipe's sustained rate on this device (mfma_stream.hip) -----------------------------------------
 // f16: 0 bf16, 1 fp16 operands; data: 0 the 3-term mix of gaussian hi / lo planes, 1 zeros, 2 uniform random

@@ -4,8 +4,9 @@
 from __future__ import annotations
 
 import ctypes as C
-from typing import Optional, Sequence, Tuple
+from typing import NamedTuple, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -98,3 +99,156 @@ def extract_patches(images_u8: torch.Tensor, samples: torch.Tensor, scale_ids: O
                                             patches.data_ptr(), pos.data_ptr(), scales.data_ptr() if scales is not None else None, NI, N,
                                             P, stream))
     return patches, pos, scales
+
+
+# ---- images of different sizes (include/vtamiq_hip_images.h, csrc/patches_ragged.hip) -------------------------------------------------------
+class ImageTables(NamedTuple):
+    """Host tables of one batch of NI images of different sizes (image_tables)."""
+    img_off: np.ndarray       # int64 [NI]      byte offset of image i in the flat buffer (images packed back to back, in order)
+    H: np.ndarray             # int32 [NI]
+    W: np.ndarray             # int32 [NI]
+    row0: np.ndarray          # int32 [NI + 1]  patch-row prefix: image i owns rows [row0[i], row0[i + 1])
+    tab: np.ndarray           # int32 [NI, 4]   (img_off low word, high word, H, W): what the kernel reads
+    patch_img: np.ndarray     # int32 [total]   the image of every patch row
+    image_bytes: int          # sum of 3 H W
+    total: int                # row0[NI]
+
+
+def _sizes(sizes) -> np.ndarray:
+    sz = np.asarray([(int(h), int(w)) for h, w in sizes], dtype=np.int64).reshape(-1, 2)
+    if sz.shape[0] < 1 or (sz < 1).any():
+        raise ValueError("sizes: at least one (H, W), both >= 1")
+    return sz
+
+
+def image_tables(sizes, lengths) -> ImageTables:
+    """The offset, prefix and image-index tables of NI images [(H_i, W_i) ...] with lengths[i] >= 0 patches each, on the host (numpy only)."""
+    sz = _sizes(sizes)
+    ln = np.asarray(lengths)
+    if ln.shape != (sz.shape[0],) or ln.dtype.kind not in "iu":
+        raise ValueError("lengths: one integer per image")
+    ln = ln.astype(np.int64)
+    if (ln < 0).any():
+        raise ValueError("lengths: >= 0")
+    nbytes = 3 * sz[:, 0] * sz[:, 1]
+    off = np.concatenate([[0], np.cumsum(nbytes)[:-1]]).astype(np.int64)
+    row0 = np.concatenate([[0], np.cumsum(ln)])
+    if row0[-1] > 0x7fffffff or (sz > 0x7fffffff).any():
+        raise ValueError("more than 2^31 - 1 patches or pixels per side")
+    tab = np.empty((sz.shape[0], 4), np.int32)
+    tab[:, :2] = off.astype("<i8").view("<i4").reshape(-1, 2)
+    tab[:, 2:] = sz
+    return ImageTables(off, sz[:, 0].astype(np.int32), sz[:, 1].astype(np.int32), row0.astype(np.int32), tab,
+                       np.repeat(np.arange(sz.shape[0], dtype=np.int32), ln), int(nbytes.sum()), int(row0[-1]))
+
+
+def check_samples_host_varlen(samples, scale_ids, sizes, lengths, num_scales: int = 1, patch_size: int = 16) -> None:
+    """check_samples_host for images of different sizes: samples (total, 2) and scale_ids (total,) or None are the per-image lists
+    concatenated, image i = (H_i, W_i) owning lengths[i] rows.  Every sample must lie inside ITS image's level -- a small image may use fewer levels than
+    num_scales; a sample on a level of its image that is smaller than one patch has no valid position -- IndexError otherwise, like the
+    reference's fancy indexing.  numpy on the calling thread, for
+    check_samples_host's reason: torch CPU operators wake the intra-op pool, which doubled a pipelined loop's time."""
+    P = int(patch_size)
+    if not 1 <= num_scales <= 4:
+        raise ValueError("1 <= num_scales <= 4")
+    sz = _sizes(sizes)
+    ln = np.asarray(lengths, dtype=np.int64)
+    smp = np.asarray(samples)
+    if ln.shape != (sz.shape[0],) or smp.shape != (int(ln.sum()), 2):
+        raise ValueError("samples must be (sum(lengths), 2), lengths one count per image")
+    if scale_ids is None:
+        if num_scales > 1:
+            raise ValueError("scale_ids are required when num_scales > 1")
+        lvl = np.zeros(smp.shape[0], dtype=np.int64)
+    else:
+        lvl = np.asarray(scale_ids).astype(np.int64)
+        if lvl.shape != (smp.shape[0],):
+            raise ValueError("scale_ids must be (sum(lengths),)")
+        if ((lvl < 0) | (lvl >= num_scales)).any():
+            raise IndexError("scale_ids outside [0, num_scales)")
+    dims = np.repeat(sz, ln, axis=0)                         # (total, 2): the image of every row
+    lim = (dims >> lvl[:, None]) - P
+    if ((smp < 0) | (smp > lim)).any():
+        raise IndexError(f"patch sample outside its image's pyramid level (row in [0, h-{P}], col in [0, w-{P}] required)")
+
+
+def gather_patches_u8(flat: torch.Tensor, tables: ImageTables, dev_tab: torch.Tensor, dev_patch_img: torch.Tensor, samples: torch.Tensor,
+                      scale_ids: Optional[torch.Tensor], flips: Optional[torch.Tensor], num_scales: int, mean, std, patch_size: int):
+    """The launch itself (vtq_k_gather_patches_u8) on the current stream: every tensor is on the device already, `tables` are the host
+    arrays dev_tab / dev_patch_img were copied from.  Nothing here copies or synchronises."""
+    lib = _lib.load()
+    dev = flat.device
+    P, T = int(patch_size), tables.total
+    with torch.cuda.device(dev):
+        patches = torch.empty(T, 3, P, P, device=dev, dtype=torch.float32)
+        pos = torch.empty(T, 2, device=dev, dtype=torch.float32)
+        scales = torch.empty(T, device=dev, dtype=torch.float32) if num_scales > 1 else None
+        as_p = lambda a, t: a.ctypes.data_as(C.POINTER(t))
+        _lib.check(lib.vtq_k_gather_patches_u8(
+            flat.data_ptr(), flat.numel(), dev_tab.data_ptr(), dev_patch_img.data_ptr(), as_p(tables.img_off, C.c_int64),
+            as_p(tables.H, C.c_int32), as_p(tables.W, C.c_int32), as_p(tables.row0, C.c_int32), len(tables.H), samples.data_ptr(),
+            scale_ids.data_ptr() if scale_ids is not None else None, flips.data_ptr() if flips is not None else None,
+            (C.c_float * 3)(*mean), (C.c_float * 3)(*std), patches.data_ptr(), pos.data_ptr(),
+            scales.data_ptr() if scales is not None else None, P, num_scales, torch.cuda.current_stream(dev).cuda_stream))
+    return patches, pos, scales
+
+
+def extract_patches_varlen(images, samples, lengths, scale_ids=None, num_scales: int = 1, flips=None,
+                           mean: Sequence[float] = (0.5, 0.5, 0.5), std: Sequence[float] = (0.5, 0.5, 0.5), patch_size: int = 16,
+                           validate: bool = True, sizes=None) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
+    """extract_patches for NI images of DIFFERENT sizes in one launch, without a normalised copy or a pyramid of any image.
+      images     a list of uint8 [H_i, W_i, 3] cuda tensors (concatenated here, on the device), or ONE flat uint8 cuda tensor holding them
+                 back to back, with sizes=[(H_i, W_i) ...]
+      samples    int32 (sum(lengths), 2): the images' sample lists concatenated, (row, col) at each patch's own level; lengths: NI counts
+      scale_ids  int32 (sum(lengths),), required when num_scales > 1;  flips int32 (NI, 2) = (hflip, vflip) or None
+    Returns patches (sum, 3, P, P), pos (sum, 2), scales (sum,) or None -- fp32, concatenated per image: what forward_varlen and
+    forward_group(..., lengths=) take.  Every element has the bits extract_patches gives for that image alone.  validate=True range-checks
+    the samples on the host (check_samples_host_varlen; samples on the device are read back, which synchronises); a pipelined loader checks
+    its host copy before the upload and passes validate=False (pipeline.ImagePairVarlenPipeline)."""
+    if isinstance(images, torch.Tensor):
+        if sizes is None:
+            raise ValueError("a flat image tensor needs sizes=[(H, W) ...]")
+        flat = images
+    else:
+        if sizes is not None:
+            raise ValueError("sizes= goes with a flat image tensor; a list of images carries its own")
+        images = list(images)
+        if not images or any(not isinstance(i, torch.Tensor) or i.dim() != 3 or i.shape[-1] != 3 for i in images):
+            raise ValueError("images must be a non-empty list of uint8 [H, W, 3] tensors")
+        sizes = [tuple(i.shape[:2]) for i in images]
+        flat = images[0]
+    dev = flat.device
+    if dev.type != "cuda":
+        raise RuntimeError("extract_patches_varlen runs on the GPU only (no CPU fallback on the product path)")
+    if not isinstance(images, torch.Tensor):
+        if any(i.dtype != torch.uint8 or i.device != dev for i in images):
+            raise ValueError("images must be uint8 tensors on one device")
+        flat = torch.cat([i.contiguous().reshape(-1) for i in images])
+    if flat.dtype != torch.uint8 or flat.dim() != 1:
+        raise ValueError("the flat image tensor must be uint8 and one-dimensional")
+    P = int(patch_size)
+    if P not in (16, 8):
+        raise ValueError("patch_size must be 16 or 8")
+    if not 1 <= num_scales <= 4:
+        raise ValueError("1 <= num_scales <= 4")
+    if num_scales > 1 and scale_ids is None:
+        raise ValueError("scale_ids are required when num_scales > 1")
+    lengths = [int(n) for n in (lengths.tolist() if isinstance(lengths, (torch.Tensor, np.ndarray)) else lengths)]
+    tables = image_tables(sizes, lengths)
+    if tables.total < 1:
+        raise ValueError("no patches: sum(lengths) must be at least 1")
+    if flat.numel() != tables.image_bytes:
+        raise ValueError(f"the flat image tensor has {flat.numel()} bytes, the sizes need {tables.image_bytes}")
+    to_np = lambda a: a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+    if tuple(samples.shape) != (tables.total, 2):
+        raise ValueError("samples must be int32 (sum(lengths), 2)")
+    if scale_ids is not None and tuple(scale_ids.shape) != (tables.total,):
+        raise ValueError("scale_ids must be int32 (sum(lengths),)")
+    if flips is not None and tuple(flips.shape) != (len(lengths), 2):
+        raise ValueError("flips must be int32 (NI, 2)")
+    if validate:
+        check_samples_host_varlen(to_np(samples), to_np(scale_ids) if scale_ids is not None else None, sizes, lengths, num_scales, P)
+    on_dev = lambda a: torch.as_tensor(a).to(device=dev, dtype=torch.int32).contiguous()
+    return gather_patches_u8(flat, tables, on_dev(tables.tab), on_dev(tables.patch_img), on_dev(samples),
+                             on_dev(scale_ids) if scale_ids is not None else None, on_dev(flips) if flips is not None else None,
+                             num_scales, mean, std, P)

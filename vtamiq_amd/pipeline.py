@@ -14,15 +14,18 @@ the device (validate.compute_correlations_cat_flat reduces them there).
 
 Measured (bench.py `e2e`, profiles/r05_bench_line.json): the loop sustains 0.98 x the forward's own throughput at B = 32, N = 500; with a 1 280-pair
 validation set's final reductions (rank statistics + the logistic fit, once per set) 0.91 - 0.95 x by box.
+
+Batches that mix image sizes and patch counts go through ImagePairVarlenPipeline below: one gather over all images of the batch
+(patches.gather_patches_u8) and forward_varlen / forward_group(lengths=), 0.977 x of forward_varlen alone (profiles/r15_image_varlen.txt).
 """
 from __future__ import annotations
 
-from typing import Optional, Sequence, Tuple
+from typing import NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
-from .patches import check_samples_host, extract_patches
+from .patches import ImageTables, check_samples_host, check_samples_host_varlen, extract_patches, gather_patches_u8, image_tables
 
 
 class ImagePairPipeline:
@@ -112,3 +115,248 @@ class ImagePairPipeline:
             else:
                 hd[:] = sid
         return self.launch()
+
+
+# ---- batches whose images differ in size and patch count -----------------------------------------------------------------------------------
+class VarlenBatch(NamedTuple):
+    """One batch as the varlen pipeline sees it, made on the host without a device (plan_varlen_batch)."""
+    sizes: list               # NI (H, W): the first side's images, then the second side's
+    lengths: np.ndarray       # int64 [NI] patches per image
+    n_first: int              # images of the first side (references)
+    tables: ImageTables
+    words: int                # int32 words of the slot's table block this batch uses: tab, patch_img, samples, scale ids
+
+
+def plan_varlen_batch(sizes_first, sizes_second, lengths_first, lengths_second, *, max_images: int, max_image_bytes: int, max_patches: int,
+                      num_scales: int = 1, patch_size: int = 16) -> VarlenBatch:
+    """Argument and capacity checking of ImagePairVarlenPipeline, device-free: the images of the first side (references) with their patch
+    counts, then those of the second.  ValueError for a batch over capacity (max_images in all, max_image_bytes in all, max_patches per
+    side), for an empty side or image, and for an image smaller than a patch."""
+    sizes = [(int(h), int(w)) for h, w in list(sizes_first) + list(sizes_second)]
+    lf, ls = np.asarray(lengths_first, dtype=np.int64).reshape(-1), np.asarray(lengths_second, dtype=np.int64).reshape(-1)
+    if len(sizes_first) < 1 or len(sizes_second) < 1 or len(lf) != len(sizes_first) or len(ls) != len(sizes_second):
+        raise ValueError("each side needs at least one image and one patch count per image")
+    if (lf < 1).any() or (ls < 1).any():
+        raise ValueError("every image needs at least one patch")
+    if len(sizes) > max_images:
+        raise ValueError(f"{len(sizes)} images in the batch, the pipeline was built for {max_images} (2 * max_pairs)")
+    if max(int(lf.sum()), int(ls.sum())) > max_patches:
+        raise ValueError(f"{max(int(lf.sum()), int(ls.sum()))} patches on one side, the pipeline was built for max_patches={max_patches}")
+    lengths = np.concatenate([lf, ls])
+    tables = image_tables(sizes, lengths)
+    if tables.image_bytes > max_image_bytes:
+        raise ValueError(f"the batch's images take {tables.image_bytes} bytes, the pipeline was built for max_image_bytes={max_image_bytes}")
+    P = int(patch_size)
+    for i, (h, w) in enumerate(sizes):
+        if h < P or w < P:
+            raise ValueError(f"image {i} ({h}x{w}) is smaller than one {P}x{P} patch")
+    return VarlenBatch(sizes, lengths, len(sizes_first), tables, 4 * len(sizes) + tables.total * (4 if num_scales > 1 else 3))
+
+
+def pair_arguments(refs, dists, samples, lengths=None, scale_ids=None, num_scales: int = 1):
+    """submit()'s argument checking, device-free.  refs, dists: B host images uint8 [H, W, 3] each; samples: B arrays (N_b, 2) -- aligned
+    sampling, one list per pair shared by its two images, which must then have ONE size -- or 2B arrays (references first) for unaligned
+    sampling with N_b patches on both sides of pair b; lengths: None or the B counts, which must then match; scale_ids like samples.
+    Returns (refs, dists, per-image samples [2B], per-image scale ids [2B] or None, lengths [B]) as numpy arrays."""
+    refs, dists = [np.asarray(r) for r in refs], [np.asarray(d) for d in dists]
+    B = len(refs)
+    if B < 1 or len(dists) != B:
+        raise ValueError("refs and dists: B >= 1 images each")
+    for im in refs + dists:
+        if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
+            raise ValueError("images must be uint8 [H, W, 3]")
+    smp = [np.asarray(s) for s in samples]
+    if len(smp) not in (B, 2 * B) or any(s.ndim != 2 or s.shape[1] != 2 or s.shape[0] < 1 or s.dtype.kind not in "iu" for s in smp):
+        raise ValueError("samples: B (aligned) or 2B (references first) integer arrays (N_b, 2), N_b >= 1")
+    aligned = len(smp) == B
+    if aligned:
+        for b in range(B):
+            if refs[b].shape != dists[b].shape:
+                raise ValueError(f"aligned sampling: the two images of pair {b} differ in size ({refs[b].shape[:2]} and {dists[b].shape[:2]}); "
+                                 "pass 2B sample arrays for unaligned sampling")
+        smp = smp + smp
+    lens = [s.shape[0] for s in smp[:B]]
+    if [s.shape[0] for s in smp[B:]] != lens:
+        raise ValueError("the two images of a pair need the same patch count")
+    if lengths is not None and [int(n) for n in lengths] != lens:
+        raise ValueError("lengths do not match the sample arrays")
+    sid = None
+    if num_scales > 1:
+        if scale_ids is None:
+            raise ValueError("scale_ids are required when num_scales > 1")
+        sid = [np.asarray(s) for s in scale_ids]
+        if len(sid) == B:
+            sid = sid + sid
+        if len(sid) != 2 * B or any(i.shape != (s.shape[0],) for i, s in zip(sid, smp)):
+            raise ValueError("scale_ids: one array (N_b,) per sample array")
+    return refs, dists, smp, sid, lens
+
+
+class ImagePairVarlenPipeline:
+    """ImagePairPipeline for batches whose images differ in size and patch count: host uint8 images in, scores out, through ONE gather over
+    all images of the batch (patches.extract_patches_varlen's kernel) and forward_varlen -- or, one reference against many distorted images,
+    forward_group(lengths=).  Slots are sized by capacity, not by shape:
+
+        pipe = ImagePairVarlenPipeline(model, max_pairs=32, max_image_bytes=2 * 32 * 3 * 512 * 512, max_patches=32 * 600)
+        q = pipe.submit(refs, dists, samples)               # lists of B host images and B (N_b, 2) sample arrays; q (B,) on the device
+        q = pipe.submit_group(refs, dists, ref_index, samples_ref, samples_dist)
+
+    Each of the `depth` slots owns one pinned byte arena for the images and one pinned int32 block for the tables, samples and scale ids, and
+    their device twins: a batch is two H2D copies on the copy stream, none from pageable memory, and nothing synchronises but the wait for
+    the slot's previous batch (`consumed`).  A loader that decodes straight into the pinned views uses acquire() / launch()."""
+
+    def __init__(self, model, max_pairs: int, max_image_bytes: int, max_patches: int, num_scales: int = 1,
+                 device: Optional[torch.device] = None, depth: int = 2, mean: Sequence[float] = (0.5, 0.5, 0.5),
+                 std: Sequence[float] = (0.5, 0.5, 0.5)):
+        if depth < 2:
+            raise ValueError("depth >= 2 (one buffer set is being filled while another is consumed)")
+        if max_pairs < 1 or max_image_bytes < 1 or max_patches < 1:
+            raise ValueError("max_pairs, max_image_bytes and max_patches must be positive")
+        self.model = model
+        self.max_images, self.max_image_bytes, self.max_patches = 2 * int(max_pairs), int(max_image_bytes), int(max_patches)
+        self.num_scales, self.P = int(num_scales), model.spec.patch_size
+        self.mean, self.std = tuple(mean), tuple(std)
+        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        if self.device.type != "cuda":
+            raise RuntimeError("ImagePairVarlenPipeline runs on the GPU only (no CPU fallback on the product path)")
+        words = 4 * self.max_images + 2 * self.max_patches * (4 if self.num_scales > 1 else 3)
+        self.depth = depth
+        self.host_img = [torch.empty(self.max_image_bytes, dtype=torch.uint8).pin_memory() for _ in range(depth)]
+        self.host_tab = [torch.zeros(words, dtype=torch.int32).pin_memory() for _ in range(depth)]
+        self.dev_img = [torch.empty(self.max_image_bytes, dtype=torch.uint8, device=self.device) for _ in range(depth)]
+        self.dev_tab = [torch.empty(words, dtype=torch.int32, device=self.device) for _ in range(depth)]
+        self.copy_stream = torch.cuda.Stream(device=self.device)
+        self.copied = [torch.cuda.Event() for _ in range(depth)]
+        self.consumed = [torch.cuda.Event() for _ in range(depth)]
+        main = torch.cuda.current_stream(self.device)
+        for ev in self.consumed:
+            ev.record(main)
+        self.count = 0
+        self._batch = None
+
+    def plan(self, sizes_first, sizes_second, lengths_first, lengths_second) -> VarlenBatch:
+        return plan_varlen_batch(sizes_first, sizes_second, lengths_first, lengths_second, max_images=self.max_images,
+                                 max_image_bytes=self.max_image_bytes, max_patches=self.max_patches, num_scales=self.num_scales,
+                                 patch_size=self.P)
+
+    @staticmethod
+    def _split(block, batch: VarlenBatch, multi: bool):
+        """tab | patch_img | samples | scale ids of a slot's int32 block (host tensor or its device twin), packed for this batch."""
+        NI, T = len(batch.sizes), batch.tables.total
+        a, b, c = 4 * NI, 4 * NI + T, 4 * NI + 3 * T
+        return block[:a], block[a:b], block[b:c].view(T, 2), (block[c:c + T] if multi else None)
+
+    def acquire(self, batch: VarlenBatch):
+        """The next slot's PINNED host buffers for `batch` (plan()) as numpy views, once the batch that used the slot `depth` submissions
+        ago no longer reads it: a list of the NI images uint8 [H_i, W_i, 3] (first side first), samples int32 (total, 2) and scale ids
+        int32 (total,) or None, both concatenated in image order.  The tables are written here.  Follow with launch() or launch_group()."""
+        s = self.count % self.depth
+        self.consumed[s].synchronize()
+        t = batch.tables
+        tab, pimg, smp, sid = self._split(self.host_tab[s], batch, self.num_scales > 1)
+        tab.numpy()[:] = t.tab.reshape(-1)
+        pimg.numpy()[:] = t.patch_img
+        arena = self.host_img[s].numpy()
+        views = [arena[o:o + 3 * h * w].reshape(h, w, 3) for o, (h, w) in zip(t.img_off.tolist(), batch.sizes)]
+        self._batch = batch
+        return views, smp.numpy(), (sid.numpy() if sid is not None else None)
+
+    def _gather(self, validate: bool):
+        batch, s = self._batch, self.count % self.depth
+        if batch is None:
+            raise RuntimeError("launch() without acquire()")
+        t, multi = batch.tables, self.num_scales > 1
+        htab, hpimg, hsmp, hsid = self._split(self.host_tab[s], batch, multi)
+        if validate:
+            # the range check the reference gets from numpy fancy-indexing, on the host copy: before anything is enqueued
+            check_samples_host_varlen(hsmp.numpy(), hsid.numpy() if multi else None, batch.sizes, batch.lengths, self.num_scales, self.P)
+        self._batch = None
+        self.count += 1
+        main = torch.cuda.current_stream(self.device)
+        with torch.cuda.stream(self.copy_stream):
+            self.copy_stream.wait_event(self.consumed[s])    # the slot's device buffers were read by batch i - depth
+            self.dev_img[s][:t.image_bytes].copy_(self.host_img[s][:t.image_bytes], non_blocking=True)
+            self.dev_tab[s][:batch.words].copy_(self.host_tab[s][:batch.words], non_blocking=True)
+            self.copied[s].record(self.copy_stream)
+        main.wait_event(self.copied[s])
+        dtab, dpimg, dsmp, dsid = self._split(self.dev_tab[s], batch, multi)
+        out = gather_patches_u8(self.dev_img[s][:t.image_bytes], t, dtab, dpimg, dsmp, dsid, None, self.num_scales, self.mean, self.std, self.P)
+        self.consumed[s].record(main)                        # behind the gather: the slot's images, tables and samples are free again
+        return batch, out
+
+    @staticmethod
+    def _sides(out, k):
+        patches, pos, scales = out
+        return (patches[:k], patches[k:]), (pos[:k], pos[k:]), ((scales[:k], scales[k:]) if scales is not None else (None, None))
+
+    def launch(self, validate: bool = True) -> torch.Tensor:
+        """Enqueue the slot filled through acquire() as B pairs (image b of the first side with image b of the second, equal patch counts):
+        range check on the host, two H2D copies on the copy stream, gather + forward_varlen on the current stream.  Returns q (B,)."""
+        b = self._batch
+        if b is not None and (2 * b.n_first != len(b.sizes) or not np.array_equal(b.lengths[:b.n_first], b.lengths[b.n_first:])):
+            raise ValueError("pairs need as many second-side images as first-side ones, with the same patch counts")
+        batch, out = self._gather(validate)
+        k = int(batch.lengths[:batch.n_first].sum())
+        with torch.no_grad():
+            return self.model.forward_varlen(*self._sides(out, k), batch.lengths[:batch.n_first].tolist())[0]
+
+    def launch_group(self, ref_index, validate: bool = True) -> torch.Tensor:
+        """Enqueue the slot filled through acquire() as G references (first side) and M distorted images (second side) with
+        ref_index[m] in [0, G): ends in forward_group(..., ref_index, lengths=(lengths_ref, lengths_dist)).  Returns q (M,)."""
+        b = self._batch
+        idx = [int(i) for i in ref_index]
+        if b is not None and (len(idx) != len(b.sizes) - b.n_first or any(not 0 <= i < b.n_first for i in idx)):
+            raise ValueError("ref_index: one reference in [0, G) per distorted image")
+        batch, out = self._gather(validate)
+        G = batch.n_first
+        k = int(batch.lengths[:G].sum())
+        with torch.no_grad():
+            return self.model.forward_group(*self._sides(out, k), idx, lengths=(batch.lengths[:G].tolist(), batch.lengths[G:].tolist()))[0]
+
+    def _fill(self, batch, images, smp, sid):
+        # checked on the caller's arrays, so that a refused batch leaves the slot and the streams alone
+        check_samples_host_varlen(np.concatenate(smp), np.concatenate(sid) if sid is not None else None, batch.sizes, batch.lengths,
+                                  self.num_scales, self.P)
+        views, hs, hd = self.acquire(batch)
+        for v, im in zip(views, images):
+            v[...] = im
+        hs[:] = np.concatenate(smp)
+        if hd is not None:
+            hd[:] = np.concatenate(sid)
+
+    def submit(self, refs, dists, samples, lengths=None, scale_ids=None) -> torch.Tensor:
+        """One batch of B pairs of any sizes: refs / dists lists of B host images uint8 [H, W, 3]; samples B arrays (N_b, 2) shared by a
+        pair's two images (aligned sampling: the two must have one size, else ValueError) or 2B arrays, references first (unaligned);
+        scale_ids likewise, (N_b,), when num_scales > 1.  ValueError for a batch over the slot capacity and IndexError for a sample
+        outside its image's level, both before anything is enqueued.  Returns q (B,) on the device; everything is asynchronous."""
+        refs, dists, smp, sid, lens = pair_arguments(refs, dists, samples, lengths, scale_ids, self.num_scales)
+        batch = self.plan([r.shape[:2] for r in refs], [d.shape[:2] for d in dists], lens, lens)
+        self._fill(batch, refs + dists, smp, sid)
+        return self.launch(validate=False)
+
+    def submit_group(self, refs, dists, ref_index, samples_ref, samples_dist, scale_ids_ref=None, scale_ids_dist=None) -> torch.Tensor:
+        """G reference images and M distorted ones of any sizes and patch counts, distorted image m scored against reference ref_index[m]:
+        every reference crosses PCIe once and is encoded once.  samples_ref: G arrays (N_g, 2), samples_dist: M arrays (N_m, 2); scale ids
+        likewise when num_scales > 1.  Returns q (M,) on the device."""
+        refs, dists = [np.asarray(r) for r in refs], [np.asarray(d) for d in dists]
+        smp = [np.asarray(s) for s in list(samples_ref) + list(samples_dist)]
+        if len(samples_ref) != len(refs) or len(samples_dist) != len(dists):
+            raise ValueError("one sample array per image")
+        if any(im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3 for im in refs + dists):
+            raise ValueError("images must be uint8 [H, W, 3]")
+        if any(s.ndim != 2 or s.shape[1] != 2 or s.dtype.kind not in "iu" for s in smp):
+            raise ValueError("samples: integer arrays (N, 2)")
+        sid = None
+        if self.num_scales > 1:
+            if scale_ids_ref is None or scale_ids_dist is None:
+                raise ValueError("scale_ids are required when num_scales > 1")
+            sid = [np.asarray(s) for s in list(scale_ids_ref) + list(scale_ids_dist)]
+            if len(sid) != len(smp) or any(i.shape != (s.shape[0],) for i, s in zip(sid, smp)):
+                raise ValueError("scale_ids: one array (N,) per sample array")
+        G = len(refs)
+        batch = self.plan([r.shape[:2] for r in refs], [d.shape[:2] for d in dists], [s.shape[0] for s in smp[:G]], [s.shape[0] for s in smp[G:]])
+        idx = [int(i) for i in ref_index]
+        if len(idx) != len(dists) or any(not 0 <= i < G for i in idx):
+            raise ValueError("ref_index: one reference in [0, G) per distorted image")
+        self._fill(batch, refs + dists, smp, sid)
+        return self.launch_group(idx, validate=False)
