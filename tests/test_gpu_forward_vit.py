@@ -201,7 +201,8 @@ PROBS_TOL = {True: 1e-5, False: 2e-3}
 @pytest.mark.parametrize("fmt", ["fp16x3", "bf16x3", "fp16", "bf16"])
 def test_probs_kernel_masks_and_stays_in_bounds(fmt):
     """Three packed sequences of S = 37 (not a multiple of 32 or 64): NaN rows behind the last sequence are never read, no element past
-    the (3, 12, 37, 37) output is written, and the values are an fp64 softmax of the planes' own Q / K."""
+    the (3, 12, 37, 37) output is written, and the values are an fp64 softmax of the planes' own Q / K.
+    The key mask itself is pinned at every seam length, on keys that dominate, in tests/test_gpu_attention_seams.py."""
     lib = _lib.load()
     nseq, S, H = 3, 37, 768
     rows = nseq * S

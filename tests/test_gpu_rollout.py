@@ -277,7 +277,8 @@ def test_against_the_rollout_of_the_reference_goldens_maps(name, precision):
 def test_step_kernel_masks_and_stays_in_bounds(fmt):
     """Three packed sequences of S = 37 with NaN canary rows behind the last one, a random positive r summing to 1: the output is finite,
     nothing past it is written, and it is 1/2 r + 1/2 mean_h r^T softmax of the planes' own Q / K in fp64.  An error eps per probability
-    gives at most eps per output (sum r = 1): the bound is PROBS_TOL of test_probs_kernel_masks_and_stays_in_bounds."""
+    gives at most eps per output (sum r = 1): the bound is PROBS_TOL of test_probs_kernel_masks_and_stays_in_bounds.
+    The key mask itself is pinned at every seam length, on keys that dominate, in tests/test_gpu_attention_seams.py."""
     lib = _lib.load()
     nseq, S, H = 3, 37, 768
     rows = nseq * S
