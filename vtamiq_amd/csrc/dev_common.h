@@ -77,7 +77,9 @@ __device__ __forceinline__ void glds16(const void* gsrc, void* lds_wave_base) {
 __device__ __forceinline__ float bf2f(bf16 v) { return (float)v; }
 
 // hi = RNE(v); lo = RNE(v - hi): v ~= hi + lo to ~16 (bf16) / ~22 (f16) significand bits.  f16 subnormals are kept by the
-// conversion and by the MFMA (tools/micro/f16_probe.hip), so no pre-scaling is needed for small values.
+// conversion and by the MFMA (tools/micro/f16_probe.hip), so no pre-scaling is needed for small values.  (The MFMA adds the product
+// of a SUBNORMAL f16 operand at the subnormal exponent 2^-14: accumulator bits below 2^-38 are dropped in that step, an absolute
+// error of at most 3.7e-12 per such product -- measured, and pinned with every conversion here, by tests/test_gpu_exact_values.py.)
 // The value is made opaque first: with fp contraction hipcc otherwise forms hi twice -- once from the fp32-rounded v (the copy
 // that is stored) and once fused with the producing multiply (v_fma_mixlo_f16 on the exact product, the copy lo is taken
 // against); at f16 ties the two differ by one ulp and lo gets the wrong sign (measured: 1e-5 of attention outputs off by an ulp).
@@ -98,8 +100,12 @@ __device__ __forceinline__ float wave_sum(float v) {
 //   gelu(x) = max(x, 0) - |x| g(|x|),   g(a) = 0.5 erfc(a / sqrt 2) = 2^(-1 - a Q(a))
 // (one form for both signs, no cancellation in either tail).  Q is a degree-6 polynomial fitted on a in [0, 5.7] to the
 // weighted minimax of the GELU's absolute error (tools/fit_gelu.py): |gelu - exact| <= 2.8e-7 over x in [-8, 8], i.e. half an
-// fp32 ulp of the result where the bound is attained (x ~ 4.2).  Beyond a = 5.7 g is held at g(5.7) = 6e-9 (relative error of
-// the result < 1e-8).  9 FMA / min / max + 1 transcendental (exp2) per element -- the round-1 form (Abramowitz-Stegun 7.1.26:
+// fp32 ulp of the result where the bound is attained (x ~ 4.2).  Beyond a = 5.7 g is held at g(5.7) = 6.28e-9: for x > 0 the
+// relative error of the result is < 1e-8 (x (1 - g) rounds to x); for x < 0, where the exact result is -0, the result is -|x| g,
+// an ABSOLUTE error of 6.3e-9 |x| (-6.3e-7 at x = -100, -4.1e-4 at fp16's range limit -65504) -- left as it is: the epilogue is
+// VALU-bound and the error is below the operand formats' own there.  tests/test_gpu_exact_values.py pins the bound, both tails and
+// the bit identity of this form with gelu_erf4; tests/test_exact_values.py pins the coefficients of both against each other.
+// 9 FMA / min / max + 1 transcendental (exp2) per element -- the round-1 form (Abramowitz-Stegun 7.1.26:
 // rcp + exp2 + 11 VALU) cost 19 issue slots against these 13, and the fc1 epilogue evaluates 10^8 of these per layer, VALU-bound.
 __device__ __forceinline__ float gelu_erf(float x) {
     const float ax = fabsf(x);
