@@ -143,6 +143,11 @@ IMAGE_SIGNATURES = {
                                           C.POINTER(C.c_float), _P, _P, _P, _I, _I, _P]),
 }
 
+# include/vtamiq_hip_sampler.h: patch coordinates sampled on the device (vtamiq_amd.sampling)
+SAMPLER_SIGNATURES = {
+    "vtq_k_sample_grid": (C.c_int, [_P, _P, _IP, C.POINTER(C.c_uint64), _I, C.c_uint64, _I, _P, _P, _P]),
+}
+
 # the fp8 experiment (include/vtamiq_hip_fp8.h): exported only by a library built with -DVTQ_WITH_FP8 (python -m vtamiq_amd.build --fp8 ->
 # LIB_PATH_FP8, load_fp8()); bound when present
 FP8_SIGNATURES = {
@@ -177,7 +182,8 @@ def load(path: str | None = None) -> C.CDLL:
     # VTQ_LIB_PATH selects WHICH build is loaded (e.g. a build of another tree, for an A/B); it does not relax any check.  An A/B
     # build of an OLDER tree (different ABI: argument layouts may differ) loads only with VTQ_ALLOW_ABI_MISMATCH=1, with a warning.
     relaxed = os.environ.get("VTQ_ALLOW_ABI_MISMATCH") == "1"
-    for name, (res, args) in list(SIGNATURES.items()) + list(ROLLOUT_SIGNATURES.items()) + list(IMAGE_SIGNATURES.items()):
+    for name, (res, args) in (list(SIGNATURES.items()) + list(ROLLOUT_SIGNATURES.items()) + list(IMAGE_SIGNATURES.items())
+                              + list(SAMPLER_SIGNATURES.items())):
         if relaxed and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)          # AttributeError if a declared symbol is not exported

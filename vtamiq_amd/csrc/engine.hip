@@ -20,6 +20,7 @@
 #include "../../include/vtamiq_hip_fp8.h"
 #include "../../include/vtamiq_hip_rollout.h"
 #include "../../include/vtamiq_hip_images.h"
+#include "../../include/vtamiq_hip_sampler.h"
 #include "kernels.h"
 
 using namespace vtq;
@@ -1849,6 +1850,34 @@ int vtq_k_gather_patches_u8(const uint8_t* images, int64_t image_bytes, const in
     if (row0[NI] < 1) return fail("vtq_k_gather_patches_u8: no patches (row0[NI]=%d)", (int)row0[NI]);
     HIP_TRY(launch_gather_patches_u8(images, tab, patch_img, samples, scale_ids, flips, patches, pos, scales, row0[NI], mean, std_, patch_size,
                                      num_scales, (hipStream_t)stream));
+    return 0;
+}
+
+// include/vtamiq_hip_sampler.h: like the gather above, every check reads HOST arrays only
+int vtq_k_sample_grid(const int32_t* seg, const uint64_t* keys, const int32_t* seg_host, const uint64_t* keys_host, int32_t NS, uint64_t seed,
+                      int32_t amount_q, int32_t* samples, int32_t* scale_ids, void* stream) {
+    if (!seg || !keys || !seg_host || !keys_host || !samples) return fail("vtq_k_sample_grid: null argument");
+    if ((uintptr_t)seg % 16) return fail("vtq_k_sample_grid: seg is not 16-byte aligned");
+    if (NS < 1) return fail("vtq_k_sample_grid: NS=%d (at least 1)", (int)NS);
+    if (amount_q < 0 || amount_q > 65535) return fail("vtq_k_sample_grid: amount_q=%d (0 .. 65535)", (int)amount_q);
+    int64_t total = 0;
+    int max_cells = 0;
+    for (int32_t j = 0; j < NS; ++j) {
+        const int32_t* t = seg_host + (int64_t)j * 8;
+        const int32_t first = t[0], n = t[1], Hg = t[2], Wg = t[3], hm = t[4], wm = t[5], level = t[6];
+        if (Hg < 1 || Wg < 1 || (int64_t)Hg * Wg > VTQ_SAMPLER_MAX_CELLS)
+            return fail("vtq_k_sample_grid: segment %d has a grid of %d x %d cells (1 .. %d cells)", (int)j, (int)Hg, (int)Wg, VTQ_SAMPLER_MAX_CELLS);
+        if (n < 1 || n > Hg * Wg) return fail("vtq_k_sample_grid: segment %d asks for %d samples of %d cells", (int)j, (int)n, (int)(Hg * Wg));
+        if (hm < 0 || wm < 0 || hm >= VTQ_SAMPLER_MAX_EXTENT || wm >= VTQ_SAMPLER_MAX_EXTENT)
+            return fail("vtq_k_sample_grid: segment %d has h - P = %d, w - P = %d (0 .. %d)", (int)j, (int)hm, (int)wm, VTQ_SAMPLER_MAX_EXTENT - 1);
+        if (level < 0 || level > 3) return fail("vtq_k_sample_grid: segment %d is on level %d (0 .. 3)", (int)j, (int)level);
+        if (level != 0 && !scale_ids) return fail("vtq_k_sample_grid: scale_ids are required when a segment is on level %d", (int)level);
+        if (first != total) return fail("vtq_k_sample_grid: segment %d starts at row %d, the segments before it end at %lld", (int)j, (int)first, (long long)total);
+        total += n;
+        if (total > 0x7fffffff) return fail("vtq_k_sample_grid: more than 2^31 - 1 samples");
+        max_cells = Hg * Wg > max_cells ? Hg * Wg : max_cells;
+    }
+    HIP_TRY(launch_sample_grid(seg, keys, NS, max_cells, seed, amount_q, samples, scale_ids, (hipStream_t)stream));
     return 0;
 }
 

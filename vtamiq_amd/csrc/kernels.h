@@ -252,6 +252,11 @@ hipError_t launch_gather_patches_u8(const uint8_t* images, const int* tab, const
                                     const int* flips, float* patches, float* pos, float* scales, int64_t total, const float* mean,
                                     const float* sd, int P, int num_scales, hipStream_t s);
 
+// patch_sampler.hip: the samples / scale_ids lists of launch_gather_patches_u8, sampled on the device (include/vtamiq_hip_sampler.h);
+// seg int32 [NS][8], keys uint64 [NS], both on the device; max_cells = the largest Hg * Wg of the table (it sizes the workgroups only)
+hipError_t launch_sample_grid(const int* seg, const uint64_t* keys, int NS, int max_cells, uint64_t seed, int amount_q, int* samples,
+                              int* scale_ids, hipStream_t s);
+
 // ---- measurement: the matrix pipe's sustained rate on this device (mfma_stream.hip) -----------------------------------------
 // f16: 0 bf16, 1 fp16 operands; data: 0 the 3-term mix of gaussian hi / lo planes, 1 zeros, 2 uniform random
 hipError_t mfma_stream_measure(int f16, int data, double warm_s, double timed_s, double* tflops, double* ghz, hipStream_t s);

@@ -17,6 +17,8 @@ validation set's final reductions (rank statistics + the logistic fit, once per 
 
 Batches that mix image sizes and patch counts go through ImagePairVarlenPipeline below: one gather over all images of the batch
 (patches.gather_patches_u8) and forward_varlen / forward_group(lengths=), 0.977 x of forward_varlen alone (profiles/r15_image_varlen.txt).
+Its submit_images / submit_group_images take the images alone: the coordinates are sampled on the device (sampling.py,
+include/vtamiq_hip_sampler.h; profiles/r16_sampler.txt).
 """
 from __future__ import annotations
 
@@ -26,6 +28,7 @@ import numpy as np
 import torch
 
 from .patches import ImageTables, check_samples_host, check_samples_host_varlen, extract_patches, gather_patches_u8, image_tables
+from .sampling import DEFAULT_NUM_SAMPLES_RATIO, PatchSampler, as_keys, launch_sample_grid, plan_samples, repeat_key
 
 
 class ImagePairPipeline:
@@ -192,6 +195,53 @@ def pair_arguments(refs, dists, samples, lengths=None, scale_ids=None, num_scale
     return refs, dists, smp, sid, lens
 
 
+class SampledBatch(NamedTuple):
+    """One batch whose coordinates the device samples (plan_sampled_batch): the varlen batch over its R-fold image list, whose table rows
+    of repeat r > 0 point at the bytes of repeat 0, and the sampler's segment table and keys."""
+    batch: VarlenBatch        # sizes / lengths / tables of the R * NI table rows, first side first, repeat-major within a side
+    seg: np.ndarray           # int32 [NS, 8]  sampling.plan_samples over those rows
+    seg_keys: np.ndarray      # uint64 [NS]
+    n_images: int             # NI: the images that cross PCIe (rows 0 .. of each side's repeat 0)
+    repeats: int
+    front: int                # int32 words of the slot's block that are uploaded: tab, patch_img, seg, keys
+    seg_at: int               # word offset of seg in the block (a multiple of 4); the keys follow it, the device-only samples and ids those
+
+
+def plan_sampled_batch(sizes_first, sizes_second, counts_first, counts_second, keys_first, keys_second, *, max_images: int,
+                       max_image_bytes: int, max_patches: int, repeats: int = 1, num_scales: int = 1,
+                       scale_num_samples_ratio: float = DEFAULT_NUM_SAMPLES_RATIO, patch_size: int = 16) -> SampledBatch:
+    """Argument and capacity checking of submit_images / submit_group_images, device-free.  Each side's images appear `repeats` times,
+    repeat-major, with the keys sampling.repeat_key(key, r): repeats count against max_images and max_patches, the image bytes once.
+    ValueError as plan_varlen_batch, before anything is written."""
+    R = int(repeats)
+    if R < 1:
+        raise ValueError("num_repeats >= 1")
+    nf, ns_ = len(sizes_first), len(sizes_second)
+    base = plan_varlen_batch(sizes_first, sizes_second, counts_first, counts_second, max_images=max_images, max_image_bytes=max_image_bytes,
+                             max_patches=max_patches, num_scales=num_scales, patch_size=patch_size)
+    if R * len(base.sizes) > max_images:
+        raise ValueError(f"{R * len(base.sizes)} images in the batch ({R} repeats), the pipeline was built for {max_images} (2 * max_pairs)")
+    side = R * max(int(base.lengths[:nf].sum()), int(base.lengths[nf:].sum()))
+    if side > max_patches:
+        raise ValueError(f"{side} patches on one side ({R} repeats), the pipeline was built for max_patches={max_patches}")
+    kf, ks = as_keys(keys_first, nf), as_keys(keys_second, ns_)
+    rows = np.concatenate([np.tile(np.arange(nf), R), np.tile(np.arange(nf, nf + ns_), R)])          # the base image of every table row
+    keys = np.array([repeat_key(k, r) for r in range(R) for k in kf.tolist()] + [repeat_key(k, r) for r in range(R) for k in ks.tolist()],
+                    dtype=np.uint64)
+    sizes = [base.sizes[i] for i in rows]
+    lengths = base.lengths[rows]
+    plan = plan_samples(sizes, lengths.tolist(), num_scales, scale_num_samples_ratio, patch_size)
+    t = base.tables
+    row0 = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int32)
+    tables = ImageTables(t.img_off[rows], t.H[rows], t.W[rows], row0, np.ascontiguousarray(t.tab[rows]),
+                         np.repeat(np.arange(len(rows), dtype=np.int32), lengths), t.image_bytes, int(row0[-1]))
+    NI, T, NS = len(rows), tables.total, len(plan.seg)
+    seg_at = (4 * NI + T + 3) // 4 * 4
+    front = seg_at + 10 * NS
+    batch = VarlenBatch(sizes, lengths, R * nf, tables, front + T * (3 if num_scales > 1 else 2))
+    return SampledBatch(batch, np.ascontiguousarray(plan.seg), np.ascontiguousarray(keys[plan.seg_image]), nf + ns_, R, front, seg_at)
+
+
 class ImagePairVarlenPipeline:
     """ImagePairPipeline for batches whose images differ in size and patch count: host uint8 images in, scores out, through ONE gather over
     all images of the batch (patches.extract_patches_varlen's kernel) and forward_varlen -- or, one reference against many distorted images,
@@ -200,6 +250,8 @@ class ImagePairVarlenPipeline:
         pipe = ImagePairVarlenPipeline(model, max_pairs=32, max_image_bytes=2 * 32 * 3 * 512 * 512, max_patches=32 * 600)
         q = pipe.submit(refs, dists, samples)               # lists of B host images and B (N_b, 2) sample arrays; q (B,) on the device
         q = pipe.submit_group(refs, dists, ref_index, samples_ref, samples_dist)
+        q = pipe.submit_images(refs, dists, 500, keys=pair_ids)     # no coordinates: sampled on the device (sampling.py); likewise
+        q = pipe.submit_group_images(refs, dists, ref_index, 500)   # the one-to-many form; num_repeats=R averages R samplings per pair
 
     Each of the `depth` slots owns one pinned byte arena for the images and one pinned int32 block for the tables, samples and scale ids, and
     their device twins: a batch is two H2D copies on the copy stream, none from pageable memory, and nothing synchronises but the wait for
@@ -220,6 +272,9 @@ class ImagePairVarlenPipeline:
         if self.device.type != "cuda":
             raise RuntimeError("ImagePairVarlenPipeline runs on the GPU only (no CPU fallback on the product path)")
         words = 4 * self.max_images + 2 * self.max_patches * (4 if self.num_scales > 1 else 3)
+        # behind what submit() / submit_group() use: room for the sampler's segment table and keys (submit_images: 10 words per
+        # (image, level), 3 of alignment)
+        words += 10 * self.num_scales * self.max_images + 4
         self.depth = depth
         self.host_img = [torch.empty(self.max_image_bytes, dtype=torch.uint8).pin_memory() for _ in range(depth)]
         self.host_tab = [torch.zeros(words, dtype=torch.int32).pin_memory() for _ in range(depth)]
@@ -360,3 +415,140 @@ class ImagePairVarlenPipeline:
             raise ValueError("ref_index: one reference in [0, G) per distorted image")
         self._fill(batch, refs + dists, smp, sid)
         return self.launch_group(idx, validate=False)
+
+    # ---- coordinates sampled on the device (sampling.py, include/vtamiq_hip_sampler.h) ----------------------------------------------
+    def plan_sampled(self, sizes_first, sizes_second, counts_first, counts_second, keys_first, keys_second, repeats: int = 1,
+                     scale_num_samples_ratio: float = DEFAULT_NUM_SAMPLES_RATIO) -> SampledBatch:
+        return plan_sampled_batch(sizes_first, sizes_second, counts_first, counts_second, keys_first, keys_second, max_images=self.max_images,
+                                  max_image_bytes=self.max_image_bytes, max_patches=self.max_patches, repeats=repeats,
+                                  num_scales=self.num_scales, scale_num_samples_ratio=scale_num_samples_ratio, patch_size=self.P)
+
+    def _default_keys(self, n: int) -> list:
+        """keys=None: image / pair b of this pipeline's i-th submission gets (i << 32) | b."""
+        return [(self.count << 32) | b for b in range(n)]
+
+    @staticmethod
+    def _host_images(refs, dists):
+        refs, dists = [np.asarray(r) for r in refs], [np.asarray(d) for d in dists]
+        if len(refs) < 1 or len(dists) < 1:
+            raise ValueError("refs and dists: at least one image each")
+        if any(im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3 for im in refs + dists):
+            raise ValueError("images must be uint8 [H, W, 3]")
+        return refs, dists
+
+    @staticmethod
+    def _counts(patch_count, n: int) -> list:
+        counts = [int(patch_count)] * n if np.ndim(patch_count) == 0 else [int(c) for c in patch_count]
+        if len(counts) != n:
+            raise ValueError("patch_count: one int, or one per pair / image")
+        return counts
+
+    def _split_sampled(self, block, sb: SampledBatch):
+        """tab | patch_img | seg | keys (int32 pairs) | samples | scale ids of a slot's int32 block for a sampled batch."""
+        NI, T, NS = len(sb.batch.sizes), sb.batch.tables.total, len(sb.seg)
+        k, s = sb.seg_at + 8 * NS, sb.front
+        return (block[:4 * NI], block[4 * NI:4 * NI + T], block[sb.seg_at:k].view(NS, 8), block[k:s], block[s:s + 2 * T].view(T, 2),
+                (block[s + 2 * T:s + 3 * T] if self.num_scales > 1 else None))
+
+    def _sample_and_gather(self, sb: SampledBatch, images, seed: int, sampler: Optional[PatchSampler]):
+        """Fill the next slot with the batch's images and tables, upload them (two copies on the copy stream) and, behind them on the copy
+        stream, launch the sampler into the slot's device block; on the current stream the gather that reads it.  The coordinates never
+        exist on the host."""
+        sampler = sampler if sampler is not None else PatchSampler()
+        s = self.count % self.depth
+        self.consumed[s].synchronize()
+        t = sb.batch.tables
+        tab, pimg, seg, keys, _, _ = self._split_sampled(self.host_tab[s], sb)
+        tab.numpy()[:] = t.tab.reshape(-1)
+        pimg.numpy()[:] = t.patch_img
+        seg.numpy()[:] = sb.seg
+        keys.numpy()[:] = sb.seg_keys.view(np.int32)
+        arena = self.host_img[s].numpy()
+        for o, im in zip(self._base_offsets(sb), images):
+            arena[o:o + im.size].reshape(im.shape)[...] = im
+        self._batch = None
+        self.count += 1
+        main = torch.cuda.current_stream(self.device)
+        dtab, dpimg, dseg, dkeys, dsmp, dsid = self._split_sampled(self.dev_tab[s], sb)
+        with torch.cuda.stream(self.copy_stream):
+            self.copy_stream.wait_event(self.consumed[s])
+            self.dev_img[s][:t.image_bytes].copy_(self.host_img[s][:t.image_bytes], non_blocking=True)
+            self.dev_tab[s][:sb.front].copy_(self.host_tab[s][:sb.front], non_blocking=True)
+            # the sampler runs on the copy stream, behind the tables it reads: under the forward of the batch before, not in front of
+            # this batch's gather on the current stream (the slot's samples were last read by batch i - depth: `consumed`)
+            launch_sample_grid(dseg, dkeys, sb.seg, sb.seg_keys, seed, sampler.amount_q, dsmp, dsid)
+            self.copied[s].record(self.copy_stream)
+        main.wait_event(self.copied[s])
+        out = gather_patches_u8(self.dev_img[s][:t.image_bytes], t, dtab, dpimg, dsmp, dsid, None, self.num_scales, self.mean, self.std, self.P)
+        self.consumed[s].record(main)
+        return out
+
+    @staticmethod
+    def _base_offsets(sb: SampledBatch) -> list:
+        """Byte offsets of the NI images that are copied: the table rows of repeat 0 of each side."""
+        nf = sb.batch.n_first // sb.repeats
+        off = sb.batch.tables.img_off
+        return off[:nf].tolist() + off[sb.batch.n_first:sb.batch.n_first + sb.n_images - nf].tolist()
+
+    def _mean_over_repeats(self, q: torch.Tensor, repeats: int) -> torch.Tensor:
+        if repeats == 1:
+            return q
+        from .validate import average_over_repeats
+        return average_over_repeats(q, repeats)
+
+    def submit_images(self, refs, dists, patch_count, keys=None, seed: int = 0, aligned: bool = True, num_repeats: int = 1,
+                      sampler: Optional[PatchSampler] = None, scale_num_samples_ratio: float = DEFAULT_NUM_SAMPLES_RATIO) -> torch.Tensor:
+        """submit() without coordinates: B pairs of host images uint8 [H, W, 3] and patch_count patches per image (one int, or B), sampled
+        on the device by the reference's default sampler (sampling.py).  keys: B 64-bit keys, one per pair (aligned=True: both images get
+        the pair's key and must have one size, so they get the same coordinates) or 2B, references first (aligned=False); None: keys from
+        the pipeline's submission counter.  The samples are a pure function of (seed, key, size, count).  num_repeats=R is the reference's
+        validation repeats: every pair is scored R times with the keys sampling.repeat_key(key, r) -- the images cross PCIe once -- and
+        the R scores are averaged on the device (validate.average_over_repeats): fp64 (B,) then, else q (B,) as submit() returns it.
+        ValueError for a batch over the slot capacity (repeats count against max_pairs and max_patches), before anything is enqueued."""
+        refs, dists = self._host_images(refs, dists)
+        B = len(refs)
+        if len(dists) != B:
+            raise ValueError("refs and dists: B >= 1 images each")
+        if aligned:
+            for b in range(B):
+                if refs[b].shape != dists[b].shape:
+                    raise ValueError(f"aligned sampling: the two images of pair {b} differ in size ({refs[b].shape[:2]} and "
+                                     f"{dists[b].shape[:2]}); pass aligned=False for unaligned sampling")
+            kr = kd = as_keys(self._default_keys(B) if keys is None else keys, B)
+        else:
+            k2 = as_keys(keys, 2 * B) if keys is not None else as_keys([k ^ (s << 63) for s in (0, 1) for k in self._default_keys(B)], 2 * B)
+            kr, kd = k2[:B], k2[B:]
+        counts = self._counts(patch_count, B)
+        sb = self.plan_sampled([r.shape[:2] for r in refs], [d.shape[:2] for d in dists], counts, counts, kr, kd, num_repeats,
+                               scale_num_samples_ratio)
+        out = self._sample_and_gather(sb, refs + dists, seed, sampler)
+        first = sb.batch.lengths[:sb.batch.n_first]
+        with torch.no_grad():
+            q = self.model.forward_varlen(*self._sides(out, int(first.sum())), first.tolist())[0]
+        return self._mean_over_repeats(q, sb.repeats)
+
+    def submit_group_images(self, refs, dists, ref_index, patch_count, keys=None, seed: int = 0, num_repeats: int = 1,
+                            sampler: Optional[PatchSampler] = None, scale_num_samples_ratio: float = DEFAULT_NUM_SAMPLES_RATIO,
+                            patch_count_dist=None) -> torch.Tensor:
+        """submit_group() without coordinates: G references and M distorted images, distorted image m scored against reference
+        ref_index[m].  patch_count: one int or G (references); patch_count_dist: one int or M (default: patch_count, which must then be
+        one int).  keys: G + M keys, references first (None: from the submission counter); a distorted image with its reference's key and
+        size gets its reference's coordinates.  num_repeats as submit_images.  Returns q (M,), fp64 when num_repeats > 1."""
+        refs, dists = self._host_images(refs, dists)
+        G, M = len(refs), len(dists)
+        idx = [int(i) for i in ref_index]
+        if len(idx) != M or any(not 0 <= i < G for i in idx):
+            raise ValueError("ref_index: one reference in [0, G) per distorted image")
+        if patch_count_dist is None:
+            if np.ndim(patch_count) != 0:
+                raise ValueError("patch_count per reference needs patch_count_dist for the distorted images")
+            patch_count_dist = patch_count
+        k = as_keys(self._default_keys(G + M) if keys is None else keys, G + M)
+        sb = self.plan_sampled([r.shape[:2] for r in refs], [d.shape[:2] for d in dists], self._counts(patch_count, G),
+                               self._counts(patch_count_dist, M), k[:G], k[G:], num_repeats, scale_num_samples_ratio)
+        out = self._sample_and_gather(sb, refs + dists, seed, sampler)
+        R, L, nf = sb.repeats, sb.batch.lengths, sb.batch.n_first
+        index = [i + r * G for r in range(R) for i in idx]
+        with torch.no_grad():
+            q = self.model.forward_group(*self._sides(out, int(L[:nf].sum())), index, lengths=(L[:nf].tolist(), L[nf:].tolist()))[0]
+        return self._mean_over_repeats(q, R)
