@@ -298,3 +298,174 @@ def test_submit_group_matches_forward_group_on_the_direct_path(nscales):
     assert q.shape == (5,) and same(q, want)
     with pytest.raises(ValueError):
         pipe.submit_group(col(ref, 0), col(dist, 0), [0, 1, 2, 0, 1], col(ref, 1), col(dist, 1), **ids)       # reference 2 of 2
+
+
+# ---- 6: acquire() + launch(), entries mixed on one ring, the uniform pipeline both ways ------------------------------------------------
+def _group_case(nscales):
+    rs = np.random.RandomState(17)
+    ref = [_image_and_samples(rs, PIPE_SIZES[k], n, nscales) for k, n in ((0, 33), (1, 60))]
+    dist = [_image_and_samples(rs, PIPE_SIZES[k], n, nscales) for k, n in ((0, 33), (1, 20), (2, 47), (1, 60), (0, 25))]
+    return ref, dist, [0, 1, 1, 0, 1]
+
+
+def _col(x, k):
+    return [t[k] for t in x]
+
+
+CAP = dict(max_pairs=4, max_image_bytes=2 * 3 * (96 * 128 * 2 + 80 * 80 + 48 * 64), max_patches=4 * 60)
+
+
+def _write(pinned, images, smp, sid):
+    views, hs, hd = pinned
+    assert len(views) == len(images) and (hd is None) == (sid is None)
+    for v, im in zip(views, images):
+        assert v.shape == im.shape and v.dtype == np.uint8
+        v[...] = im
+    hs[:] = np.concatenate(smp)
+    if hd is not None:
+        hd[:] = np.concatenate(sid)
+    return hs
+
+
+@pytest.mark.parametrize("nscales", [1, 3])
+def test_acquire_and_launch_have_the_bits_of_submit(nscales):
+    """The caller writes images and samples into the pinned views of acquire(): launch() equals submit() and launch_group() equals
+    submit_group() of the same batch on a fresh pipeline, bit for bit.  launch() without acquire() is a RuntimeError; a sample one row past
+    its level in the pinned view an IndexError that takes no slot, and the corrected view gives the right bits; sides that differ in patch
+    counts are no pairs."""
+    m = _model(nscales)
+    cap = dict(CAP, num_scales=nscales)
+    refs, dists, smp, sid = _batches(nscales)[0]
+    want = ImagePairVarlenPipeline(m, **cap).submit(refs, dists, smp, scale_ids=sid)
+    pipe = ImagePairVarlenPipeline(m, **cap)
+    with pytest.raises(RuntimeError):
+        pipe.launch()
+    lens = [len(s) for s in smp]
+    batch = pipe.plan([r.shape[:2] for r in refs], [d.shape[:2] for d in dists], lens, lens)
+    hs = _write(pipe.acquire(batch), refs + dists, smp + smp, sid + sid if sid is not None else None)
+    row = lens[0] + 3                                                 # sample 3 of the second image
+    keep = int(hs[row, 0])
+    hs[row, 0] = (refs[1].shape[0] >> (int(sid[1][3]) if sid is not None else 0)) - 15                 # one row past its level
+    with pytest.raises(IndexError):
+        pipe.launch()
+    assert pipe.count == 0 and pipe._batch is batch, "a refused launch took the slot"
+    hs[row, 0] = keep
+    got = pipe.launch()
+    assert pipe.count == 1 and pipe._batch is None
+    torch.cuda.synchronize()
+    assert got.shape == (len(refs),) and same(got, want)
+    direct = _direct(m, (refs, dists, smp, sid), nscales)
+    torch.cuda.synchronize()
+    assert same(want, direct)
+
+    ref, dist, index = _group_case(nscales)
+    ids = dict(scale_ids_ref=_col(ref, 2), scale_ids_dist=_col(dist, 2)) if nscales > 1 else {}
+    want = ImagePairVarlenPipeline(m, **cap).submit_group(_col(ref, 0), _col(dist, 0), index, _col(ref, 1), _col(dist, 1), **ids)
+    both = ref + dist
+    batch = pipe.plan([t[0].shape[:2] for t in ref], [t[0].shape[:2] for t in dist], [len(t[1]) for t in ref], [len(t[1]) for t in dist])
+    _write(pipe.acquire(batch), _col(both, 0), _col(both, 1), _col(both, 2) if nscales > 1 else None)
+    with pytest.raises(ValueError):                                   # 2 references and 5 distorted images are no pairs
+        pipe.launch()
+    assert pipe.count == 1 and pipe._batch is batch
+    got = pipe.launch_group(index)
+    torch.cuda.synchronize()
+    assert got.shape == (5,) and same(got, want) and pipe.count == 2
+
+    pipe.acquire(pipe.plan([(48, 64), (80, 80)], [(48, 64), (80, 80)], [20, 30], [20, 31]))
+    with pytest.raises(ValueError):                                   # as many images on both sides, other patch counts
+        pipe.launch()
+    assert pipe.count == 2
+
+
+def _mixed_calls(nscales):
+    """Seven calls cycling through the four entries, each another layout of a slot's block; the keys are given, so that a result does
+    not depend on the pipeline's submission counter."""
+    b = _batches(nscales)
+    ref, dist, index = _group_case(nscales)
+    ids = dict(scale_ids_ref=_col(ref, 2), scale_ids_dist=_col(dist, 2)) if nscales > 1 else {}
+    ids2 = dict(scale_ids_ref=_col(ref, 2)[::-1], scale_ids_dist=_col(dist, 2)[:3]) if nscales > 1 else {}
+    return [
+        lambda p: p.submit(b[0][0], b[0][1], b[0][2], scale_ids=b[0][3]),
+        lambda p: p.submit_images(b[1][0], b[1][1], 30, keys=[11, 12, 13, 14], seed=5),
+        lambda p: p.submit_group(_col(ref, 0), _col(dist, 0), index, _col(ref, 1), _col(dist, 1), **ids),
+        lambda p: p.submit_group_images(_col(ref, 0), _col(dist, 0), index, [33, 60], keys=list(range(100, 107)), seed=5,
+                                        patch_count_dist=[33, 20, 47, 60, 25]),
+        lambda p: p.submit(b[2][0], b[2][1], b[2][2], scale_ids=b[2][3]),                               # unaligned: 2B sample arrays
+        lambda p: p.submit_images(b[3][0], b[3][1], [25, 40, 31, 52], keys=[2 ** 63 + 1, 22, 23, 24], seed=6),
+        lambda p: p.submit_group(_col(ref, 0)[::-1], _col(dist, 0)[:3], [1, 0, 0], _col(ref, 1)[::-1], _col(dist, 1)[:3], **ids2),
+    ]
+
+
+@pytest.mark.parametrize("side_stream", [False, True], ids=["default-stream", "side-stream"])
+@pytest.mark.parametrize("depth", [2, 3])
+@pytest.mark.parametrize("nscales", [1, 3])
+def test_entries_mixed_on_one_ring_have_the_bits_of_a_fresh_pipeline(nscales, depth, side_stream):
+    """submit, submit_images, submit_group, submit_group_images in turn on ONE pipeline: every slot is reused by a batch of another layout
+    (host-sampled: the whole block is uploaded; device-sampled: its front, the rest is written by the sampler).  Each result equals the
+    same call on a pipeline of its own; a batch refused in the middle (five pairs into max_pairs=4) takes no slot and the calls behind
+    it are still right.  Also with a side stream current while the default stream is busy."""
+    m = _model(nscales)
+    cap = dict(CAP, num_scales=nscales, depth=depth)
+    calls = _mixed_calls(nscales)
+    refs, dists, smp, sid = _batches(nscales)[4]
+
+    def run():
+        pipe = ImagePairVarlenPipeline(m, **cap)
+        got = []
+        for i, call in enumerate(calls):
+            if i == 4:
+                with pytest.raises(ValueError):
+                    pipe.submit(refs + refs[:2], dists + dists[:2], smp + smp[:2], scale_ids=sid + sid[:2] if sid is not None else None)
+                assert pipe.count == 4 and pipe._batch is None, "a refused batch took a slot"
+            got.append(call(pipe))
+        assert pipe.count == len(calls)
+        return got
+
+    if side_stream:
+        side, busy = torch.cuda.Stream(), Busy()
+        torch.cuda.synchronize()
+        busy(torch.cuda.default_stream())
+        with torch.cuda.stream(side):
+            got = run()
+    else:
+        got = run()
+    torch.cuda.synchronize()
+    for i, (call, g) in enumerate(zip(calls, got)):
+        want = call(ImagePairVarlenPipeline(m, **cap))
+        torch.cuda.synchronize()
+        assert same(g, want), i
+    assert [g.shape[0] for g in got] == [3, 4, 5, 5, 2, 4, 3]
+
+
+@pytest.mark.parametrize("nscales,size", [(1, (48, 64)), (3, (96, 128))], ids=["1-scale-48x64", "3-scales-96x128"])
+def test_uniform_pipeline_acquire_and_launch_have_the_bits_of_submit(nscales, size):
+    """ImagePairPipeline both ways at B = 2, N = 24: three batches decoded into the pinned views of acquire() and launched -- the call
+    sequence of bench.py -- equal submit() of the same arrays on a pipeline of its own.  Three scales run at 96 x 128: level 2 of a 48 x 64
+    image (12 x 16) is smaller than a 16 x 16 patch, and extract_patches refuses such a batch whole."""
+    from vtamiq_amd.pipeline import ImagePairPipeline
+    m = _model(nscales)
+    B, N = 2, 24
+    rs = np.random.RandomState(23)
+    a, b = ImagePairPipeline(m, B, size, N, num_scales=nscales), ImagePairPipeline(m, B, size, N, num_scales=nscales)
+    got, want = [], []
+    for it in range(3):
+        items = [_image_and_samples(rs, size, N, nscales) for _ in range(2 * B)]
+        img, smp, sid = (np.stack(_col(items, k)) for k in range(3))
+        hi, hs, hd = a.acquire()
+        assert hi.shape == img.shape and hs.shape == smp.shape and (hd is None) == (nscales == 1)
+        hi[:], hs[:] = img, smp
+        if hd is not None:
+            hd[:] = sid
+        got.append(a.launch())
+        want.append(b.submit(img[:B], img[B:], smp, sid if nscales > 1 else None))
+    torch.cuda.synchronize()
+    assert a.count == b.count == 3
+    for g, w in zip(got, want):
+        assert g.shape == (B,) and same(g, w)
+    assert not torch.equal(got[0], got[1])
+    with torch.no_grad():
+        pa, po, sc = extract_patches(torch.from_numpy(img).to(DEV), torch.from_numpy(smp).to(DEV),
+                                     torch.from_numpy(sid).to(DEV) if nscales > 1 else None, nscales)
+        direct = m((pa[:B], pa[B:]), (po[:B], po[B:]), (sc[:B], sc[B:]) if sc is not None else (None, None))[0]
+    torch.cuda.synchronize()
+    assert same(got[2], direct)

@@ -12,32 +12,41 @@ import torch
 from . import _lib
 
 
-def check_samples_host(samples: torch.Tensor, scale_ids: Optional[torch.Tensor], H: int, W: int, num_scales: int = 1, patch_size: int = 16) -> None:
-    """The range check of the sampled coordinates (IndexError like the reference's numpy fancy-indexing).  Works on the tensors where they
-    are: host tensors cost no GPU synchronisation (a pipelined loader calls this BEFORE the copy and passes validate=False below)."""
-    P = int(patch_size)
-    if samples.device.type == "cpu" and (scale_ids is None or scale_ids.device.type == "cpu"):
-        # numpy on the calling thread: torch CPU operators on these small tensors wake the intra-op thread pool, whose spinning workers
-        # then compete with the HIP runtime's own threads -- measured: a pipelined loop fell from 15.4 to 31 ms per batch with the
-        # torch form of this check on the host (tools/e2e_probe.py)
-        import numpy as np
-        smp_np = samples.detach().numpy()
-        lvl_np = scale_ids.detach().numpy().astype(np.int64) if scale_ids is not None else np.zeros(smp_np.shape[:2], dtype=np.int64)
-        if ((lvl_np < 0) | (lvl_np >= num_scales)).any():
-            raise IndexError("scale_ids outside [0, num_scales)")
-        hmax_np = np.array([(H >> s) - P for s in range(num_scales)])[lvl_np]
-        wmax_np = np.array([(W >> s) - P for s in range(num_scales)])[lvl_np]
-        if ((smp_np[..., 0] < 0) | (smp_np[..., 0] > hmax_np) | (smp_np[..., 1] < 0) | (smp_np[..., 1] > wmax_np)).any():
-            raise IndexError(f"patch sample outside its pyramid level (row in [0, h-{P}], col in [0, w-{P}] required)")
-        return
-    smp = samples.to(torch.int64)
-    lvl = scale_ids.to(device=smp.device, dtype=torch.int64) if scale_ids is not None else torch.zeros(smp.shape[:2], dtype=torch.int64, device=smp.device)
-    if bool(((lvl < 0) | (lvl >= num_scales)).any()):
+def _in_range(samples: np.ndarray, levels: Optional[np.ndarray], dims: np.ndarray, num_scales: int, P: int) -> None:
+    """THE range rule of a sample, stated once: level in [0, num_scales), 0 <= row <= (H >> level) - P, 0 <= col <= (W >> level) - P.
+    samples int [..., 2], levels int [...] or None (all level 0), dims int (H, W) of each sample's image, [..., 2] or [2]; IndexError
+    like the reference's numpy fancy-indexing."""
+    # numpy on the calling thread: torch CPU operators on these small tensors wake the intra-op thread pool, whose spinning workers
+    # then compete with the HIP runtime's own threads -- measured: a pipelined loop fell from 15.4 to 31 ms per batch with the
+    # torch form of this check on the host (tools/e2e_probe.py)
+    lvl = levels.astype(np.int64) if levels is not None else np.zeros(samples.shape[:-1], dtype=np.int64)
+    if ((lvl < 0) | (lvl >= num_scales)).any():
         raise IndexError("scale_ids outside [0, num_scales)")
-    hmax = torch.tensor([(H >> s) - P for s in range(num_scales)], device=smp.device)[lvl]
-    wmax = torch.tensor([(W >> s) - P for s in range(num_scales)], device=smp.device)[lvl]
-    if bool(((smp[..., 0] < 0) | (smp[..., 0] > hmax) | (smp[..., 1] < 0) | (smp[..., 1] > wmax)).any()):
-        raise IndexError(f"patch sample outside its pyramid level (row in [0, h-{P}], col in [0, w-{P}] required)")
+    lim = (dims >> lvl[..., None]) - P
+    if ((samples < 0) | (samples > lim)).any():
+        raise IndexError(f"patch sample outside its image's pyramid level (row in [0, h-{P}], col in [0, w-{P}] required)")
+
+
+def _check_levels(num_scales: int, scale_ids) -> None:
+    if not 1 <= num_scales <= 4:
+        raise ValueError("1 <= num_scales <= 4")
+    if num_scales > 1 and scale_ids is None:
+        raise ValueError("scale_ids are required when num_scales > 1")
+
+
+def _patch_size(patch_size: int) -> int:
+    if int(patch_size) not in (16, 8):
+        raise ValueError("patch_size must be 16 or 8")
+    return int(patch_size)
+
+
+def check_samples_host(samples: torch.Tensor, scale_ids: Optional[torch.Tensor], H: int, W: int, num_scales: int = 1, patch_size: int = 16) -> None:
+    """The range check of the sampled coordinates (IndexError like the reference's numpy fancy-indexing).  Host tensors are checked where
+    they are and cost no GPU synchronisation (a pipelined loader calls this BEFORE the copy and passes validate=False below); device
+    tensors are read back, which synchronises."""
+    to_np = lambda a: a.detach().numpy() if a.device.type == "cpu" else a.detach().cpu().numpy()
+    _in_range(to_np(samples), to_np(scale_ids) if scale_ids is not None else None, np.array([H, W], dtype=np.int64), num_scales,
+              int(patch_size))
 
 
 def extract_patches(images_u8: torch.Tensor, samples: torch.Tensor, scale_ids: Optional[torch.Tensor] = None, num_scales: int = 1,
@@ -58,13 +67,8 @@ def extract_patches(images_u8: torch.Tensor, samples: torch.Tensor, scale_ids: O
     N = samples.shape[1]
     if tuple(samples.shape) != (NI, N, 2):
         raise ValueError("samples must be int32 [NI, N, 2]")
-    if num_scales > 1 and scale_ids is None:
-        raise ValueError("scale_ids are required when num_scales > 1")
-    if not 1 <= num_scales <= 4:
-        raise ValueError("1 <= num_scales <= 4")
-    P = int(patch_size)
-    if P not in (16, 8):
-        raise ValueError("patch_size must be 16 or 8")
+    _check_levels(num_scales, scale_ids)
+    P = _patch_size(patch_size)
     # Range checks the reference gets for free from numpy fancy-indexing (an out-of-range patch raises IndexError there); the
     # gather kernel itself does not bounds-check.  One small reduction + sync per call, on the loader side of the pipeline.
     if (H >> (num_scales - 1)) < P or (W >> (num_scales - 1)) < P:
@@ -146,30 +150,17 @@ def check_samples_host_varlen(samples, scale_ids, sizes, lengths, num_scales: in
     """check_samples_host for images of different sizes: samples (total, 2) and scale_ids (total,) or None are the per-image lists
     concatenated, image i = (H_i, W_i) owning lengths[i] rows.  Every sample must lie inside ITS image's level -- a small image may use fewer levels than
     num_scales; a sample on a level of its image that is smaller than one patch has no valid position -- IndexError otherwise, like the
-    reference's fancy indexing.  numpy on the calling thread, for
-    check_samples_host's reason: torch CPU operators wake the intra-op pool, which doubled a pipelined loop's time."""
-    P = int(patch_size)
-    if not 1 <= num_scales <= 4:
-        raise ValueError("1 <= num_scales <= 4")
+    reference's fancy indexing.  numpy on the calling thread (_in_range says why)."""
+    _check_levels(num_scales, scale_ids)
     sz = _sizes(sizes)
     ln = np.asarray(lengths, dtype=np.int64)
     smp = np.asarray(samples)
     if ln.shape != (sz.shape[0],) or smp.shape != (int(ln.sum()), 2):
         raise ValueError("samples must be (sum(lengths), 2), lengths one count per image")
-    if scale_ids is None:
-        if num_scales > 1:
-            raise ValueError("scale_ids are required when num_scales > 1")
-        lvl = np.zeros(smp.shape[0], dtype=np.int64)
-    else:
-        lvl = np.asarray(scale_ids).astype(np.int64)
-        if lvl.shape != (smp.shape[0],):
-            raise ValueError("scale_ids must be (sum(lengths),)")
-        if ((lvl < 0) | (lvl >= num_scales)).any():
-            raise IndexError("scale_ids outside [0, num_scales)")
-    dims = np.repeat(sz, ln, axis=0)                         # (total, 2): the image of every row
-    lim = (dims >> lvl[:, None]) - P
-    if ((smp < 0) | (smp > lim)).any():
-        raise IndexError(f"patch sample outside its image's pyramid level (row in [0, h-{P}], col in [0, w-{P}] required)")
+    lvl = np.asarray(scale_ids) if scale_ids is not None else None
+    if lvl is not None and lvl.shape != (smp.shape[0],):
+        raise ValueError("scale_ids must be (sum(lengths),)")
+    _in_range(smp, lvl, np.repeat(sz, ln, axis=0), num_scales, int(patch_size))           # dims (total, 2): the image of every row
 
 
 def gather_patches_u8(flat: torch.Tensor, tables: ImageTables, dev_tab: torch.Tensor, dev_patch_img: torch.Tensor, samples: torch.Tensor,
@@ -226,13 +217,8 @@ def extract_patches_varlen(images, samples, lengths, scale_ids=None, num_scales:
         flat = torch.cat([i.contiguous().reshape(-1) for i in images])
     if flat.dtype != torch.uint8 or flat.dim() != 1:
         raise ValueError("the flat image tensor must be uint8 and one-dimensional")
-    P = int(patch_size)
-    if P not in (16, 8):
-        raise ValueError("patch_size must be 16 or 8")
-    if not 1 <= num_scales <= 4:
-        raise ValueError("1 <= num_scales <= 4")
-    if num_scales > 1 and scale_ids is None:
-        raise ValueError("scale_ids are required when num_scales > 1")
+    P = _patch_size(patch_size)
+    _check_levels(num_scales, scale_ids)
     lengths = [int(n) for n in (lengths.tolist() if isinstance(lengths, (torch.Tensor, np.ndarray)) else lengths)]
     tables = image_tables(sizes, lengths)
     if tables.total < 1:

@@ -19,6 +19,12 @@ Batches that mix image sizes and patch counts go through ImagePairVarlenPipeline
 (patches.gather_patches_u8) and forward_varlen / forward_group(lengths=), 0.977 x of forward_varlen alone (profiles/r15_image_varlen.txt).
 Its submit_images / submit_group_images take the images alone: the coordinates are sampled on the device (sampling.py,
 include/vtamiq_hip_sampler.h; profiles/r16_sampler.txt).
+
+Both pipelines are a _SlotRing, whose free_slot / upload / release ARE the slot protocol: no other code touches the copy stream or the
+events.  The uniform pipeline's slot is three tensors of one shape; the varlen pipeline's is a byte arena and one int32 block whose word
+ranges block_layout names for both kinds of batch (VarlenBatch: host-sampled, SampledBatch: device-sampled).  Every varlen entry is
+plan -> _stage (the one place a slot's host side is written) -> _upload_and_gather (the one place it is enqueued; the sampler is its
+optional step on the copy stream) -> _as_pairs or _as_group.  The argument checks the entries share stand in front of the classes.
 """
 from __future__ import annotations
 
@@ -28,31 +34,24 @@ import numpy as np
 import torch
 
 from .patches import ImageTables, check_samples_host, check_samples_host_varlen, extract_patches, gather_patches_u8, image_tables
-from .sampling import DEFAULT_NUM_SAMPLES_RATIO, PatchSampler, as_keys, launch_sample_grid, plan_samples, repeat_key
+from .sampling import DEFAULT_NUM_SAMPLES_RATIO, PatchSampler, as_keys, launch_sample_grid, patch_counts, plan_samples, repeat_key
 
 
-class ImagePairPipeline:
-    def __init__(self, model, pairs_per_batch: int, image_hw: Tuple[int, int], patches: int, num_scales: int = 1,
-                 device: Optional[torch.device] = None, depth: int = 2, mean: Sequence[float] = (0.5, 0.5, 0.5),
-                 std: Sequence[float] = (0.5, 0.5, 0.5)):
+class _SlotRing:
+    """`depth` buffer sets (slots) used in turn, a copy stream and two events per slot.  The protocol of a submission on slot s:
+      free_slot()   the host waits for consumed[s]: the batch `depth` submissions ago no longer reads the slot's host or device buffers
+      upload()      on the copy stream: wait for consumed[s], the H2D copies, an optional step behind them, record copied[s]; the stream
+                    current at the call then waits for copied[s]
+      release()     record consumed[s] on the current stream, directly behind the gather that read the slot -- not behind the forward
+    `count` is the number of submissions enqueued; a refused batch is not counted and enqueues nothing."""
+
+    def __init__(self, device: Optional[torch.device], depth: int):
         if depth < 2:
             raise ValueError("depth >= 2 (one buffer set is being filled while another is consumed)")
-        self.model = model
-        self.B, self.N, self.num_scales = int(pairs_per_batch), int(patches), int(num_scales)
-        self.H, self.W = int(image_hw[0]), int(image_hw[1])
-        self.P = model.spec.patch_size
-        self.mean, self.std = tuple(mean), tuple(std)
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         if self.device.type != "cuda":
-            raise RuntimeError("ImagePairPipeline runs on the GPU only (no CPU fallback on the product path)")
-        NI = 2 * self.B
+            raise RuntimeError(f"{type(self).__name__} runs on the GPU only (no CPU fallback on the product path)")
         self.depth = depth
-        self.host_img = [torch.empty(NI, self.H, self.W, 3, dtype=torch.uint8).pin_memory() for _ in range(depth)]
-        self.host_smp = [torch.empty(NI, self.N, 2, dtype=torch.int32).pin_memory() for _ in range(depth)]
-        self.host_sid = [torch.zeros(NI, self.N, dtype=torch.int32).pin_memory() for _ in range(depth)] if num_scales > 1 else None
-        self.dev_img = [torch.empty(NI, self.H, self.W, 3, dtype=torch.uint8, device=self.device) for _ in range(depth)]
-        self.dev_smp = [torch.empty(NI, self.N, 2, dtype=torch.int32, device=self.device) for _ in range(depth)]
-        self.dev_sid = [torch.empty(NI, self.N, dtype=torch.int32, device=self.device) for _ in range(depth)] if num_scales > 1 else None
         self.copy_stream = torch.cuda.Stream(device=self.device)
         self.copied = [torch.cuda.Event() for _ in range(depth)]
         self.consumed = [torch.cuda.Event() for _ in range(depth)]
@@ -60,6 +59,97 @@ class ImagePairPipeline:
         for ev in self.consumed:
             ev.record(main)
         self.count = 0
+
+    def free_slot(self) -> int:
+        s = self.count % self.depth
+        self.consumed[s].synchronize()
+        return s
+
+    def upload(self, s: int, copies, behind=None) -> None:
+        """copies: (device tensor, pinned host tensor) pairs; behind: run with the copy stream current.  Counts the submission."""
+        self.count += 1
+        main = torch.cuda.current_stream(self.device)
+        with torch.cuda.stream(self.copy_stream):
+            self.copy_stream.wait_event(self.consumed[s])    # the slot's device buffers were read by batch i - depth
+            for dst, src in copies:
+                dst.copy_(src, non_blocking=True)
+            if behind is not None:
+                behind()
+            self.copied[s].record(self.copy_stream)
+        main.wait_event(self.copied[s])
+
+    def release(self, s: int) -> None:
+        self.consumed[s].record(torch.cuda.current_stream(self.device))
+
+
+# ---- argument checks shared by the entries, device-free ------------------------------------------------------------------------------------
+def _two_sides(x, B: int, what: str):
+    """x for B pairs, shared by a pair's two images (aligned sampling), or for 2B images, references first -> (first side's, second's)."""
+    if len(x) not in (B, 2 * B):
+        raise ValueError(f"{what}: B (aligned, shared by a pair's two images) or 2B (references first), B = {B}")
+    return (x, x) if len(x) == B else (x[:B], x[B:])
+
+
+def _host_images(refs, dists, pairs: bool = False):
+    """Two lists of host images uint8 [H, W, 3] as numpy arrays, at least one each; pairs: as many distorted images as references."""
+    refs, dists = [np.asarray(r) for r in refs], [np.asarray(d) for d in dists]
+    if len(refs) < 1 or len(dists) < 1 or (pairs and len(dists) != len(refs)):
+        raise ValueError("refs and dists: B >= 1 images each" if pairs else "refs and dists: at least one image each")
+    if any(im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3 for im in refs + dists):
+        raise ValueError("images must be uint8 [H, W, 3]")
+    return refs, dists
+
+
+def _aligned_sizes(refs, dists) -> None:
+    for b, (r, d) in enumerate(zip(refs, dists)):
+        if r.shape != d.shape:
+            raise ValueError(f"aligned sampling: pair {b}'s images differ in size ({r.shape[:2]}, {d.shape[:2]}); pass 2B sample arrays / aligned=False")
+
+
+def _ref_indices(ref_index, G: int, M: int) -> list:
+    idx = [int(i) for i in ref_index]
+    if len(idx) != M or any(not 0 <= i < G for i in idx):
+        raise ValueError("ref_index: one reference in [0, G) per distorted image")
+    return idx
+
+
+def _sample_lists(samples, scale_ids, num_scales: int):
+    """One integer array (N_i, 2), N_i >= 1, per image and, with levels, one scale-id array (N_i,) each -> (samples, scale ids or None)."""
+    smp = [np.asarray(s) for s in samples]
+    if any(s.ndim != 2 or s.shape[1] != 2 or s.shape[0] < 1 or s.dtype.kind not in "iu" for s in smp):
+        raise ValueError("samples: integer arrays (N, 2), N >= 1")
+    if num_scales <= 1:
+        return smp, None
+    if scale_ids is None:
+        raise ValueError("scale_ids are required when num_scales > 1")
+    sid = [np.asarray(i) for i in scale_ids]
+    if len(sid) != len(smp) or any(i.shape != (s.shape[0],) for i, s in zip(sid, smp)):
+        raise ValueError("scale_ids: one array (N,) per sample array")
+    return smp, sid
+
+
+def _sides(out, k: int):
+    """The gather's (patches, pos, scales) split behind row k: the call tensors of the two sides."""
+    patches, pos, scales = out
+    return (patches[:k], patches[k:]), (pos[:k], pos[k:]), ((scales[:k], scales[k:]) if scales is not None else (None, None))
+
+
+class ImagePairPipeline(_SlotRing):
+    def __init__(self, model, pairs_per_batch: int, image_hw: Tuple[int, int], patches: int, num_scales: int = 1,
+                 device: Optional[torch.device] = None, depth: int = 2, mean: Sequence[float] = (0.5, 0.5, 0.5),
+                 std: Sequence[float] = (0.5, 0.5, 0.5)):
+        super().__init__(device, depth)
+        self.model = model
+        self.B, self.N, self.num_scales = int(pairs_per_batch), int(patches), int(num_scales)
+        self.H, self.W, self.P = int(image_hw[0]), int(image_hw[1]), model.spec.patch_size
+        self.mean, self.std = tuple(mean), tuple(std)
+        NI = 2 * self.B
+        self.host_img = [torch.empty(NI, self.H, self.W, 3, dtype=torch.uint8).pin_memory() for _ in range(depth)]
+        self.host_smp = [torch.empty(NI, self.N, 2, dtype=torch.int32).pin_memory() for _ in range(depth)]
+        self.host_sid = [torch.zeros(NI, self.N, dtype=torch.int32).pin_memory() for _ in range(depth)] if num_scales > 1 else None
+        self.dev_img = [torch.empty(NI, self.H, self.W, 3, dtype=torch.uint8, device=self.device) for _ in range(depth)]
+        self.dev_smp = [torch.empty(NI, self.N, 2, dtype=torch.int32, device=self.device) for _ in range(depth)]
+        self.dev_sid = [torch.empty(NI, self.N, dtype=torch.int32, device=self.device) for _ in range(depth)] if num_scales > 1 else None
 
     @staticmethod
     def _np(a):
@@ -69,58 +159,76 @@ class ImagePairPipeline:
         """The next slot's PINNED host buffers as numpy views -- images uint8 [2B, H, W, 3] (ref rows first), samples int32 [2B, N, 2], scale ids
         int32 [2B, N] or None -- once the batch that used them `depth` submissions ago no longer reads them.  A loader that decodes straight
         into these views saves the host copy of submit(); follow with launch()."""
-        s = self.count % self.depth
-        self.consumed[s].synchronize()                       # the slot's buffers are no longer being copied from / gathered from (batch i - depth)
+        s = self.free_slot()
         return self.host_img[s].numpy(), self.host_smp[s].numpy(), (self.host_sid[s].numpy() if self.host_sid is not None else None)
 
     def launch(self) -> torch.Tensor:
         """Enqueue the slot filled through acquire(): range check of the samples on the host, H2D on the copy stream, gather + forward on the
         current stream.  Returns the batch's scores as a device tensor [B]."""
-        s = self.count % self.depth
-        self.count += 1
-        B = self.B
+        s, B, multi = self.count % self.depth, self.B, self.host_sid is not None
         # the range check the reference gets from numpy fancy-indexing, on the host copy (no GPU synchronisation, no torch CPU operators)
-        check_samples_host(self.host_smp[s], self.host_sid[s] if self.host_sid is not None else None, self.H, self.W, self.num_scales, self.P)
-        main = torch.cuda.current_stream(self.device)
-        with torch.cuda.stream(self.copy_stream):
-            self.copy_stream.wait_event(self.consumed[s])    # the slot's device buffers were read by batch i - depth
-            self.dev_img[s].copy_(self.host_img[s], non_blocking=True)
-            self.dev_smp[s].copy_(self.host_smp[s], non_blocking=True)
-            if self.dev_sid is not None:
-                self.dev_sid[s].copy_(self.host_sid[s], non_blocking=True)
-            self.copied[s].record(self.copy_stream)
-        main.wait_event(self.copied[s])
-        patches, pos, scales = extract_patches(self.dev_img[s], self.dev_smp[s], self.dev_sid[s] if self.dev_sid is not None else None,
-                                               self.num_scales, mean=self.mean, std=self.std, patch_size=self.P, validate=False)
-        self.consumed[s].record(main)                        # behind the gather: the uint8 images and the samples of the slot are free again
-        sc = (scales[:B], scales[B:]) if scales is not None else (None, None)
+        check_samples_host(self.host_smp[s], self.host_sid[s] if multi else None, self.H, self.W, self.num_scales, self.P)
+        self.upload(s, [(self.dev_img[s], self.host_img[s]), (self.dev_smp[s], self.host_smp[s])]
+                    + ([(self.dev_sid[s], self.host_sid[s])] if multi else []))
+        out = extract_patches(self.dev_img[s], self.dev_smp[s], self.dev_sid[s] if multi else None, self.num_scales, mean=self.mean,
+                              std=self.std, patch_size=self.P, validate=False)
+        self.release(s)                                      # behind the gather: the uint8 images and the samples of the slot are free again
         with torch.no_grad():
-            return self.model((patches[:B], patches[B:]), (pos[:B], pos[B:]), sc)[0]
+            return self.model(*_sides(out, B))[0]
 
     def submit(self, ref_u8, dist_u8, samples, scale_ids=None) -> torch.Tensor:
         """One batch of B pairs: ref / dist uint8 images [B, H, W, 3] (host), sampled patch coordinates int32 [B, N, 2] (shared by ref and
         dist: aligned sampling, the reference's default) or [2B, N, 2] (ref rows first), scale ids [B, N] / [2B, N] when num_scales > 1.
         Returns the batch's scores as a device tensor [B]; everything is enqueued asynchronously."""
-        B = self.B
-        img, hs, hd = self.acquire()
+        if self.host_sid is not None and scale_ids is None:
+            raise ValueError("scale_ids are required when num_scales > 1")
+        B, (img, hs, hd) = self.B, self.acquire()
         img[:B], img[B:] = self._np(ref_u8), self._np(dist_u8)
-        smp = self._np(samples)
-        if smp.shape[0] == B:
-            hs[:B], hs[B:] = smp, smp
-        else:
-            hs[:] = smp
+        hs[:B], hs[B:] = _two_sides(self._np(samples), B, "samples")
         if hd is not None:
-            if scale_ids is None:
-                raise ValueError("scale_ids are required when num_scales > 1")
-            sid = self._np(scale_ids)
-            if sid.shape[0] == B:
-                hd[:B], hd[B:] = sid, sid
-            else:
-                hd[:] = sid
+            hd[:B], hd[B:] = _two_sides(self._np(scale_ids), B, "scale_ids")
         return self.launch()
 
 
 # ---- batches whose images differ in size and patch count -----------------------------------------------------------------------------------
+class BlockLayout(NamedTuple):
+    """The word ranges of one batch in a slot's int32 block, in block order (block_layout)."""
+    tab: slice                # [NI, 4] the image table
+    patch_img: slice          # [T] the image of every patch row
+    seg: slice                # [NS, 8] the sampler's segment table, from a multiple of 4 words on; empty when the host samples
+    keys: slice               # NS uint64 keys as int32 pairs; empty when the host samples
+    samples: slice            # [T, 2]
+    ids: slice                # [T] scale ids; empty with one scale
+    uploaded: int             # the words that cross PCIe, from word 0: all of them when the host samples, up to the samples when the device does
+    words: int                # the words the batch uses
+
+    def split(self, block):
+        """(tab, patch_img, seg [NS, 8], keys, samples [T, 2], scale ids or None): views of a slot's block, host tensor or device twin."""
+        ids = block[self.ids] if self.ids.stop > self.ids.start else None
+        return (block[self.tab], block[self.patch_img], block[self.seg].view((self.seg.stop - self.seg.start) // 8, 8), block[self.keys],
+                block[self.samples].view(self.patch_img.stop - self.patch_img.start, 2), ids)
+
+
+def block_layout(n_images: int, n_patches: int, n_segments: Optional[int] = None, multi: bool = False) -> BlockLayout:
+    """THE layout of a slot's int32 block, device-free, for NI table rows and T patch rows in all.  n_segments None, the host samples:
+    tab | patch_img | samples | scale ids, all uploaded.  n_segments = NS, the device samples: tab | patch_img | (pad to 4 words) seg |
+    keys, uploaded, then samples | scale ids, which the sampler writes and which never exist on the host."""
+    a, b = 4 * n_images, 4 * n_images + n_patches
+    seg_at = b if n_segments is None else (b + 3) // 4 * 4
+    keys_at = seg_at + 8 * (n_segments or 0)
+    front = keys_at + 2 * (n_segments or 0)
+    c, d = front + 2 * n_patches, front + (3 if multi else 2) * n_patches
+    return BlockLayout(slice(0, a), slice(a, b), slice(seg_at, keys_at), slice(keys_at, front), slice(front, c), slice(c, d),
+                       d if n_segments is None else front, d)
+
+
+def block_capacity(max_images: int, max_patches: int, num_scales: int) -> int:
+    """int32 words of a slot's block: the largest layout a batch within max_images table rows, max_patches patches a side and num_scales
+    levels (one segment per image and level at most) can have, of either kind, and one 16-byte unit of slack -- with it the block is
+    never smaller than 4 max_images + 2 max_patches (4 | 3) + 10 num_scales max_images + 4, the size slots have always had."""
+    return max(block_layout(max_images, 2 * max_patches, ns, num_scales > 1).words for ns in (None, num_scales * max_images)) + 4
+
+
 class VarlenBatch(NamedTuple):
     """One batch as the varlen pipeline sees it, made on the host without a device (plan_varlen_batch)."""
     sizes: list               # NI (H, W): the first side's images, then the second side's
@@ -153,7 +261,7 @@ def plan_varlen_batch(sizes_first, sizes_second, lengths_first, lengths_second, 
     for i, (h, w) in enumerate(sizes):
         if h < P or w < P:
             raise ValueError(f"image {i} ({h}x{w}) is smaller than one {P}x{P} patch")
-    return VarlenBatch(sizes, lengths, len(sizes_first), tables, 4 * len(sizes) + tables.total * (4 if num_scales > 1 else 3))
+    return VarlenBatch(sizes, lengths, len(sizes_first), tables, block_layout(len(sizes), tables.total, None, num_scales > 1).words)
 
 
 def pair_arguments(refs, dists, samples, lengths=None, scale_ids=None, num_scales: int = 1):
@@ -161,37 +269,21 @@ def pair_arguments(refs, dists, samples, lengths=None, scale_ids=None, num_scale
     sampling, one list per pair shared by its two images, which must then have ONE size -- or 2B arrays (references first) for unaligned
     sampling with N_b patches on both sides of pair b; lengths: None or the B counts, which must then match; scale_ids like samples.
     Returns (refs, dists, per-image samples [2B], per-image scale ids [2B] or None, lengths [B]) as numpy arrays."""
-    refs, dists = [np.asarray(r) for r in refs], [np.asarray(d) for d in dists]
+    refs, dists = _host_images(refs, dists, pairs=True)
     B = len(refs)
-    if B < 1 or len(dists) != B:
-        raise ValueError("refs and dists: B >= 1 images each")
-    for im in refs + dists:
-        if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
-            raise ValueError("images must be uint8 [H, W, 3]")
-    smp = [np.asarray(s) for s in samples]
-    if len(smp) not in (B, 2 * B) or any(s.ndim != 2 or s.shape[1] != 2 or s.shape[0] < 1 or s.dtype.kind not in "iu" for s in smp):
-        raise ValueError("samples: B (aligned) or 2B (references first) integer arrays (N_b, 2), N_b >= 1")
-    aligned = len(smp) == B
-    if aligned:
-        for b in range(B):
-            if refs[b].shape != dists[b].shape:
-                raise ValueError(f"aligned sampling: the two images of pair {b} differ in size ({refs[b].shape[:2]} and {dists[b].shape[:2]}); "
-                                 "pass 2B sample arrays for unaligned sampling")
-        smp = smp + smp
+    first, second = _two_sides(list(samples), B, "samples")
+    if first is second:
+        _aligned_sizes(refs, dists)
+    ids = None
+    if scale_ids is not None and num_scales > 1:
+        ids_first, ids_second = _two_sides(list(scale_ids), B, "scale_ids")
+        ids = ids_first + ids_second
+    smp, sid = _sample_lists(first + second, ids, num_scales)
     lens = [s.shape[0] for s in smp[:B]]
     if [s.shape[0] for s in smp[B:]] != lens:
         raise ValueError("the two images of a pair need the same patch count")
     if lengths is not None and [int(n) for n in lengths] != lens:
         raise ValueError("lengths do not match the sample arrays")
-    sid = None
-    if num_scales > 1:
-        if scale_ids is None:
-            raise ValueError("scale_ids are required when num_scales > 1")
-        sid = [np.asarray(s) for s in scale_ids]
-        if len(sid) == B:
-            sid = sid + sid
-        if len(sid) != 2 * B or any(i.shape != (s.shape[0],) for i, s in zip(sid, smp)):
-            raise ValueError("scale_ids: one array (N_b,) per sample array")
     return refs, dists, smp, sid, lens
 
 
@@ -235,14 +327,13 @@ def plan_sampled_batch(sizes_first, sizes_second, counts_first, counts_second, k
     row0 = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int32)
     tables = ImageTables(t.img_off[rows], t.H[rows], t.W[rows], row0, np.ascontiguousarray(t.tab[rows]),
                          np.repeat(np.arange(len(rows), dtype=np.int32), lengths), t.image_bytes, int(row0[-1]))
-    NI, T, NS = len(rows), tables.total, len(plan.seg)
-    seg_at = (4 * NI + T + 3) // 4 * 4
-    front = seg_at + 10 * NS
-    batch = VarlenBatch(sizes, lengths, R * nf, tables, front + T * (3 if num_scales > 1 else 2))
-    return SampledBatch(batch, np.ascontiguousarray(plan.seg), np.ascontiguousarray(keys[plan.seg_image]), nf + ns_, R, front, seg_at)
+    layout = block_layout(len(rows), tables.total, len(plan.seg), num_scales > 1)
+    batch = VarlenBatch(sizes, lengths, R * nf, tables, layout.words)
+    return SampledBatch(batch, np.ascontiguousarray(plan.seg), np.ascontiguousarray(keys[plan.seg_image]), nf + ns_, R, layout.uploaded,
+                        layout.seg.start)
 
 
-class ImagePairVarlenPipeline:
+class ImagePairVarlenPipeline(_SlotRing):
     """ImagePairPipeline for batches whose images differ in size and patch count: host uint8 images in, scores out, through ONE gather over
     all images of the batch (patches.extract_patches_varlen's kernel) and forward_varlen -- or, one reference against many distorted images,
     forward_group(lengths=).  Slots are sized by capacity, not by shape:
@@ -260,89 +351,95 @@ class ImagePairVarlenPipeline:
     def __init__(self, model, max_pairs: int, max_image_bytes: int, max_patches: int, num_scales: int = 1,
                  device: Optional[torch.device] = None, depth: int = 2, mean: Sequence[float] = (0.5, 0.5, 0.5),
                  std: Sequence[float] = (0.5, 0.5, 0.5)):
-        if depth < 2:
-            raise ValueError("depth >= 2 (one buffer set is being filled while another is consumed)")
         if max_pairs < 1 or max_image_bytes < 1 or max_patches < 1:
             raise ValueError("max_pairs, max_image_bytes and max_patches must be positive")
+        super().__init__(device, depth)
         self.model = model
         self.max_images, self.max_image_bytes, self.max_patches = 2 * int(max_pairs), int(max_image_bytes), int(max_patches)
         self.num_scales, self.P = int(num_scales), model.spec.patch_size
         self.mean, self.std = tuple(mean), tuple(std)
-        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        if self.device.type != "cuda":
-            raise RuntimeError("ImagePairVarlenPipeline runs on the GPU only (no CPU fallback on the product path)")
-        words = 4 * self.max_images + 2 * self.max_patches * (4 if self.num_scales > 1 else 3)
-        # behind what submit() / submit_group() use: room for the sampler's segment table and keys (submit_images: 10 words per
-        # (image, level), 3 of alignment)
-        words += 10 * self.num_scales * self.max_images + 4
-        self.depth = depth
+        self._caps = dict(max_images=self.max_images, max_image_bytes=self.max_image_bytes, max_patches=self.max_patches,
+                          num_scales=self.num_scales, patch_size=self.P)
+        words = block_capacity(self.max_images, self.max_patches, self.num_scales)
         self.host_img = [torch.empty(self.max_image_bytes, dtype=torch.uint8).pin_memory() for _ in range(depth)]
         self.host_tab = [torch.zeros(words, dtype=torch.int32).pin_memory() for _ in range(depth)]
         self.dev_img = [torch.empty(self.max_image_bytes, dtype=torch.uint8, device=self.device) for _ in range(depth)]
         self.dev_tab = [torch.empty(words, dtype=torch.int32, device=self.device) for _ in range(depth)]
-        self.copy_stream = torch.cuda.Stream(device=self.device)
-        self.copied = [torch.cuda.Event() for _ in range(depth)]
-        self.consumed = [torch.cuda.Event() for _ in range(depth)]
-        main = torch.cuda.current_stream(self.device)
-        for ev in self.consumed:
-            ev.record(main)
-        self.count = 0
         self._batch = None
 
     def plan(self, sizes_first, sizes_second, lengths_first, lengths_second) -> VarlenBatch:
-        return plan_varlen_batch(sizes_first, sizes_second, lengths_first, lengths_second, max_images=self.max_images,
-                                 max_image_bytes=self.max_image_bytes, max_patches=self.max_patches, num_scales=self.num_scales,
-                                 patch_size=self.P)
+        return plan_varlen_batch(sizes_first, sizes_second, lengths_first, lengths_second, **self._caps)
 
-    @staticmethod
-    def _split(block, batch: VarlenBatch, multi: bool):
-        """tab | patch_img | samples | scale ids of a slot's int32 block (host tensor or its device twin), packed for this batch."""
-        NI, T = len(batch.sizes), batch.tables.total
-        a, b, c = 4 * NI, 4 * NI + T, 4 * NI + 3 * T
-        return block[:a], block[a:b], block[b:c].view(T, 2), (block[c:c + T] if multi else None)
+    # ---- one path for every entry: stage the slot's host side, upload it and gather, end as pairs or as a group -----------------------
+    def _layout(self, planned):
+        """(the VarlenBatch, its block_layout) of a planned batch, VarlenBatch or SampledBatch."""
+        batch, ns = (planned.batch, len(planned.seg)) if isinstance(planned, SampledBatch) else (planned, None)
+        return batch, block_layout(len(batch.sizes), batch.tables.total, ns, self.num_scales > 1)
+
+    def _stage(self, planned):
+        """The one place a slot's host side is written: wait for the next slot, write the batch's tables (a SampledBatch's segment table
+        and keys with them) into its pinned block, and return numpy views of what the caller fills -- the images that cross PCIe in the
+        pinned arena, uint8 [H_i, W_i, 3] each, the samples int32 (total, 2) and the scale ids int32 (total,) or None."""
+        s = self.free_slot()
+        sb = planned if isinstance(planned, SampledBatch) else None
+        batch, layout = self._layout(planned)
+        t = batch.tables
+        tab, pimg, seg, keys, smp, sid = layout.split(self.host_tab[s])
+        tab.numpy()[:] = t.tab.reshape(-1)
+        pimg.numpy()[:] = t.patch_img
+        rows = range(len(batch.sizes))
+        if sb is not None:
+            seg.numpy()[:] = sb.seg
+            keys.numpy()[:] = sb.seg_keys.view(np.int32)
+            nf = batch.n_first // sb.repeats                 # the table rows of repeat 0 of each side: the images that are copied
+            rows = list(range(nf)) + list(range(batch.n_first, batch.n_first + sb.n_images - nf))
+        arena, off = self.host_img[s].numpy(), t.img_off.tolist()
+        views = [arena[off[i]:off[i] + 3 * h * w].reshape(h, w, 3) for i in rows for h, w in [batch.sizes[i]]]
+        return views, smp.numpy(), (sid.numpy() if sid is not None else None)
+
+    def _upload_and_gather(self, planned, behind=None):
+        """The one place a staged slot is enqueued: two H2D copies on the copy stream (the arena's used bytes, the block's uploaded
+        words) and behind them `behind(seg, keys, samples, scale_ids)` on the slot's device block, then on the current stream the gather,
+        with `consumed` directly behind it.  Returns the gather's (patches, pos, scales)."""
+        s, (batch, layout) = self.count % self.depth, self._layout(planned)
+        t = batch.tables
+        dtab, dpimg, dseg, dkeys, dsmp, dsid = layout.split(self.dev_tab[s])
+        self._batch = None
+        self.upload(s, [(self.dev_img[s][:t.image_bytes], self.host_img[s][:t.image_bytes]),
+                        (self.dev_tab[s][:layout.uploaded], self.host_tab[s][:layout.uploaded])],
+                    (lambda: behind(dseg, dkeys, dsmp, dsid)) if behind is not None else None)
+        out = gather_patches_u8(self.dev_img[s][:t.image_bytes], t, dtab, dpimg, dsmp, dsid, None, self.num_scales, self.mean, self.std, self.P)
+        self.release(s)                                      # behind the gather: the slot's images, tables and samples are free again
+        return out
+
+    def _as_pairs(self, batch: VarlenBatch, out) -> torch.Tensor:
+        first = batch.lengths[:batch.n_first]
+        with torch.no_grad():
+            return self.model.forward_varlen(*_sides(out, int(first.sum())), first.tolist())[0]
+
+    def _as_group(self, batch: VarlenBatch, out, index) -> torch.Tensor:
+        L, G = batch.lengths, batch.n_first
+        with torch.no_grad():
+            return self.model.forward_group(*_sides(out, int(L[:G].sum())), index, lengths=(L[:G].tolist(), L[G:].tolist()))[0]
 
     def acquire(self, batch: VarlenBatch):
         """The next slot's PINNED host buffers for `batch` (plan()) as numpy views, once the batch that used the slot `depth` submissions
         ago no longer reads it: a list of the NI images uint8 [H_i, W_i, 3] (first side first), samples int32 (total, 2) and scale ids
         int32 (total,) or None, both concatenated in image order.  The tables are written here.  Follow with launch() or launch_group()."""
-        s = self.count % self.depth
-        self.consumed[s].synchronize()
-        t = batch.tables
-        tab, pimg, smp, sid = self._split(self.host_tab[s], batch, self.num_scales > 1)
-        tab.numpy()[:] = t.tab.reshape(-1)
-        pimg.numpy()[:] = t.patch_img
-        arena = self.host_img[s].numpy()
-        views = [arena[o:o + 3 * h * w].reshape(h, w, 3) for o, (h, w) in zip(t.img_off.tolist(), batch.sizes)]
+        pinned = self._stage(batch)
         self._batch = batch
-        return views, smp.numpy(), (sid.numpy() if sid is not None else None)
+        return pinned
 
-    def _gather(self, validate: bool):
-        batch, s = self._batch, self.count % self.depth
+    def _launch(self, validate: bool):
+        batch = self._batch
         if batch is None:
             raise RuntimeError("launch() without acquire()")
-        t, multi = batch.tables, self.num_scales > 1
-        htab, hpimg, hsmp, hsid = self._split(self.host_tab[s], batch, multi)
         if validate:
             # the range check the reference gets from numpy fancy-indexing, on the host copy: before anything is enqueued
-            check_samples_host_varlen(hsmp.numpy(), hsid.numpy() if multi else None, batch.sizes, batch.lengths, self.num_scales, self.P)
-        self._batch = None
-        self.count += 1
-        main = torch.cuda.current_stream(self.device)
-        with torch.cuda.stream(self.copy_stream):
-            self.copy_stream.wait_event(self.consumed[s])    # the slot's device buffers were read by batch i - depth
-            self.dev_img[s][:t.image_bytes].copy_(self.host_img[s][:t.image_bytes], non_blocking=True)
-            self.dev_tab[s][:batch.words].copy_(self.host_tab[s][:batch.words], non_blocking=True)
-            self.copied[s].record(self.copy_stream)
-        main.wait_event(self.copied[s])
-        dtab, dpimg, dsmp, dsid = self._split(self.dev_tab[s], batch, multi)
-        out = gather_patches_u8(self.dev_img[s][:t.image_bytes], t, dtab, dpimg, dsmp, dsid, None, self.num_scales, self.mean, self.std, self.P)
-        self.consumed[s].record(main)                        # behind the gather: the slot's images, tables and samples are free again
-        return batch, out
-
-    @staticmethod
-    def _sides(out, k):
-        patches, pos, scales = out
-        return (patches[:k], patches[k:]), (pos[:k], pos[k:]), ((scales[:k], scales[k:]) if scales is not None else (None, None))
+            *_, smp, sid = self._layout(batch)[1].split(self.host_tab[self.count % self.depth])
+            check_samples_host_varlen(smp.numpy(), sid.numpy() if sid is not None else None, batch.sizes, batch.lengths, self.num_scales,
+                                      self.P)
+        return batch, self._upload_and_gather(batch)
 
     def launch(self, validate: bool = True) -> torch.Tensor:
         """Enqueue the slot filled through acquire() as B pairs (image b of the first side with image b of the second, equal patch counts):
@@ -350,34 +447,25 @@ class ImagePairVarlenPipeline:
         b = self._batch
         if b is not None and (2 * b.n_first != len(b.sizes) or not np.array_equal(b.lengths[:b.n_first], b.lengths[b.n_first:])):
             raise ValueError("pairs need as many second-side images as first-side ones, with the same patch counts")
-        batch, out = self._gather(validate)
-        k = int(batch.lengths[:batch.n_first].sum())
-        with torch.no_grad():
-            return self.model.forward_varlen(*self._sides(out, k), batch.lengths[:batch.n_first].tolist())[0]
+        return self._as_pairs(*self._launch(validate))
 
     def launch_group(self, ref_index, validate: bool = True) -> torch.Tensor:
         """Enqueue the slot filled through acquire() as G references (first side) and M distorted images (second side) with
         ref_index[m] in [0, G): ends in forward_group(..., ref_index, lengths=(lengths_ref, lengths_dist)).  Returns q (M,)."""
         b = self._batch
-        idx = [int(i) for i in ref_index]
-        if b is not None and (len(idx) != len(b.sizes) - b.n_first or any(not 0 <= i < b.n_first for i in idx)):
-            raise ValueError("ref_index: one reference in [0, G) per distorted image")
-        batch, out = self._gather(validate)
-        G = batch.n_first
-        k = int(batch.lengths[:G].sum())
-        with torch.no_grad():
-            return self.model.forward_group(*self._sides(out, k), idx, lengths=(batch.lengths[:G].tolist(), batch.lengths[G:].tolist()))[0]
+        idx = _ref_indices(ref_index, b.n_first, len(b.sizes) - b.n_first) if b is not None else None
+        return self._as_group(*self._launch(validate), idx)
 
     def _fill(self, batch, images, smp, sid):
+        smp, sid = np.concatenate(smp), (np.concatenate(sid) if sid is not None else None)
         # checked on the caller's arrays, so that a refused batch leaves the slot and the streams alone
-        check_samples_host_varlen(np.concatenate(smp), np.concatenate(sid) if sid is not None else None, batch.sizes, batch.lengths,
-                                  self.num_scales, self.P)
+        check_samples_host_varlen(smp, sid, batch.sizes, batch.lengths, self.num_scales, self.P)
         views, hs, hd = self.acquire(batch)
         for v, im in zip(views, images):
             v[...] = im
-        hs[:] = np.concatenate(smp)
+        hs[:] = smp
         if hd is not None:
-            hd[:] = np.concatenate(sid)
+            hd[:] = sid
 
     def submit(self, refs, dists, samples, lengths=None, scale_ids=None) -> torch.Tensor:
         """One batch of B pairs of any sizes: refs / dists lists of B host images uint8 [H, W, 3]; samples B arrays (N_b, 2) shared by a
@@ -393,102 +481,37 @@ class ImagePairVarlenPipeline:
         """G reference images and M distorted ones of any sizes and patch counts, distorted image m scored against reference ref_index[m]:
         every reference crosses PCIe once and is encoded once.  samples_ref: G arrays (N_g, 2), samples_dist: M arrays (N_m, 2); scale ids
         likewise when num_scales > 1.  Returns q (M,) on the device."""
-        refs, dists = [np.asarray(r) for r in refs], [np.asarray(d) for d in dists]
-        smp = [np.asarray(s) for s in list(samples_ref) + list(samples_dist)]
-        if len(samples_ref) != len(refs) or len(samples_dist) != len(dists):
-            raise ValueError("one sample array per image")
-        if any(im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3 for im in refs + dists):
-            raise ValueError("images must be uint8 [H, W, 3]")
-        if any(s.ndim != 2 or s.shape[1] != 2 or s.dtype.kind not in "iu" for s in smp):
-            raise ValueError("samples: integer arrays (N, 2)")
-        sid = None
-        if self.num_scales > 1:
-            if scale_ids_ref is None or scale_ids_dist is None:
-                raise ValueError("scale_ids are required when num_scales > 1")
-            sid = [np.asarray(s) for s in list(scale_ids_ref) + list(scale_ids_dist)]
-            if len(sid) != len(smp) or any(i.shape != (s.shape[0],) for i, s in zip(sid, smp)):
-                raise ValueError("scale_ids: one array (N,) per sample array")
+        refs, dists = _host_images(refs, dists)
         G = len(refs)
+        if len(samples_ref) != G or len(samples_dist) != len(dists):
+            raise ValueError("one sample array per image")
+        ids = None if scale_ids_ref is None or scale_ids_dist is None else list(scale_ids_ref) + list(scale_ids_dist)
+        smp, sid = _sample_lists(list(samples_ref) + list(samples_dist), ids, self.num_scales)
         batch = self.plan([r.shape[:2] for r in refs], [d.shape[:2] for d in dists], [s.shape[0] for s in smp[:G]], [s.shape[0] for s in smp[G:]])
-        idx = [int(i) for i in ref_index]
-        if len(idx) != len(dists) or any(not 0 <= i < G for i in idx):
-            raise ValueError("ref_index: one reference in [0, G) per distorted image")
+        idx = _ref_indices(ref_index, G, len(dists))
         self._fill(batch, refs + dists, smp, sid)
         return self.launch_group(idx, validate=False)
 
     # ---- coordinates sampled on the device (sampling.py, include/vtamiq_hip_sampler.h) ----------------------------------------------
     def plan_sampled(self, sizes_first, sizes_second, counts_first, counts_second, keys_first, keys_second, repeats: int = 1,
                      scale_num_samples_ratio: float = DEFAULT_NUM_SAMPLES_RATIO) -> SampledBatch:
-        return plan_sampled_batch(sizes_first, sizes_second, counts_first, counts_second, keys_first, keys_second, max_images=self.max_images,
-                                  max_image_bytes=self.max_image_bytes, max_patches=self.max_patches, repeats=repeats,
-                                  num_scales=self.num_scales, scale_num_samples_ratio=scale_num_samples_ratio, patch_size=self.P)
+        return plan_sampled_batch(sizes_first, sizes_second, counts_first, counts_second, keys_first, keys_second, repeats=repeats,
+                                  scale_num_samples_ratio=scale_num_samples_ratio, **self._caps)
 
     def _default_keys(self, n: int) -> list:
         """keys=None: image / pair b of this pipeline's i-th submission gets (i << 32) | b."""
         return [(self.count << 32) | b for b in range(n)]
 
-    @staticmethod
-    def _host_images(refs, dists):
-        refs, dists = [np.asarray(r) for r in refs], [np.asarray(d) for d in dists]
-        if len(refs) < 1 or len(dists) < 1:
-            raise ValueError("refs and dists: at least one image each")
-        if any(im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3 for im in refs + dists):
-            raise ValueError("images must be uint8 [H, W, 3]")
-        return refs, dists
-
-    @staticmethod
-    def _counts(patch_count, n: int) -> list:
-        counts = [int(patch_count)] * n if np.ndim(patch_count) == 0 else [int(c) for c in patch_count]
-        if len(counts) != n:
-            raise ValueError("patch_count: one int, or one per pair / image")
-        return counts
-
-    def _split_sampled(self, block, sb: SampledBatch):
-        """tab | patch_img | seg | keys (int32 pairs) | samples | scale ids of a slot's int32 block for a sampled batch."""
-        NI, T, NS = len(sb.batch.sizes), sb.batch.tables.total, len(sb.seg)
-        k, s = sb.seg_at + 8 * NS, sb.front
-        return (block[:4 * NI], block[4 * NI:4 * NI + T], block[sb.seg_at:k].view(NS, 8), block[k:s], block[s:s + 2 * T].view(T, 2),
-                (block[s + 2 * T:s + 3 * T] if self.num_scales > 1 else None))
-
     def _sample_and_gather(self, sb: SampledBatch, images, seed: int, sampler: Optional[PatchSampler]):
-        """Fill the next slot with the batch's images and tables, upload them (two copies on the copy stream) and, behind them on the copy
-        stream, launch the sampler into the slot's device block; on the current stream the gather that reads it.  The coordinates never
-        exist on the host."""
+        """Stage the batch's images and tables and, as the upload's step on the copy stream, launch the sampler into the slot's device
+        block: behind the tables it reads and under the forward of the batch before, not in front of this batch's gather on the current
+        stream (the slot's samples were last read by batch i - depth: `consumed`).  The coordinates never exist on the host."""
         sampler = sampler if sampler is not None else PatchSampler()
-        s = self.count % self.depth
-        self.consumed[s].synchronize()
-        t = sb.batch.tables
-        tab, pimg, seg, keys, _, _ = self._split_sampled(self.host_tab[s], sb)
-        tab.numpy()[:] = t.tab.reshape(-1)
-        pimg.numpy()[:] = t.patch_img
-        seg.numpy()[:] = sb.seg
-        keys.numpy()[:] = sb.seg_keys.view(np.int32)
-        arena = self.host_img[s].numpy()
-        for o, im in zip(self._base_offsets(sb), images):
-            arena[o:o + im.size].reshape(im.shape)[...] = im
-        self._batch = None
-        self.count += 1
-        main = torch.cuda.current_stream(self.device)
-        dtab, dpimg, dseg, dkeys, dsmp, dsid = self._split_sampled(self.dev_tab[s], sb)
-        with torch.cuda.stream(self.copy_stream):
-            self.copy_stream.wait_event(self.consumed[s])
-            self.dev_img[s][:t.image_bytes].copy_(self.host_img[s][:t.image_bytes], non_blocking=True)
-            self.dev_tab[s][:sb.front].copy_(self.host_tab[s][:sb.front], non_blocking=True)
-            # the sampler runs on the copy stream, behind the tables it reads: under the forward of the batch before, not in front of
-            # this batch's gather on the current stream (the slot's samples were last read by batch i - depth: `consumed`)
-            launch_sample_grid(dseg, dkeys, sb.seg, sb.seg_keys, seed, sampler.amount_q, dsmp, dsid)
-            self.copied[s].record(self.copy_stream)
-        main.wait_event(self.copied[s])
-        out = gather_patches_u8(self.dev_img[s][:t.image_bytes], t, dtab, dpimg, dsmp, dsid, None, self.num_scales, self.mean, self.std, self.P)
-        self.consumed[s].record(main)
-        return out
-
-    @staticmethod
-    def _base_offsets(sb: SampledBatch) -> list:
-        """Byte offsets of the NI images that are copied: the table rows of repeat 0 of each side."""
-        nf = sb.batch.n_first // sb.repeats
-        off = sb.batch.tables.img_off
-        return off[:nf].tolist() + off[sb.batch.n_first:sb.batch.n_first + sb.n_images - nf].tolist()
+        views, _, _ = self._stage(sb)
+        for v, im in zip(views, images):
+            v[...] = im
+        return self._upload_and_gather(sb, lambda seg, keys, smp, sid: launch_sample_grid(seg, keys, sb.seg, sb.seg_keys, seed,
+                                                                                          sampler.amount_q, smp, sid))
 
     def _mean_over_repeats(self, q: torch.Tensor, repeats: int) -> torch.Tensor:
         if repeats == 1:
@@ -505,27 +528,19 @@ class ImagePairVarlenPipeline:
         validation repeats: every pair is scored R times with the keys sampling.repeat_key(key, r) -- the images cross PCIe once -- and
         the R scores are averaged on the device (validate.average_over_repeats): fp64 (B,) then, else q (B,) as submit() returns it.
         ValueError for a batch over the slot capacity (repeats count against max_pairs and max_patches), before anything is enqueued."""
-        refs, dists = self._host_images(refs, dists)
+        refs, dists = _host_images(refs, dists, pairs=True)
         B = len(refs)
-        if len(dists) != B:
-            raise ValueError("refs and dists: B >= 1 images each")
         if aligned:
-            for b in range(B):
-                if refs[b].shape != dists[b].shape:
-                    raise ValueError(f"aligned sampling: the two images of pair {b} differ in size ({refs[b].shape[:2]} and "
-                                     f"{dists[b].shape[:2]}); pass aligned=False for unaligned sampling")
+            _aligned_sizes(refs, dists)
             kr = kd = as_keys(self._default_keys(B) if keys is None else keys, B)
         else:
             k2 = as_keys(keys, 2 * B) if keys is not None else as_keys([k ^ (s << 63) for s in (0, 1) for k in self._default_keys(B)], 2 * B)
             kr, kd = k2[:B], k2[B:]
-        counts = self._counts(patch_count, B)
+        counts = patch_counts(patch_count, B)
         sb = self.plan_sampled([r.shape[:2] for r in refs], [d.shape[:2] for d in dists], counts, counts, kr, kd, num_repeats,
                                scale_num_samples_ratio)
         out = self._sample_and_gather(sb, refs + dists, seed, sampler)
-        first = sb.batch.lengths[:sb.batch.n_first]
-        with torch.no_grad():
-            q = self.model.forward_varlen(*self._sides(out, int(first.sum())), first.tolist())[0]
-        return self._mean_over_repeats(q, sb.repeats)
+        return self._mean_over_repeats(self._as_pairs(sb.batch, out), sb.repeats)
 
     def submit_group_images(self, refs, dists, ref_index, patch_count, keys=None, seed: int = 0, num_repeats: int = 1,
                             sampler: Optional[PatchSampler] = None, scale_num_samples_ratio: float = DEFAULT_NUM_SAMPLES_RATIO,
@@ -534,21 +549,15 @@ class ImagePairVarlenPipeline:
         ref_index[m].  patch_count: one int or G (references); patch_count_dist: one int or M (default: patch_count, which must then be
         one int).  keys: G + M keys, references first (None: from the submission counter); a distorted image with its reference's key and
         size gets its reference's coordinates.  num_repeats as submit_images.  Returns q (M,), fp64 when num_repeats > 1."""
-        refs, dists = self._host_images(refs, dists)
+        refs, dists = _host_images(refs, dists)
         G, M = len(refs), len(dists)
-        idx = [int(i) for i in ref_index]
-        if len(idx) != M or any(not 0 <= i < G for i in idx):
-            raise ValueError("ref_index: one reference in [0, G) per distorted image")
+        idx = _ref_indices(ref_index, G, M)
         if patch_count_dist is None:
             if np.ndim(patch_count) != 0:
                 raise ValueError("patch_count per reference needs patch_count_dist for the distorted images")
             patch_count_dist = patch_count
         k = as_keys(self._default_keys(G + M) if keys is None else keys, G + M)
-        sb = self.plan_sampled([r.shape[:2] for r in refs], [d.shape[:2] for d in dists], self._counts(patch_count, G),
-                               self._counts(patch_count_dist, M), k[:G], k[G:], num_repeats, scale_num_samples_ratio)
+        sb = self.plan_sampled([r.shape[:2] for r in refs], [d.shape[:2] for d in dists], patch_counts(patch_count, G),
+                               patch_counts(patch_count_dist, M), k[:G], k[G:], num_repeats, scale_num_samples_ratio)
         out = self._sample_and_gather(sb, refs + dists, seed, sampler)
-        R, L, nf = sb.repeats, sb.batch.lengths, sb.batch.n_first
-        index = [i + r * G for r in range(R) for i in idx]
-        with torch.no_grad():
-            q = self.model.forward_group(*self._sides(out, int(L[:nf].sum())), index, lengths=(L[:nf].tolist(), L[nf:].tolist()))[0]
-        return self._mean_over_repeats(q, R)
+        return self._mean_over_repeats(self._as_group(sb.batch, out, [i + r * G for r in range(sb.repeats) for i in idx]), sb.repeats)

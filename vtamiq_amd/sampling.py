@@ -104,6 +104,14 @@ class SamplePlan(NamedTuple):
     total: int
 
 
+def patch_counts(patch_count, n: int) -> list:
+    """patch_count as n ints: one int for all n images (or pairs), or n of them."""
+    counts = [int(patch_count)] * n if np.ndim(patch_count) == 0 else [int(c) for c in patch_count]
+    if len(counts) != n:
+        raise ValueError(f"patch_count: one int, or one per pair / image ({n})")
+    return counts
+
+
 def plan_samples(sizes, patch_count, num_scales: int = 1, scale_num_samples_ratio: float = DEFAULT_NUM_SAMPLES_RATIO,
                  patch_size: int = 16) -> SamplePlan:
     """Host side of the sampler, numpy only.  sizes: NI (H, W); patch_count: one int for all images or NI ints.  Image i gets the
@@ -116,9 +124,7 @@ def plan_samples(sizes, patch_count, num_scales: int = 1, scale_num_samples_rati
     sizes = [(int(h), int(w)) for h, w in sizes]
     if not sizes:
         raise ValueError("sizes: at least one (H, W)")
-    counts = [int(patch_count)] * len(sizes) if np.ndim(patch_count) == 0 else [int(c) for c in patch_count]
-    if len(counts) != len(sizes):
-        raise ValueError("patch_count: one int, or one per image")
+    counts = patch_counts(patch_count, len(sizes))
     rows, seg_image, levels, first = [], [], [], 0
     for i, ((h, w), count) in enumerate(zip(sizes, counts)):
         if h < P or w < P:
