@@ -447,6 +447,15 @@ def test_sources_have_no_build_switch_but_fp8():
                     assert names <= {"VTQ_WITH_FP8"}, (f, line.strip())
 
 
+def test_dynamic_lds_opt_in_is_stated_once():
+    """The per-device dynamic-LDS opt-in of the launchers lives in csrc/launch_common.h (ensure_dynamic_lds) and nowhere else: one
+    file of csrc/ names hipFuncSetAttribute, and no source keeps a per-device flag array of its own."""
+    csrc = os.path.join(ROOT, "vtamiq_amd", "csrc")
+    sources = {f: open(os.path.join(csrc, f)).read() for f in os.listdir(csrc) if f.endswith((".hip", ".h"))}
+    assert [f for f, text in sorted(sources.items()) if "hipFuncSetAttribute" in text] == ["launch_common.h"]
+    assert [f for f, text in sorted(sources.items()) if "static bool configured[" in text] == []
+
+
 def test_weight_signature_sees_replacement_and_new_storage():
     """`p.data = new_tensor`, load_state_dict(assign=True) and module replacement must all change the signature the
     engine's packed weights are keyed by (CPU-only: the signature is host logic)."""

@@ -19,80 +19,13 @@
 #include <atomic>
 #include <mutex>
 
+#include "attention_common.h"
 #include "dev_common.h"
 #include "kernels.h"
+#include "launch_common.h"
 
 namespace vtq {
 namespace {
-
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(8))) short s16x8;
-__device__ __forceinline__ s16x4 lds_tr16(const char* p) {
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)p);
-}
-
-// Split 8 probabilities into the hi / lo MFMA fragments (element j of the fragment = p[j]).
-template <typename T>
-__device__ __forceinline__ void split_p8(const float (&p)[8], typename Vec<T>::x8& hi, typename Vec<T>::x8& lo) {
-    if constexpr (std::is_same<T, f16>::value) {
-        typedef __attribute__((ext_vector_type(2))) _Float16 h2;
-        uint32_t hw[4], lw[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const auto hp = __builtin_amdgcn_cvt_pkrtz(p[2 * j], p[2 * j + 1]);      // truncation: hi <= p, p - hi exact in fp32
-            const h2 hh = __builtin_bit_cast(h2, hp);
-            hw[j] = __builtin_bit_cast(uint32_t, hp);
-            // plain C++ (v_cvt_f32_f16 + v_sub): an inline-asm v_fma_mix here read v_exp results inside the hardware's
-            // trans -> VALU forwarding window, which hipcc does not pad for asm operands: rare wrong lo halves (measured)
-            lw[j] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(p[2 * j] - (float)hh[0], p[2 * j + 1] - (float)hh[1]));
-        }
-        typedef __attribute__((ext_vector_type(4))) uint32_t u4;
-        hi = __builtin_bit_cast(f16x8, u4{hw[0], hw[1], hw[2], hw[3]});
-        lo = __builtin_bit_cast(f16x8, u4{lw[0], lw[1], lw[2], lw[3]});
-    } else {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const uint32_t hb = __builtin_bit_cast(uint32_t, p[j]) & 0xFFFF0000u;     // bf16 by truncation
-            const float hf = __builtin_bit_cast(float, hb);
-            hi[j] = __builtin_bit_cast(bf16, (unsigned short)(hb >> 16));
-            lo[j] = (bf16)(p[j] - hf);
-        }
-    }
-}
-
-// Two scores at a time: the exponent's argument and the row sum as packed fp32 operations (v_pk_add_f32 / v_pk_fma_f32: two lanes'
-// worth of work per vector issue slot; the exponential itself has no packed form).  The row sum therefore runs as TWO partial sums
-// (even / odd accumulator registers), added at the end of a tile -- both kernels use this helper, so they stay bit-identical.
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-template <int NSPLIT>
-__device__ __forceinline__ void exp_pair(f32x16& v, int r, float m_new, float sc, float nm, f32x2& rs2) {      // registers r, r + 1 of v
-    f32x2 t = {v[r], v[r + 1]};
-    if constexpr (NSPLIT == 3) t = t - f32x2{m_new, m_new};
-    else t = t * f32x2{sc, sc} + f32x2{nm, nm};
-    f32x2 pv = {__builtin_amdgcn_exp2f(t[0]), __builtin_amdgcn_exp2f(t[1])};
-    v[r] = pv[0];
-    v[r + 1] = pv[1];
-    rs2 += pv;
-}
-
-// 3-term formats: the softmax scale (1/sqrt(64) * log2 e) is folded into Q once per query block -- q c = (hi + lo) c in fp32, split
-// again -- so that scores arrive in log2 units and the exponent is exp2(s - m): one subtraction that is EXACT for the row maximum at
-// any magnitude.  (The one-FMA form exp2(s c - m c) subtracts the rounded product m c: fine at ordinary logits, inf at the 1e13
-// logits of a 1e7-gain model, where the fp32 reference is finite; the single-plane formats keep it behind a magnitude guard, since
-// re-rounding q c to 11 bits would cost them accuracy.)
-template <typename T>
-__device__ __forceinline__ void prescale_q(typename Vec<T>::x8 (&qf)[2][4], float sc) {
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const float v = ((float)qf[0][t][j] + (float)qf[1][t][j]) * sc;
-            T a, b;
-            split2<T>(v, a, b);
-            qf[0][t][j] = a;
-            qf[1][t][j] = b;
-        }
-}
 
 template <typename T, int NSPLIT>
 __global__ __launch_bounds__(256) void attention_kernel(const T* __restrict__ qkv, int64_t plane, T* __restrict__ out,
@@ -1056,20 +989,8 @@ template <typename T, int NSPLIT>
 hipError_t launch_attention_t(const void* qkv, int64_t plane, void* out, int64_t o_plane, int nseq, int S, int S_pad, int H, hipStream_t s,
                               float out8_scale, Fp8Obs obs, bool q_log2, int q0 = 0) {
     constexpr int LDS = 2 * 2 * 64 * 128 * (NSPLIT == 1 ? 1 : 2);
-    static std::mutex mu;
-    static bool configured[64] = {false};          // hipFuncSetAttribute is per device
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
+    const hipError_t e = ensure_dynamic_lds<attention_kernel<T, NSPLIT>>(LDS);
     if (e != hipSuccess) return e;
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-        if (!configured[dev]) {
-            e = hipFuncSetAttribute((const void*)attention_kernel<T, NSPLIT>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-            if (e != hipSuccess) return e;
-            configured[dev] = true;
-        }
-    }
     const dim3 grid(((S_pad - q0 + 127) / 128) * (H / 64) * nseq), blk(256);
     hipLaunchKernelGGL((attention_kernel<T, NSPLIT>), grid, blk, LDS, s, (const T*)qkv, plane, (T*)out, o_plane, S, S_pad, H, out8_scale, obs,
                        q_log2 ? 1 : 0, q0, S_pad);
@@ -1085,20 +1006,8 @@ hipError_t launch_attention_sw_t(const void* qkv, int64_t plane, void* out, int6
                                  float out8_scale, Fp8Obs obs, int cus, bool q_log2, int Sq = 0) {
     if (Sq <= 0) Sq = S_pad;
     constexpr int LDS = 4 * 2 * 64 * 128 * (NSPLIT == 1 ? 1 : 2) + 8 * 4096;     // K/V ring + output staging
-    static std::mutex mu;
-    static bool configured[64] = {false};
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
+    const hipError_t e = ensure_dynamic_lds<attention_sw_kernel<T, NSPLIT>>(LDS);
     if (e != hipSuccess) return e;
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-        if (!configured[dev]) {
-            e = hipFuncSetAttribute((const void*)attention_sw_kernel<T, NSPLIT>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-            if (e != hipSuccess) return e;
-            configured[dev] = true;
-        }
-    }
     const int nblk = ((Sq + 255) / 256) * (H / 64) * nseq;
     int per = (nblk + cus - 1) / cus;
     dim3 grid((nblk + per - 1) / per), blk(512);
@@ -1118,8 +1027,8 @@ hipError_t launch_attention_sw_t(const void* qkv, int64_t plane, void* out, int6
     return hipGetLastError();
 }
 
-static int g_attn_variant = -1;                 // -1: the rule below, 0: 4-wave kernel, 1: pipelined kernel
-void attention_set_variant(int v) { g_attn_variant = v; }
+static std::atomic<int> g_attn_variant{-1};     // -1: the rule below, 0: 4-wave kernel, 1: pipelined kernel
+void attention_set_variant(int v) { g_attn_variant.store(v, std::memory_order_relaxed); }
 
 static std::atomic<int> g_attn_cus{0};          // measurement hook (a launch on a CU-masked stream): 0 = the device's CU count
 void attention_set_cus(int cus) { g_attn_cus.store(cus, std::memory_order_relaxed); }
@@ -1158,7 +1067,7 @@ int attention_rule(int nseq, int S_pad, int H, int terms, int cus) {
 }
 
 static int pick_variant(int nseq, int S_pad, int H, int terms, int cus) {
-    const int forced = g_attn_variant;
+    const int forced = g_attn_variant.load(std::memory_order_relaxed);
     if (forced == 2) return (S_pad >= 256 && S_pad % 256) ? 2 : 1;      // forced split needs a full block and a rest
     if (forced >= 0) return forced == 1 ? 1 : 0;
     return attention_rule(nseq, S_pad, H, terms, cus);
@@ -1183,12 +1092,9 @@ hipError_t launch_attention(const void* qkv, int64_t plane, void* out, int64_t o
     if (device_cus(&cus) || cus < 1) return hipErrorInvalidDevice;
     if (const int o = g_attn_cus.load(std::memory_order_relaxed); o > 0) cus = o;
     const int v = pick_variant(nseq, S_pad, H, num.terms, cus);
-    if (!num.f16) {
-        if (num.terms == 1) return launch_attention_v<bf16, 1>(v, qkv, plane, out, o_plane, nseq, S, S_pad, H, s, out8_scale, obs, cus, q_log2);
-        return launch_attention_v<bf16, 3>(v, qkv, plane, out, o_plane, nseq, S, S_pad, H, s, out8_scale, obs, cus, q_log2);
-    }
-    if (num.terms == 1) return launch_attention_v<f16, 1>(v, qkv, plane, out, o_plane, nseq, S, S_pad, H, s, out8_scale, obs, cus, q_log2);
-    return launch_attention_v<f16, 3>(v, qkv, plane, out, o_plane, nseq, S, S_pad, H, s, out8_scale, obs, cus, q_log2);
+    return with_format<BF16_1 | BF16_3 | F16_1 | F16_3>(num, [&](auto t, auto terms) {
+        return launch_attention_v<typename decltype(t)::type, terms.value>(v, qkv, plane, out, o_plane, nseq, S, S_pad, H, s, out8_scale, obs, cus, q_log2);
+    });
 }
 
 }  // namespace vtq

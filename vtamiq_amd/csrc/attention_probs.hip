@@ -25,6 +25,7 @@
 // kQLog2Scale); otherwise the kernel multiplies the fp32 score by it.  Row max and row sum are fp32.
 #include "dev_common.h"
 #include "kernels.h"
+#include "launch_common.h"
 
 namespace vtq {
 namespace {
@@ -161,14 +162,11 @@ hipError_t launch_attention_probs(const void* qkv, int64_t plane, float* probs, 
     if (nwg > 0x7fffffff) return hipErrorInvalidValue;
     const dim3 g((unsigned)nwg), b(256);
     const int ql = q_log2 ? 1 : 0;
-    if (num.f16) {
-        if (num.terms == 3) hipLaunchKernelGGL((attention_probs_kernel<f16, 3>), g, b, 0, s, (const f16*)qkv, plane, probs, S, S_pad, H, ql);
-        else hipLaunchKernelGGL((attention_probs_kernel<f16, 1>), g, b, 0, s, (const f16*)qkv, plane, probs, S, S_pad, H, ql);
-    } else {
-        if (num.terms == 3) hipLaunchKernelGGL((attention_probs_kernel<bf16, 3>), g, b, 0, s, (const bf16*)qkv, plane, probs, S, S_pad, H, ql);
-        else hipLaunchKernelGGL((attention_probs_kernel<bf16, 1>), g, b, 0, s, (const bf16*)qkv, plane, probs, S, S_pad, H, ql);
-    }
-    return hipGetLastError();
+    return with_format<BF16_1 | BF16_3 | F16_1 | F16_3>(num, [&](auto t, auto terms) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((attention_probs_kernel<T, terms.value>), g, b, 0, s, (const T*)qkv, plane, probs, S, S_pad, H, ql);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace vtq

@@ -20,8 +20,13 @@
 // for sequences of different lengths packed back to back (vtq_forward_varlen's layout), which look their work item up in the call's attention
 // block table and address r, the result and the partials like the rows.  The body sees (first row, S, block, head) and two pointers either way,
 // so a sequence's bits are those of the uniform kernel at S = S_pad = S_j, whatever else the launch holds.
+//
+// The Q-fragment load, the K tile staging, the QK^T block and the sweep-0 update / combine are COPIES of attention_probs.hip's, by decision:
+// each was tried as a __forceinline__ function of a shared header, one at a time, and each changed the instruction stream of a kernel
+// here or there (profiles/r18_launchers_isa.txt).
 #include "dev_common.h"
 #include "kernels.h"
+#include "launch_common.h"
 
 namespace vtq {
 namespace {
@@ -236,14 +241,11 @@ hipError_t launch_rollout_step(const void* qkv, int64_t plane, const float* r, i
     if (nwg > 0x7fffffff || nseq > 65535) return hipErrorInvalidValue;
     const dim3 g((unsigned)nwg), b(256);
     const int ql = q_log2 ? 1 : 0;
-    if (num.f16) {
-        if (num.terms == 3) hipLaunchKernelGGL((rollout_step_kernel<f16, 3>), g, b, 0, s, (const f16*)qkv, plane, r, part, S, S_pad, H, ql, token);
-        else hipLaunchKernelGGL((rollout_step_kernel<f16, 1>), g, b, 0, s, (const f16*)qkv, plane, r, part, S, S_pad, H, ql, token);
-    } else {
-        if (num.terms == 3) hipLaunchKernelGGL((rollout_step_kernel<bf16, 3>), g, b, 0, s, (const bf16*)qkv, plane, r, part, S, S_pad, H, ql, token);
-        else hipLaunchKernelGGL((rollout_step_kernel<bf16, 1>), g, b, 0, s, (const bf16*)qkv, plane, r, part, S, S_pad, H, ql, token);
-    }
-    hipError_t e = hipGetLastError();
+    const hipError_t e = with_format<BF16_1 | BF16_3 | F16_1 | F16_3>(num, [&](auto t, auto terms) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((rollout_step_kernel<T, terms.value>), g, b, 0, s, (const T*)qkv, plane, r, part, S, S_pad, H, ql, token);
+        return hipGetLastError();
+    });
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(rollout_combine_kernel, dim3((S + 255) / 256, nseq), dim3(256), 0, s, (const float*)part, r, token, out, heads_out, S, nh, nqb);
     return hipGetLastError();
@@ -259,14 +261,11 @@ hipError_t launch_rollout_step_varlen(const void* qkv, int64_t plane, const floa
     const dim3 g((unsigned)nblocks), b(256);
     const int ql = q_log2 ? 1 : 0;
     const int4* bl = (const int4*)blocks;
-    if (num.f16) {
-        if (num.terms == 3) hipLaunchKernelGGL((rollout_step_varlen_kernel<f16, 3>), g, b, 0, s, (const f16*)qkv, plane, r, part, bl, nqb_max, R, H, ql, token);
-        else hipLaunchKernelGGL((rollout_step_varlen_kernel<f16, 1>), g, b, 0, s, (const f16*)qkv, plane, r, part, bl, nqb_max, R, H, ql, token);
-    } else {
-        if (num.terms == 3) hipLaunchKernelGGL((rollout_step_varlen_kernel<bf16, 3>), g, b, 0, s, (const bf16*)qkv, plane, r, part, bl, nqb_max, R, H, ql, token);
-        else hipLaunchKernelGGL((rollout_step_varlen_kernel<bf16, 1>), g, b, 0, s, (const bf16*)qkv, plane, r, part, bl, nqb_max, R, H, ql, token);
-    }
-    hipError_t e = hipGetLastError();
+    const hipError_t e = with_format<BF16_1 | BF16_3 | F16_1 | F16_3>(num, [&](auto t, auto terms) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((rollout_step_varlen_kernel<T, terms.value>), g, b, 0, s, (const T*)qkv, plane, r, part, bl, nqb_max, R, H, ql, token);
+        return hipGetLastError();
+    });
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(rollout_combine_varlen_kernel, dim3((S_max + 255) / 256, nseq), dim3(256), 0, s, (const float*)part, r, token, out, heads_out,
                        row0, len, nh, nqb_max, R);

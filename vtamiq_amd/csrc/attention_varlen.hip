@@ -10,77 +10,18 @@
 // built both ways (the body as a device function taking the decoded block; the same with the decode passed in as a functor evaluated at its
 // old place): each time hipcc gave attention.hip's own attention_kernel another register allocation and instruction schedule (~7000
 // changed lines of ISA), i.e. a production kernel that would have to be measured and verified again for no gain of its own.  With the copy
-// attention.hip and its objects stay exactly as they were.
+// attention.hip and its objects stay exactly as they were.  What the two files do share is attention_common.h: the __forceinline__ leaf
+// helpers (lds_tr16, split_p8, exp_pair, prescale_q), whose move left every kernel's instruction stream as it was.
 // The e4m3 output form of the fp8 experiment is not offered here (vtq_forward_varlen refuses that engine).
-#include <mutex>
 #include <vector>
 
+#include "attention_common.h"
 #include "dev_common.h"
 #include "kernels.h"
+#include "launch_common.h"
 
 namespace vtq {
 namespace {
-
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(8))) short s16x8;
-__device__ __forceinline__ s16x4 lds_tr16(const char* p) {
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)p);
-}
-
-// Split 8 probabilities into the hi / lo MFMA fragments (element j of the fragment = p[j]); attention.hip split_p8.
-template <typename T>
-__device__ __forceinline__ void split_p8(const float (&p)[8], typename Vec<T>::x8& hi, typename Vec<T>::x8& lo) {
-    if constexpr (std::is_same<T, f16>::value) {
-        typedef __attribute__((ext_vector_type(2))) _Float16 h2;
-        uint32_t hw[4], lw[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const auto hp = __builtin_amdgcn_cvt_pkrtz(p[2 * j], p[2 * j + 1]);      // truncation: hi <= p, p - hi exact in fp32
-            const h2 hh = __builtin_bit_cast(h2, hp);
-            hw[j] = __builtin_bit_cast(uint32_t, hp);
-            lw[j] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(p[2 * j] - (float)hh[0], p[2 * j + 1] - (float)hh[1]));
-        }
-        typedef __attribute__((ext_vector_type(4))) uint32_t u4;
-        hi = __builtin_bit_cast(f16x8, u4{hw[0], hw[1], hw[2], hw[3]});
-        lo = __builtin_bit_cast(f16x8, u4{lw[0], lw[1], lw[2], lw[3]});
-    } else {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const uint32_t hb = __builtin_bit_cast(uint32_t, p[j]) & 0xFFFF0000u;     // bf16 by truncation
-            const float hf = __builtin_bit_cast(float, hb);
-            hi[j] = __builtin_bit_cast(bf16, (unsigned short)(hb >> 16));
-            lo[j] = (bf16)(p[j] - hf);
-        }
-    }
-}
-
-// Two scores at a time (attention.hip exp_pair): the row sum runs as two partial sums, added at the end of a tile.
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-template <int NSPLIT>
-__device__ __forceinline__ void exp_pair(f32x16& v, int r, float m_new, float sc, float nm, f32x2& rs2) {      // registers r, r + 1 of v
-    f32x2 t = {v[r], v[r + 1]};
-    if constexpr (NSPLIT == 3) t = t - f32x2{m_new, m_new};
-    else t = t * f32x2{sc, sc} + f32x2{nm, nm};
-    f32x2 pv = {__builtin_amdgcn_exp2f(t[0]), __builtin_amdgcn_exp2f(t[1])};
-    v[r] = pv[0];
-    v[r + 1] = pv[1];
-    rs2 += pv;
-}
-
-// 3-term formats: the softmax scale folded into Q once per query block (attention.hip prescale_q)
-template <typename T>
-__device__ __forceinline__ void prescale_q(typename Vec<T>::x8 (&qf)[2][4], float sc) {
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const float v = ((float)qf[0][t][j] + (float)qf[1][t][j]) * sc;
-            T a, b;
-            split2<T>(v, a, b);
-            qf[0][t][j] = a;
-            qf[1][t][j] = b;
-        }
-}
 
 // blocks[w] = {first row of the sequence, S_j, query block (128 rows), head} for work id w; gridDim.x = number of entries
 template <typename T, int NSPLIT>
@@ -356,20 +297,8 @@ template <typename T, int NSPLIT>
 hipError_t launch_varlen_t(const void* qkv, int64_t plane, void* out, int64_t o_plane, const int* blocks, int nblocks, int H, hipStream_t s,
                            bool q_log2) {
     constexpr int LDS = 2 * 2 * 64 * 128 * (NSPLIT == 1 ? 1 : 2);
-    static std::mutex mu;
-    static bool configured[64] = {false};          // hipFuncSetAttribute is per device
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
+    const hipError_t e = ensure_dynamic_lds<attention_varlen_kernel<T, NSPLIT>>(LDS);
     if (e != hipSuccess) return e;
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-        if (!configured[dev]) {
-            e = hipFuncSetAttribute((const void*)attention_varlen_kernel<T, NSPLIT>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-            if (e != hipSuccess) return e;
-            configured[dev] = true;
-        }
-    }
     hipLaunchKernelGGL((attention_varlen_kernel<T, NSPLIT>), dim3(nblocks), dim3(256), LDS, s, (const T*)qkv, plane, (T*)out, o_plane,
                        (const int4*)blocks, H, q_log2 ? 1 : 0);
     return hipGetLastError();
@@ -396,12 +325,9 @@ hipError_t launch_attention_varlen(const void* qkv, int64_t plane, void* out, in
                                    hipStream_t s, bool q_log2) {
     if (H % 64 || H < 64 || nblocks < 1 || !blocks || (num.terms != 1 && num.terms != 3) || num.f16 > 1) return hipErrorInvalidValue;
     if (q_log2 && num.terms != 3) return hipErrorInvalidValue;
-    if (!num.f16) {
-        if (num.terms == 1) return launch_varlen_t<bf16, 1>(qkv, plane, out, o_plane, blocks, nblocks, H, s, q_log2);
-        return launch_varlen_t<bf16, 3>(qkv, plane, out, o_plane, blocks, nblocks, H, s, q_log2);
-    }
-    if (num.terms == 1) return launch_varlen_t<f16, 1>(qkv, plane, out, o_plane, blocks, nblocks, H, s, q_log2);
-    return launch_varlen_t<f16, 3>(qkv, plane, out, o_plane, blocks, nblocks, H, s, q_log2);
+    return with_format<BF16_1 | BF16_3 | F16_1 | F16_3>(num, [&](auto t, auto terms) {
+        return launch_varlen_t<typename decltype(t)::type, terms.value>(qkv, plane, out, o_plane, blocks, nblocks, H, s, q_log2);
+    });
 }
 
 }  // namespace vtq

@@ -7,10 +7,9 @@
 // reads the fp32 residual rows once.  This file holds the row LayerNorm and that attention; the tail's five linear stages run on the
 // MFMA pipe (skinny.hip).  Results are identical in exact arithmetic to running the full layer and reading row 0 (SURVEY.md 8d allows
 // the pruning; bench reports executed flops).
-#include <mutex>
-
 #include "dev_common.h"
 #include "kernels.h"
+#include "launch_common.h"
 
 namespace vtq {
 namespace {
@@ -355,20 +354,8 @@ template <int V4>
 hipError_t launch_fold_attention(const float* x, int64_t seq_stride, const float* lw, const float* lb, const float* u, float* part, int nseq,
                                  int S, int nh, int q_log2, hipStream_t s, VarSeq vl) {
     constexpr int lds = (kFoldSub * (256 * V4 + kFoldPad) + 6 * kFoldSub * 16 + 48) * 4;
-    {   // beyond the default dynamic-LDS limit: raise it once per device
-        static std::mutex mu;
-        static bool configured[64] = {false};
-        int dev = 0;
-        hipError_t e = hipGetDevice(&dev);
-        if (e != hipSuccess) return e;
-        std::lock_guard<std::mutex> lk(mu);
-        if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-        if (!configured[dev]) {
-            e = hipFuncSetAttribute((const void*)cls_fold_attention_kernel<V4>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-            if (e != hipSuccess) return e;
-            configured[dev] = true;
-        }
-    }
+    const hipError_t e = ensure_dynamic_lds<cls_fold_attention_kernel<V4>>(lds);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL((cls_fold_attention_kernel<V4>), dim3((S + kFoldChunk - 1) / kFoldChunk, nseq), dim3(512), lds, s, x, seq_stride, lw, lb, u,
                        part, S, nh, q_log2, vl);
     return hipGetLastError();
@@ -383,11 +370,11 @@ hipError_t launch_cls_fold(const float* q, const void* wk, int64_t w_plane, int 
         return hipErrorInvalidValue;
     const int nh = H / 64, nchunks = (S + kFoldChunk - 1) / kFoldChunk;
     const dim3 gk(nh, (nseq + 3) / 4), blk(256);
-#define VTQ_KF(TT, NP) hipLaunchKernelGGL((cls_key_fold_kernel<TT, NP>), gk, dim3(H), 0, s, q, (const TT*)wk, w_plane, ldw, u, nseq, H)
-    if (!f16_) { if (wplanes == 1) VTQ_KF(bf16, 1); else VTQ_KF(bf16, 2); }
-    else { if (wplanes == 1) VTQ_KF(f16, 1); else VTQ_KF(f16, 2); }
-#undef VTQ_KF
-    hipError_t e = hipGetLastError();
+    hipError_t e = with_format<BF16_1 | BF16_2 | F16_1 | F16_2>(f16_ ? 1 : 0, wplanes, [&](auto t, auto planes) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((cls_key_fold_kernel<T, planes.value>), gk, dim3(H), 0, s, q, (const T*)wk, w_plane, ldw, u, nseq, H);
+        return hipGetLastError();
+    });
     if (e != hipSuccess) return e;
     e = H == 768 ? launch_fold_attention<3>(x, seq_stride, lw, lb, u, part, nseq, S, nh, q_log2 ? 1 : 0, s, vl)
                  : launch_fold_attention<4>(x, seq_stride, lw, lb, u, part, nseq, S, nh, q_log2 ? 1 : 0, s, vl);

@@ -377,6 +377,7 @@ inline int grid_for(int64_t work, int block) {
 }  // namespace
 
 // dispatch on (f16, planes) -> K<T, NPL>; e4m3 outputs (f16 == 2) exist in builds of the fp8 experiment only (-DVTQ_WITH_FP8)
+// (not launch_common.h with_format: that one has no e4m3 branch, and one here would make the shared form longer than this macro)
 #ifdef VTQ_WITH_FP8
 #define VTQ_FMT_F8(f16_, npl_, CALL) else if ((f16_) == 2 && (npl_) == 1) { CALL(f8, 1); }
 #else

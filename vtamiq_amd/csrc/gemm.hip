@@ -46,6 +46,7 @@
 
 #include "dev_common.h"
 #include "kernels.h"
+#include "launch_common.h"
 
 namespace vtq {
 
@@ -867,20 +868,8 @@ hipError_t schedule_for(int ntm, int ntn, int cg, DevSched& ds, hipStream_t s) {
 
 template <typename T, int TERMS, int EPI> hipError_t launch_t(GemmArgs a, hipStream_t s) {
     constexpr int LDS = 163840;                    // full tiles: DMA ring 128 KiB, epilogue images 256x528 B; half tiles: 3 x 48 KiB; bias vector (N <= 4096) above 144 KiB
-    static std::mutex mu;
-    static bool configured[64] = {false};          // hipFuncSetAttribute is per device
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
+    hipError_t e = ensure_dynamic_lds<gemm_pp2_kernel<T, TERMS, EPI>>(LDS);
     if (e != hipSuccess) return e;
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-        if (!configured[dev]) {
-            e = hipFuncSetAttribute((const void*)gemm_pp2_kernel<T, TERMS, EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-            if (e != hipSuccess) return e;
-            configured[dev] = true;
-        }
-    }
     constexpr int WPL = (TERMS == 3) ? 2 : 1;
     DevSched ds;
     e = schedule_for(a.M / 256, a.N / 256, column_group(a.N / 256, a.K, WPL), ds, s);
@@ -953,15 +942,9 @@ hipError_t launch_gemm(const GemmArgs& a, Num num, int epilogue, hipStream_t s) 
         return hipErrorNotSupported;
 #endif
     }
-    if (!num.f16) {
-        if (num.terms == 1) return launch_e<bf16, 1>(a, epilogue, s);
-        if (num.terms == 3) return launch_e<bf16, 3>(a, epilogue, s);
-    } else {
-        if (num.terms == 1) return launch_e<f16, 1>(a, epilogue, s);
-        if (num.terms == 2) return launch_e<f16, 2>(a, epilogue, s);
-        if (num.terms == 3) return launch_e<f16, 3>(a, epilogue, s);
-    }
-    return hipErrorInvalidValue;
+    return with_format<BF16_1 | BF16_3 | F16_1 | F16_2 | F16_3>(num, [&](auto t, auto terms) {
+        return launch_e<typename decltype(t)::type, terms.value>(a, epilogue, s);
+    });
 }
 
 }  // namespace vtq

@@ -27,10 +27,9 @@
 //     residual row brought into LDS by LDS-DMA one pass ahead, two wave reductions, x stored as 1-KiB row segments, the planes as 512-B ones.
 //   * measured (profiles/r04_rowln_*.txt): bit-identical and NOT faster than the two launches it replaces -- out-proj ties,
 //     fc2 is 7 % slower -- so the engine uses it only under vtq_config.options & VTQ_OPT_FUSED_LAYERNORM.
-#include <mutex>
-
 #include "dev_common.h"
 #include "kernels.h"
+#include "launch_common.h"
 
 namespace vtq {
 
@@ -386,37 +385,32 @@ __global__ __launch_bounds__(256, 1) void gemm_rowln_kernel(RowLnKArgs p) {
     }
 }
 
+template <typename T, bool LN>
+hipError_t launch_rowln_t(const RowLnKArgs& k, int grid, hipStream_t s) {
+    const hipError_t e = ensure_dynamic_lds<gemm_rowln_kernel<T, LN>>(kLds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((gemm_rowln_kernel<T, LN>), dim3(grid), dim3(256), kLds, s, k);
+    return hipGetLastError();
+}
+
 }  // namespace
 
 hipError_t launch_gemm_rowln(const RowLnArgs& a, Num num, hipStream_t s) {
     if (a.M <= 0 || a.M % kRows || a.K <= 0 || a.K % 32 || a.K < 128 || a.lda % 8 || a.N != kH || num.terms != 3 || num.f16 > 1) return hipErrorInvalidValue;
     if (!a.A || !a.W || !a.bias || !a.x || (a.ln_w && (!a.ln_b || !a.out))) return hipErrorInvalidValue;
-    static std::mutex mu;
-    static bool configured[64][4] = {};
     int dev = 0, cus = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;
     if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
     e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     if (e != hipSuccess) return e;
-    const bool ln = a.ln_w != nullptr;
-    typedef void (*kern_t)(RowLnKArgs);
-    const kern_t kern = num.f16 ? (ln ? (kern_t)gemm_rowln_kernel<f16, true> : (kern_t)gemm_rowln_kernel<f16, false>)
-                                : (ln ? (kern_t)gemm_rowln_kernel<bf16, true> : (kern_t)gemm_rowln_kernel<bf16, false>);
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        bool& done = configured[dev][num.f16 * 2 + (ln ? 1 : 0)];
-        if (!done) {
-            e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
-            if (e != hipSuccess) return e;
-            done = true;
-        }
-    }
-    RowLnKArgs k{a.A, a.a_plane, a.lda, a.W, a.w_plane, a.M, a.K, a.bias, a.gamma, a.x, a.ln_w, a.ln_b, a.out, a.o_plane};
+    const RowLnKArgs k{a.A, a.a_plane, a.lda, a.W, a.w_plane, a.M, a.K, a.bias, a.gamma, a.x, a.ln_w, a.ln_b, a.out, a.o_plane};
     const int ntiles = a.M / kRows;
     const int grid = ntiles < cus ? ntiles : cus;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), kLds, s, k);
-    return hipGetLastError();
+    return with_format<BF16_3 | F16_3>(num, [&](auto t, auto) {
+        using T = typename decltype(t)::type;
+        return a.ln_w ? launch_rowln_t<T, true>(k, grid, s) : launch_rowln_t<T, false>(k, grid, s);
+    });
 }
 
 }  // namespace vtq

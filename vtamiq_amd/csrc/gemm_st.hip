@@ -37,8 +37,7 @@
 // inside a forward is 3 - 10 %.  So small tiles only pay while the 256x256 form leaves most CUs idle (gemm.hip gemm_tile_rule).
 #include "dev_common.h"
 #include "kernels.h"
-
-#include <mutex>
+#include "launch_common.h"
 
 namespace vtq {
 
@@ -328,20 +327,10 @@ hipError_t launch_v(const GemmArgs& a, hipStream_t s) {
     constexpr int APL = (TERMS == 1) ? 1 : 2, WPL = (TERMS == 3) ? 2 : 1;
     constexpr int LDS = NST * (APL * BM + WPL * BN) * 128;
     static_assert(LDS <= 163840, "LDS ring");
-    auto kern = gemm_st_kernel<T, TERMS, EPI, BM, BN, WR, WC, NST, NPW>;
+    constexpr auto kern = gemm_st_kernel<T, TERMS, EPI, BM, BN, WR, WC, NST, NPW>;
     if constexpr (LDS > 65536) {
-        static std::mutex mu;
-        static bool configured[64] = {false};
-        int dev = 0;
-        hipError_t e = hipGetDevice(&dev);
+        const hipError_t e = ensure_dynamic_lds<kern>(LDS);
         if (e != hipSuccess) return e;
-        std::lock_guard<std::mutex> lk(mu);
-        if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-        if (!configured[dev]) {
-            e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-            if (e != hipSuccess) return e;
-            configured[dev] = true;
-        }
     }
     const int ntm = a.M / BM, ntn = a.N / BN;
     GemmArgs b = a;
@@ -377,15 +366,9 @@ template <typename T, int TERMS> hipError_t launch_epi(const GemmArgs& a, int ep
 
 hipError_t launch_gemm_st(const GemmArgs& a, Num num, int epilogue, int variant, hipStream_t s) {
     if (a.M <= 0 || a.M % 256 || a.N <= 0 || a.N % 256 || a.K <= 0 || a.K % 64 || a.lda % 16 || !num_valid(num) || num.f16 == 2) return hipErrorInvalidValue;
-    if (!num.f16) {
-        if (num.terms == 1) return launch_epi<bf16, 1>(a, epilogue, variant, s);
-        if (num.terms == 3) return launch_epi<bf16, 3>(a, epilogue, variant, s);
-    } else {
-        if (num.terms == 1) return launch_epi<f16, 1>(a, epilogue, variant, s);
-        if (num.terms == 2) return launch_epi<f16, 2>(a, epilogue, variant, s);
-        if (num.terms == 3) return launch_epi<f16, 3>(a, epilogue, variant, s);
-    }
-    return hipErrorInvalidValue;
+    return with_format<BF16_1 | BF16_3 | F16_1 | F16_2 | F16_3>(num, [&](auto t, auto terms) {
+        return launch_epi<typename decltype(t)::type, terms.value>(a, epilogue, variant, s);
+    });
 }
 
 }  // namespace vtq

@@ -8,10 +8,10 @@
 // with such operands before a single byte has moved; bench.py prints it beside the nominal peak (roofline.practical_peak_tflops_measured_here).
 // Measurement only: nothing on the forward path calls it.
 #include <chrono>
-#include <mutex>
 
 #include "dev_common.h"
 #include "kernels.h"
+#include "launch_common.h"
 
 namespace vtq {
 namespace {
@@ -80,10 +80,8 @@ __global__ __launch_bounds__(256) void cu_map_kernel(unsigned* out, long long sp
 
 hipError_t launch_cu_map(unsigned* out, int nblocks, int spin_us, hipStream_t s) {
     constexpr int LDS = 144 * 1024;
-    static std::once_flag once;
-    static hipError_t attr = hipSuccess;
-    std::call_once(once, [] { attr = hipFuncSetAttribute((const void*)cu_map_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS); });
-    if (attr != hipSuccess) return attr;
+    const hipError_t e = ensure_dynamic_lds<cu_map_kernel>(LDS);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(cu_map_kernel, dim3(nblocks), dim3(256), LDS, s, out, (long long)spin_us * 100);      // wall_clock64: 100 MHz
     return hipGetLastError();
 }

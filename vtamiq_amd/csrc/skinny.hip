@@ -15,10 +15,9 @@
 //   * the 8 waves split K (k-step = 32) round-robin, three k-steps' loads in flight per wave (a 768-deep product is one
 //     exposed memory latency), and combine their partial sums through LDS; wave w < 4 then finishes row block w (16 rows):
 //     bias, activation, residual / gate forms, and writes fp32 and / or the planes the next stage reads.
-#include <mutex>
-
 #include "dev_common.h"
 #include "kernels.h"
+#include "launch_common.h"
 
 namespace vtq {
 namespace {
@@ -182,16 +181,14 @@ hipError_t launch_skinny(const SkinnyArgs& a, Num num, hipStream_t s) {
     for (int t = 1; t <= 4; t *= 2)
         if (a.R <= 16 * t || nb * ((a.R + 16 * t - 1) / (16 * t)) <= 256) { rb = t; break; }
     const dim3 g(nb, (a.R + 16 * rb - 1) / (16 * rb)), blk(512);
-#define VTQ_SK(TT, TM)                                                                              \
-    do {                                                                                            \
-        if (rb == 1) hipLaunchKernelGGL((skinny_linear_kernel<TT, TM, 1>), g, blk, 0, s, a);        \
-        else if (rb == 2) hipLaunchKernelGGL((skinny_linear_kernel<TT, TM, 2>), g, blk, 0, s, a);   \
-        else hipLaunchKernelGGL((skinny_linear_kernel<TT, TM, 4>), g, blk, 0, s, a);                \
-    } while (0)
-    if (!num.f16) { if (num.terms == 1) VTQ_SK(bf16, 1); else if (num.terms == 3) VTQ_SK(bf16, 3); else return hipErrorInvalidValue; }
-    else { if (num.terms == 1) VTQ_SK(f16, 1); else if (num.terms == 2) VTQ_SK(f16, 2); else VTQ_SK(f16, 3); }
-#undef VTQ_SK
-    return hipGetLastError();
+    // an e4m3 engine's skinny stages run on fp16 planes: any non-zero element code is fp16 here (num_valid has refused the rest)
+    return with_format<BF16_1 | BF16_3 | F16_1 | F16_2 | F16_3>(num.f16 ? 1 : 0, num.terms, [&](auto t, auto terms) {
+        using T = typename decltype(t)::type;
+        if (rb == 1) hipLaunchKernelGGL((skinny_linear_kernel<T, terms.value, 1>), g, blk, 0, s, a);
+        else if (rb == 2) hipLaunchKernelGGL((skinny_linear_kernel<T, terms.value, 2>), g, blk, 0, s, a);
+        else hipLaunchKernelGGL((skinny_linear_kernel<T, terms.value, 4>), g, blk, 0, s, a);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_rows_to_planes(const float* x, int ldx, const float* slope, void* out, int64_t plane, int ldo, int R, int K, int f16_,
