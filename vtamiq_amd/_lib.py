@@ -148,6 +148,13 @@ SAMPLER_SIGNATURES = {
     "vtq_k_sample_grid": (C.c_int, [_P, _P, _IP, C.POINTER(C.c_uint64), _I, C.c_uint64, _I, _P, _P, _P]),
 }
 
+# include/vtamiq_hip_weighted_sampler.h: the difference pass and the weighted sampler (vtamiq_amd.sampling)
+WEIGHTED_SAMPLER_SIGNATURES = {
+    "vtq_k_diff_cells": (C.c_int, [_P, C.c_int64, _P, _P, C.POINTER(C.c_int64), _IP, _I, _I, _I, _P, C.c_int64, _P]),
+    "vtq_k_sample_weighted": (C.c_int, [_P, _P, _IP, C.POINTER(C.c_uint64), _I, _I, _P, C.c_int64, C.c_double, C.c_double, C.c_uint64, _I,
+                                        _P, _P, _P]),
+}
+
 # the fp8 experiment (include/vtamiq_hip_fp8.h): exported only by a library built with -DVTQ_WITH_FP8 (python -m vtamiq_amd.build --fp8 ->
 # LIB_PATH_FP8, load_fp8()); bound when present
 FP8_SIGNATURES = {
@@ -183,7 +190,7 @@ def load(path: str | None = None) -> C.CDLL:
     # build of an OLDER tree (different ABI: argument layouts may differ) loads only with VTQ_ALLOW_ABI_MISMATCH=1, with a warning.
     relaxed = os.environ.get("VTQ_ALLOW_ABI_MISMATCH") == "1"
     for name, (res, args) in (list(SIGNATURES.items()) + list(ROLLOUT_SIGNATURES.items()) + list(IMAGE_SIGNATURES.items())
-                              + list(SAMPLER_SIGNATURES.items())):
+                              + list(SAMPLER_SIGNATURES.items()) + list(WEIGHTED_SAMPLER_SIGNATURES.items())):
         if relaxed and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)          # AttributeError if a declared symbol is not exported

@@ -6,6 +6,7 @@
 // (the reference runs two serial passes with the same weights, vtamiq.py:100-101).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -21,6 +22,7 @@
 #include "../../include/vtamiq_hip_rollout.h"
 #include "../../include/vtamiq_hip_images.h"
 #include "../../include/vtamiq_hip_sampler.h"
+#include "../../include/vtamiq_hip_weighted_sampler.h"
 #include "kernels.h"
 
 using namespace vtq;
@@ -1878,6 +1880,92 @@ int vtq_k_sample_grid(const int32_t* seg, const uint64_t* keys, const int32_t* s
         max_cells = Hg * Wg > max_cells ? Hg * Wg : max_cells;
     }
     HIP_TRY(launch_sample_grid(seg, keys, NS, max_cells, seed, amount_q, samples, scale_ids, (hipStream_t)stream));
+    return 0;
+}
+
+// include/vtamiq_hip_weighted_sampler.h: the cell geometry (cs, sh, sw) of an h x w level, checked the same way by both entries
+static const char* bad_cells(int32_t P, int32_t cs, int32_t sh, int32_t sw, int64_t hm, int64_t wm) {
+    if (cs < 1 || cs < 3 * P / 4) return "cs < max(1, 3 P / 4)";
+    if (sh != std::max<int64_t>(1, (hm + cs - 1) / cs) || sw != std::max<int64_t>(1, (wm + cs - 1) / cs)) return "sh, sw are not max(1, ceil((dim - P) / cs))";
+    if ((int64_t)sh * sw > VTQ_WSAMPLER_MAX_CELLS) return "more than 8192 cells";
+    return nullptr;
+}
+
+int vtq_k_diff_cells(const uint8_t* images, int64_t image_bytes, const int64_t* pairs, const int32_t* lev, const int64_t* pairs_host,
+                     const int32_t* lev_host, int32_t NP, int32_t NL, int32_t P, uint64_t* tab, int64_t tab_words, void* stream) {
+    if (!images || !pairs || !lev || !pairs_host || !lev_host || !tab) return fail("vtq_k_diff_cells: null argument");
+    if ((uintptr_t)lev % 16) return fail("vtq_k_diff_cells: lev is not 16-byte aligned");
+    if (NP < 1 || NP > 65535 || NL < 1) return fail("vtq_k_diff_cells: NP=%d (1 .. 65535), NL=%d (at least 1)", (int)NP, (int)NL);
+    if (P < 8 || P > 64) return fail("vtq_k_diff_cells: patch size %d (8 .. 64)", (int)P);
+    int64_t T = 0, max_pixels = 0;
+    int32_t row = 0;
+    for (int32_t p = 0; p < NP; ++p) {
+        const int64_t* q = pairs_host + (int64_t)p * 8;
+        const int64_t H = q[2], W = q[3];
+        if (H < P || W < P || H > VTQ_WSAMPLER_MAX_PIXELS || W > VTQ_WSAMPLER_MAX_PIXELS || H * W > VTQ_WSAMPLER_MAX_PIXELS)
+            return fail("vtq_k_diff_cells: pair %d is %lld x %lld (a patch of %d at least, %d pixels at most)", (int)p, (long long)H, (long long)W,
+                        (int)P, VTQ_WSAMPLER_MAX_PIXELS);
+        for (int k = 0; k < 2; ++k)
+            if (q[k] < 0 || image_bytes < 0 || q[k] > image_bytes || 3 * H * W > image_bytes - q[k])
+                return fail("vtq_k_diff_cells: pair %d, image %d (%lld x %lld at byte %lld) leaves the buffer of %lld bytes", (int)p, k, (long long)H,
+                            (long long)W, (long long)q[k], (long long)image_bytes);
+        if (q[4] != T) return fail("vtq_k_diff_cells: pair %d has its head at %lld, the table before it ends at %lld", (int)p, (long long)q[4], (long long)T);
+        T += 4;
+        if (q[5] != row) return fail("vtq_k_diff_cells: pair %d starts at row %lld of lev, the rows before it end at %d", (int)p, (long long)q[5], (int)row);
+        int32_t last = -1, cnt = 0;
+        for (; row < NL && lev_host[(int64_t)row * 8] == p; ++row, ++cnt) {
+            const int32_t* t = lev_host + (int64_t)row * 8;
+            const int32_t level = t[1], cs = t[2], sh = t[3], sw = t[4];
+            if (level <= last || level > 3) return fail("vtq_k_diff_cells: row %d of lev is level %d (0 .. 3, increasing within a pair)", (int)row, (int)level);
+            last = level;
+            const int64_t h = H >> level, w = W >> level;
+            if (h < P || w < P) return fail("vtq_k_diff_cells: row %d of lev: level %d of pair %d is %lld x %lld, below a patch", (int)row, (int)level, (int)p, (long long)h, (long long)w);
+            if (const char* why = bad_cells(P, cs, sh, sw, h - P, w - P)) return fail("vtq_k_diff_cells: row %d of lev: %s", (int)row, why);
+            if (t[5] != q[4] || t[6] != T) return fail("vtq_k_diff_cells: row %d of lev has head %d, tab_off %d (%lld, %lld expected)", (int)row, (int)t[5], (int)t[6], (long long)q[4], (long long)T);
+            T += 2 + (int64_t)sh * sw;
+            if (T > 0x7fffffff) return fail("vtq_k_diff_cells: a table above 2^31 - 1 words");
+        }
+        if (cnt < 1 || q[6] != cnt) return fail("vtq_k_diff_cells: pair %d has %d rows in lev and says %lld (at least 1)", (int)p, (int)cnt, (long long)q[6]);
+        max_pixels = std::max(max_pixels, H * W);
+    }
+    if (row != NL) return fail("vtq_k_diff_cells: row %d of lev belongs to pair %d (pairs 0 .. %d in order)", (int)row, (int)lev_host[(int64_t)row * 8], (int)NP - 1);
+    if (T != tab_words) return fail("vtq_k_diff_cells: the table has %lld words, tab_words=%lld", (long long)T, (long long)tab_words);
+    HIP_TRY(launch_diff_cells(images, pairs, lev, NP, max_pixels, P, tab, tab_words, (hipStream_t)stream));
+    return 0;
+}
+
+int vtq_k_sample_weighted(const int32_t* seg, const uint64_t* keys, const int32_t* seg_host, const uint64_t* keys_host, int32_t NS, int32_t P,
+                          const uint64_t* tab, int64_t tab_words, double dw, double uw, uint64_t seed, int32_t amount_q, int32_t* samples,
+                          int32_t* scale_ids, void* stream) {
+    if (!seg || !keys || !seg_host || !keys_host || !samples) return fail("vtq_k_sample_weighted: null argument");
+    if ((uintptr_t)seg % 16) return fail("vtq_k_sample_weighted: seg is not 16-byte aligned");
+    if (NS < 1) return fail("vtq_k_sample_weighted: NS=%d (at least 1)", (int)NS);
+    if (P < 8 || P > 64) return fail("vtq_k_sample_weighted: patch size %d (8 .. 64)", (int)P);
+    if (amount_q < 0 || amount_q > 65535) return fail("vtq_k_sample_weighted: amount_q=%d (0 .. 65535)", (int)amount_q);
+    if (!(dw >= 0.0) || !(uw >= 0.0) || !std::isfinite(dw) || !std::isfinite(uw) || dw + uw < 1e-6)
+        return fail("vtq_k_sample_weighted: weights dw=%g, uw=%g (finite, not negative, a sum of 1e-6 at least)", dw, uw);
+    int64_t total = 0;
+    int max_cells = 0;
+    for (int32_t j = 0; j < NS; ++j) {
+        const int32_t* t = seg_host + (int64_t)j * 12;
+        const int32_t first = t[0], n = t[1], cs = t[2], sh = t[3], sw = t[4], hm = t[5], wm = t[6], level = t[7], head = t[8], off = t[9];
+        if (n < 1 || n > VTQ_WSAMPLER_MAX_SAMPLES) return fail("vtq_k_sample_weighted: segment %d asks for %d samples (1 .. %d)", (int)j, (int)n, VTQ_WSAMPLER_MAX_SAMPLES);
+        if (hm < 0 || wm < 0 || hm >= VTQ_WSAMPLER_MAX_PIXELS || wm >= VTQ_WSAMPLER_MAX_PIXELS)
+            return fail("vtq_k_sample_weighted: segment %d has h - P = %d, w - P = %d (0 .. %d)", (int)j, (int)hm, (int)wm, VTQ_WSAMPLER_MAX_PIXELS - 1);
+        if (const char* why = bad_cells(P, cs, sh, sw, hm, wm)) return fail("vtq_k_sample_weighted: segment %d: %s", (int)j, why);
+        if (level < 0 || level > 3) return fail("vtq_k_sample_weighted: segment %d is on level %d (0 .. 3)", (int)j, (int)level);
+        if (level != 0 && !scale_ids) return fail("vtq_k_sample_weighted: scale_ids are required when a segment is on level %d", (int)level);
+        if (first != total) return fail("vtq_k_sample_weighted: segment %d starts at row %d, the segments before it end at %lld", (int)j, (int)first, (long long)total);
+        total += n;
+        if (total > 0x7fffffff) return fail("vtq_k_sample_weighted: more than 2^31 - 1 samples");
+        if (!(head == -1 && off == -1)) {
+            if (head < 0 || off < 0 || (int64_t)head + 4 > tab_words || (int64_t)off + 2 + (int64_t)sh * sw > tab_words)
+                return fail("vtq_k_sample_weighted: segment %d reads the table at %d and %d, beyond its %lld words", (int)j, (int)head, (int)off, (long long)tab_words);
+            if (!tab && dw > 0.0) return fail("vtq_k_sample_weighted: segment %d has a table, diff_weight is %g and tab is NULL", (int)j, dw);
+        }
+        max_cells = std::max(max_cells, sh * sw);
+    }
+    HIP_TRY(launch_sample_weighted(seg, keys, NS, max_cells, P, tab, dw, uw, seed, amount_q, samples, scale_ids, (hipStream_t)stream));
     return 0;
 }
 

@@ -256,6 +256,13 @@ hipError_t launch_gather_patches_u8(const uint8_t* images, const int* tab, const
 // seg int32 [NS][8], keys uint64 [NS], both on the device; max_cells = the largest Hg * Wg of the table (it sizes the workgroups only)
 hipError_t launch_sample_grid(const int* seg, const uint64_t* keys, int NS, int max_cells, uint64_t seed, int amount_q, int* samples,
                               int* scale_ids, hipStream_t s);
+// patch_sampler_weighted.hip (include/vtamiq_hip_weighted_sampler.h): the difference pass -- tab zeroed, then two kernels; pairs int64
+// [NP][8], lev int32 [NL][8] on the device, max_pixels = the largest H W (it sizes the grids only) -- and the weighted sampler, seg int32
+// [NS][12], max_cells = the largest sh * sw (it sizes the workgroups only)
+hipError_t launch_diff_cells(const uint8_t* images, const int64_t* pairs, const int* lev, int NP, int64_t max_pixels, int P, uint64_t* tab,
+                             int64_t tab_words, hipStream_t s);
+hipError_t launch_sample_weighted(const int* seg, const uint64_t* keys, int NS, int max_cells, int P, const uint64_t* tab, double dw, double uw,
+                                  uint64_t seed, int amount_q, int* samples, int* scale_ids, hipStream_t s);
 
 // ---- measurement: the matrix pipe's sustained rate on this device (mfma_stream.hip) -----------------------------------------
 // f16: 0 bf16, 1 fp16 operands; data: 0 the 3-term mix of gaussian hi / lo planes, 1 zeros, 2 uniform random

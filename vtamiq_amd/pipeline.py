@@ -34,7 +34,8 @@ import numpy as np
 import torch
 
 from .patches import ImageTables, check_samples_host, check_samples_host_varlen, extract_patches, gather_patches_u8, image_tables
-from .sampling import DEFAULT_NUM_SAMPLES_RATIO, PatchSampler, as_keys, launch_sample_grid, patch_counts, plan_samples, repeat_key
+from .sampling import (DEFAULT_NUM_SAMPLES_RATIO, MAX_CELLS, PatchSampler, WeightedPatchSampler, as_keys, launch_diff_cells, launch_sample_grid,
+                       launch_sample_weighted, patch_counts, plan_samples, plan_samples_weighted, repeat_key, segments_for)
 
 
 class _SlotRing:
@@ -366,6 +367,7 @@ class ImagePairVarlenPipeline(_SlotRing):
         self.dev_img = [torch.empty(self.max_image_bytes, dtype=torch.uint8, device=self.device) for _ in range(depth)]
         self.dev_tab = [torch.empty(words, dtype=torch.int32, device=self.device) for _ in range(depth)]
         self._batch = None
+        self._weighted = None                                # the weighted sampler's per-slot tables, made when it is first asked for
 
     def plan(self, sizes_first, sizes_second, lengths_first, lengths_second) -> VarlenBatch:
         return plan_varlen_batch(sizes_first, sizes_second, lengths_first, lengths_second, **self._caps)
@@ -513,6 +515,55 @@ class ImagePairVarlenPipeline(_SlotRing):
         return self._upload_and_gather(sb, lambda seg, keys, smp, sid: launch_sample_grid(seg, keys, sb.seg, sb.seg_keys, seed,
                                                                                           sampler.amount_q, smp, sid))
 
+    def _weighted_slots(self):
+        """Per slot, sized by capacity: a pinned int32 block and its device twin for the weighted sampler's segment table, keys, pair and
+        level tables, and the device's uint64 weight table (4 words per pair, 2 + 8192 per pair and level at most)."""
+        if self._weighted is None:
+            ns, pairs = self.num_scales * self.max_images, self.max_images // 2
+            words = 14 * ns + 16 * pairs + 8 * self.num_scales * pairs + 4
+            sums = pairs * (4 + self.num_scales * (2 + MAX_CELLS))
+            self._weighted = ([torch.zeros(words, dtype=torch.int32).pin_memory() for _ in range(self.depth)],
+                              [torch.empty(words, dtype=torch.int32, device=self.device) for _ in range(self.depth)],
+                              [torch.empty(sums, dtype=torch.int64, device=self.device) for _ in range(self.depth)])
+        return self._weighted
+
+    def _sample_weighted_and_gather(self, sb: SampledBatch, images, seed: int, sampler: WeightedPatchSampler, ratio: float):
+        """_sample_and_gather with the weighted sampler: the pair, level and segment tables go up in one more copy on the copy stream, and
+        behind the images the difference pass runs ONCE per pair -- whatever the number of repeats, and for both images of the pair,
+        aligned or not -- followed by one sampler launch over every segment of the batch.  With diff_weight == 0 no pixel is read.
+        Everything the two entries refuse is refused here first, by plan_samples_weighted and the sampler's constructor, before the slot
+        is staged: the tables the entries see are this function's own."""
+        B, R = len(images) // 2, sb.repeats
+        base = sb.batch.tables.img_off
+        plan = plan_samples_weighted(sb.batch.sizes, sb.batch.lengths.tolist(), self.num_scales, ratio, self.P,
+                                     pair_of=[i % B for i in range(len(sb.batch.sizes))])
+        if plan.seg.shape[0] != sb.seg.shape[0] or not np.array_equal(plan.seg[:, :2], sb.seg[:, :2]):
+            raise RuntimeError("the weighted plan's segments are not those of the batch's plan (rows, counts per level)")
+        pairs = plan.pairs.copy()
+        pairs[:, 0], pairs[:, 1] = base[:B], base[R * B:R * B + B]
+        NS, NL = plan.seg.shape[0], plan.lev.shape[0]
+        seg, lev = segments_for(plan, sampler), np.ascontiguousarray(plan.lev)
+        host, dev, sums = self._weighted_slots()
+        views, _, _ = self._stage(sb)
+        for v, im in zip(views, images):
+            v[...] = im
+        s = self.count % self.depth
+        at = np.cumsum([0, 12 * NS, 2 * NS + (-2 * NS) % 4, 16 * B, 8 * NL])
+        h = host[s].numpy()
+        h[at[0]:at[1]], h[at[1]:at[1] + 2 * NS] = seg.reshape(-1), sb.seg_keys.view(np.int32)
+        h[at[2]:at[3]], h[at[3]:at[4]] = pairs.reshape(-1).view(np.int32), plan.lev.reshape(-1)
+        flat, d, tab = self.dev_img[s][:sb.batch.tables.image_bytes], dev[s], sums[s]
+        weigh = sampler.diff_weight > 0
+
+        def behind(_seg, _keys, smp, sid):
+            d[:at[4]].copy_(host[s][:at[4]], non_blocking=True)
+            if weigh:
+                launch_diff_cells(flat, d[at[2]:at[3]], d[at[3]:at[4]], pairs, lev, self.P, tab, plan.tab_words)
+            launch_sample_weighted(d[at[0]:at[1]], d[at[1]:at[1] + 2 * NS], seg, sb.seg_keys, self.P, tab if weigh else None,
+                                   plan.tab_words if weigh else 0, sampler, seed, smp, sid)
+
+        return self._upload_and_gather(sb, behind)
+
     def _mean_over_repeats(self, q: torch.Tensor, repeats: int) -> torch.Tensor:
         if repeats == 1:
             return q
@@ -522,7 +573,9 @@ class ImagePairVarlenPipeline(_SlotRing):
     def submit_images(self, refs, dists, patch_count, keys=None, seed: int = 0, aligned: bool = True, num_repeats: int = 1,
                       sampler: Optional[PatchSampler] = None, scale_num_samples_ratio: float = DEFAULT_NUM_SAMPLES_RATIO) -> torch.Tensor:
         """submit() without coordinates: B pairs of host images uint8 [H, W, 3] and patch_count patches per image (one int, or B), sampled
-        on the device by the reference's default sampler (sampling.py).  keys: B 64-bit keys, one per pair (aligned=True: both images get
+        on the device by the reference's default sampler (sampling.py) -- or, with sampler=WeightedPatchSampler(diff_weight, uniform_weight),
+        where the pair's images differ: the difference pass and the weighted sampler run on the copy stream behind the upload, once and R
+        times for num_repeats=R, and a pair's images must have one size (ValueError).  keys: B 64-bit keys, one per pair (aligned=True: both images get
         the pair's key and must have one size, so they get the same coordinates) or 2B, references first (aligned=False); None: keys from
         the pipeline's submission counter.  The samples are a pure function of (seed, key, size, count).  num_repeats=R is the reference's
         validation repeats: every pair is scored R times with the keys sampling.repeat_key(key, r) -- the images cross PCIe once -- and
@@ -537,9 +590,15 @@ class ImagePairVarlenPipeline(_SlotRing):
             k2 = as_keys(keys, 2 * B) if keys is not None else as_keys([k ^ (s << 63) for s in (0, 1) for k in self._default_keys(B)], 2 * B)
             kr, kd = k2[:B], k2[B:]
         counts = patch_counts(patch_count, B)
+        weighted = isinstance(sampler, WeightedPatchSampler)
+        if weighted and any(r.shape != d.shape for r, d in zip(refs, dists)):
+            raise ValueError("WeightedPatchSampler: the two images of a pair must have one size (their difference is taken pixel by pixel)")
         sb = self.plan_sampled([r.shape[:2] for r in refs], [d.shape[:2] for d in dists], counts, counts, kr, kd, num_repeats,
                                scale_num_samples_ratio)
-        out = self._sample_and_gather(sb, refs + dists, seed, sampler)
+        if weighted:
+            out = self._sample_weighted_and_gather(sb, refs + dists, seed, sampler, scale_num_samples_ratio)
+        else:
+            out = self._sample_and_gather(sb, refs + dists, seed, sampler)
         return self._mean_over_repeats(self._as_pairs(sb.batch, out), sb.repeats)
 
     def submit_group_images(self, refs, dists, ref_index, patch_count, keys=None, seed: int = 0, num_repeats: int = 1,
@@ -549,6 +608,8 @@ class ImagePairVarlenPipeline(_SlotRing):
         ref_index[m].  patch_count: one int or G (references); patch_count_dist: one int or M (default: patch_count, which must then be
         one int).  keys: G + M keys, references first (None: from the submission counter); a distorted image with its reference's key and
         size gets its reference's coordinates.  num_repeats as submit_images.  Returns q (M,), fp64 when num_repeats > 1."""
+        if isinstance(sampler, WeightedPatchSampler):
+            raise NotImplementedError("submit_group_images with WeightedPatchSampler is not built: a group has no pairs of one size to difference")
         refs, dists = _host_images(refs, dists)
         G, M = len(refs), len(dists)
         idx = _ref_indices(ref_index, G, M)
