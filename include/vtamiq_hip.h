@@ -514,6 +514,19 @@ int  vtq_k_cls_fold(const float* q, const void* wqkv, int64_t w_plane, const flo
                     float* u, float* part, void* z, int64_t z_plane, float* ctx, void* stream);
 /* HOST-only: rows of a sequence per partial of vtq_k_cls_fold (a compile-time constant). */
 int  vtq_k_cls_fold_chunk_rows(void);
+/* vtq_k_cls_fold over nseq sequences of DIFFERENT lengths packed back to back, the table-driven form vtq_forward_varlen, vtq_forward_group and
+ * the cached entries run: sequence j is the seq_len[j] >= 1 rows from row0[j] = sum_{i<j} seq_len[i] (seq_len: HOST int32[nseq], nseq <= 65535);
+ * with R = the sum of all lengths and S_max = the largest:
+ *   x     fp32 [R][H]: rows [row0[j], row0[j] + seq_len[j]) are read for sequence j and nothing else -- no row at or behind R, and no row of
+ *         another sequence reaches sequence j's result.
+ *   q     fp32 [nseq][H], one query per sequence.  wqkv, bqkv, ln_w, ln_b, q_log2, num: as vtq_k_cls_fold.
+ *   u     fp32 [nseq][H/64][H];  part fp32 [nseq][ceil(S_max / vtq_k_cls_fold_chunk_rows())][H/64][H + 2]: a sequence writes and reads the
+ *         chunks of its own length only, the others of its slot are not touched;  z, ctx: as vtq_k_cls_fold (exactly those sizes).
+ * Row j of ctx has the bits vtq_k_cls_fold(nseq = 1, S = seq_len[j]) gives on that sequence's rows and query.  A test entry: it uploads its
+ * row-offset and length tables to a temporary and waits for `stream` before returning. */
+int  vtq_vl_cls_fold(const float* q, const void* wqkv, int64_t w_plane, const float* bqkv, const float* x, const float* ln_w, const float* ln_b,
+                     int32_t nseq, const int32_t* seq_len, int32_t H, int32_t num, int32_t q_log2, float* u, float* part, void* z,
+                     int64_t z_plane, float* ctx, void* stream);
 
 /* The DiffNet head + quality predictor alone (quality_decoder -> q_predictor, vtamiq.py:114-117, channel_attention.py:13-86) with
  * the handle's loaded weights: d fp32 [HB][H] = diff_scale(cls_ref - cls_dist) -> q_out fp32 [HB] (HB >= 1; exactly these extents are read

@@ -24,7 +24,7 @@ import torch
 from tests import footprint as fp
 from tests.footprint import Arena, FootprintError
 from tests.gpu_util import FORMATS, elt_dtype, num_code, planes_of, planes_value, stream, to_planes
-from tests.test_gpu_cls_fold import Case as FoldCase, _err as fold_err
+from tests.test_gpu_cls_fold import LOG2_SCALE, Case as FoldCase, _err as fold_err
 from tests.test_gpu_forward_vit import PROBS_TOL
 from tests.test_gpu_kernels import ATTN_TOL, FMTS, HEAD_TOL, LN_TOL, OUT_TOL, RESID_TOL, SKINNY_TOL, _attention_ref, _randn
 from tests.test_validation_metrics import TOL as METRIC_TOL
@@ -80,6 +80,12 @@ CONTRACTS = {
         "x": "R rows [0, S) of each sequence at x + r * seq_stride; [S * H, seq_stride) never used",
         "u": "W/R nseq * (H/64) * H fp32", "part": "W/R nseq * ceil(S / chunk_rows) * (H/64) * (H + 2) fp32",
         "z": "W rows [0, nseq), R rows [0, ceil64(nseq)) of planes x [*][(H/64) * H]; rows >= nseq reach no output", "ctx": "W nseq x H fp32"},
+    "vtq_vl_cls_fold": {
+        "q, wqkv, bqkv, ln_w, ln_b": "as vtq_k_cls_fold", "seq_len": "HOST nseq int32",
+        "x": "R rows [0, sum of the lengths), packed; sequence j reads rows [row0[j], row0[j] + seq_len[j]) only",
+        "u": "W/R nseq * (H/64) * H fp32",
+        "part": "W/R nseq * ceil(max length / chunk_rows) * (H/64) * (H + 2) fp32; a sequence's slots behind its own chunks untouched",
+        "z": "as vtq_k_cls_fold", "ctx": "W nseq x H fp32"},
     "vtq_k_diffnet_head": {"d": "R HB x H fp32", "q_out": "W HB fp32"},
     "vtq_k_image_normalize": {"images": "R NI*H*W*3 uint8", "flips": "R NI x 2 int32 (may be NULL)", "out": "W NI*3*H*W fp32"},
     "vtq_k_avgpool2": {"in": "R NC*H*W fp32", "out": "W NC*(H/2)*(W/2) fp32"},
@@ -89,7 +95,8 @@ CONTRACTS = {
     "vtq_k_repeat_mean": {"q": "R R*N fp32", "out": "W N fp64"},
     "vtq_k_rank_metrics": {"a, b": "R N fp64", "work": "W/R 4N fp64", "counts": "W 3 int64", "out": "W 3 fp64"},
 }
-HOST_ONLY = {"vtq_k_gemm_tile_rule", "vtq_k_attention_rule", "vtq_k_gemm_schedule", "vtq_k_cls_fold_chunk_rows"}
+HOST_ONLY = {"vtq_k_gemm_tile_rule", "vtq_k_attention_rule", "vtq_k_gemm_schedule", "vtq_k_cls_fold_chunk_rows", "vtq_vl_attention_blocks"}
+PINNED_ELSEWHERE = {"vtq_vl_attention": "tests/test_gpu_varlen.py (the same arena, beside vtq_forward_varlen)"}
 
 
 def print_contracts():
@@ -103,7 +110,7 @@ def print_contracts():
 
 def test_contract_table_covers_every_kernel_entry():
     hdr = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "include", "vtamiq_hip.h")).read()
-    entries = set(re.findall(r"\b(vtq_k_\w+)\s*\(", hdr)) - HOST_ONLY
+    entries = set(re.findall(r"\b(vtq_(?:k|vl)_\w+)\s*\(", hdr)) - HOST_ONLY - set(PINNED_ELSEWHERE)
     assert entries == set(CONTRACTS), entries ^ set(CONTRACTS)
     assert max(attention_overread_rows(s) for s in range(1, 2049)) == 127
     print_contracts()
@@ -555,6 +562,67 @@ def test_cls_fold(nseq, H, fmt):
         assert e_fold <= 2.0 * e_full, (fmt, H, nseq, S, e_fold, e_full)
 
 
+# ---- vtq_vl_cls_fold ----------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("fmt", ["fp16x3", "bf16"])
+@pytest.mark.parametrize("H", [768, 1024])
+def test_vl_cls_fold(H, fmt):
+    """Lengths (131, 1, chunk, chunk + 1) and (chunk + 1, 2) packed back to back: x of exactly the sum of the lengths, nothing behind it; u,
+    part, z, ctx of exactly the documented sizes, `part` at the pitch of the longest sequence with the slots behind a shorter sequence's own
+    chunks holes.  Every sequence has the bits of vtq_k_cls_fold(nseq = 1, S = its length) on its rows, and that entry's accuracy."""
+    lib = _lib.load()
+    chunk = lib.vtq_k_cls_fold_chunk_rows()
+    nh, dt = H // 64, elt_dtype(fmt)
+    apl, wpl = planes_of(fmt, "a"), planes_of(fmt, "w")
+    for lengths in ((131, 1, chunk, chunk + 1), (chunk + 1, 2)):
+        nseq, R, Rz = len(lengths), sum(lengths), 64
+        c = FoldCase(H, 1, R, fmt, seed=2000 + R)                   # its x: R rows; the parameters
+        starts = [sum(lengths[:j]) for j in range(nseq)]
+        ln = c.ln64()[0]
+        q = ((ln[starts] @ c.W64[:H].t() + c.b[:H].double()) * (LOG2_SCALE if c.q_log2 else 1.0)).float().contiguous()
+        cmax = (max(lengths) + chunk - 1) // chunk
+        slot = nh * (H + 2)
+        L = Layout()
+        L.add("q", (nseq, H), F32)
+        L.add("W", (wpl, 3 * H, H), dt, H * 2, 3 * H * H * 2)
+        L.add("b", (3 * H,), F32), L.add("lw", (H,), F32), L.add("lb", (H,), F32)
+        L.add("x", (R, H), F32)
+        L.add("u", (nseq * nh * H,), F32)
+        L.add("part", (nseq * cmax * slot,), F32)
+        L.add("z", (apl, Rz, nh * H), dt, nh * H * 2, Rz * nh * H * 2)
+        L.add("ctx", (nseq, H), F32)
+        a, v = L.build()
+        v["q"].copy_(q), v["W"].copy_(c.Wp), v["b"].copy_(c.b), v["lw"].copy_(c.lw), v["lb"].copy_(c.lb), v["x"].copy_(c.x[:R])
+        a.scratch("z", "rows >= nseq", nseq * nh * H * 2, (Rz - nseq) * nh * H * 2, Rz * nh * H * 2, apl)
+        for j, S in enumerate(lengths):
+            own = (S + chunk - 1) // chunk
+            if own < cmax:
+                a.hole("part", f"slots [{own}, {cmax}) of sequence {j}", (j * cmax + own) * slot * 4, (cmax - own) * slot * 4)
+        arr = (C.c_int32 * nseq)(*lengths)
+
+        def launch():
+            _lib.check(lib.vtq_vl_cls_fold(v["q"].data_ptr(), v["W"].data_ptr(), 3 * H * H, v["b"].data_ptr(), v["x"].data_ptr(), v["lw"].data_ptr(),
+                                           v["lb"].data_ptr(), nseq, arr, H, num_code(fmt), 1 if c.q_log2 else 0, v["u"].data_ptr(), v["part"].data_ptr(),
+                                           v["z"].data_ptr(), Rz * nh * H, v["ctx"].data_ptr(), stream()))
+
+        def prepare():
+            for n in ("u", "part", "z", "ctx"):
+                v[n].zero_()
+        try:
+            (ctx,) = a.run_twice(launch, lambda: [v["ctx"]], prepare=prepare)
+        except FootprintError as e:
+            raise AssertionError(f"{fmt} H={H} lengths {lengths}: {e}") from e
+        for j, (r0, S) in enumerate(zip(starts, lengths)):
+            one = FoldCase(H, 1, S, fmt, seed=1)                    # sequence j alone: c's parameters and rows [r0, r0 + S) of its x
+            one.Wp, one.W64, one.b, one.lw, one.lb = c.Wp, c.W64, c.b, c.lw, c.lb
+            one.x = torch.zeros_like(one.x)
+            one.x[:S] = c.x[r0:r0 + S]
+            assert torch.equal(ctx[j].view(torch.int32), one.fold(q[j:j + 1])[0].view(torch.int32)), (fmt, H, lengths, j)
+            # accuracy as test_cls_fold bounds the uniform entry: the un-folded fp64 formula, twice the full-layer kernels' error
+            e_fold = fold_err(ctx[j:j + 1], one.ref(q_in=q[j:j + 1])[0])
+            e_full = fold_err(one.full_layer(0), one.ref(token=0)[0])
+            assert e_fold <= 2.0 * e_full, (fmt, H, lengths, j, e_fold, e_full)
+
+
 # ---- vtq_k_diffnet_head -------------------------------------------------------------------------------------------------
 def _model(precision="fp16x3", **vit):
     from vtamiq_amd import VTAMIQ, synth
@@ -807,6 +875,9 @@ def test_rejected_calls_launch_nothing():
     skinny = lambda K=64, num=19: lib.vtq_k_skinny_linear(i0, 64 * 64, 64, i1, 16 * 64, 4, 16, K, num, 0, i2, None, None, None, None, 16, 0, o0, 16, 16,
                                                           None, 0, 0, 0, None, s)
     fold = lambda H=768, num=19: lib.vtq_k_cls_fold(i0, i1, 3 * H * H, i2, i0, 2 * H, i2, i2, 1, 2, H, num, 0, o0, o1, o2, 64 * (H // 64) * H, o0, s)
+    two = (C.c_int32 * 1)(2)
+    vfold = lambda x=i0, nseq=1, seq_len=two, H=768, num=19, q_log2=0: lib.vtq_vl_cls_fold(i0, i1, 3 * H * H, i2, x, i2, i2, nseq, seq_len, H, num, q_log2,
+                                                                                       o0, o1, o2, 64 * (H // 64) * H, o0, s)
     calls = {
         "vtq_k_split: numel % 4": lambda: lib.vtq_k_split(i0, o0, 64, 6, 1, 2, s),
         "vtq_k_layernorm: H = 512": lambda: lib.vtq_k_layernorm(i0, i1, i2, o0, 4 * 512, 4, 512, 1, 2, s),
@@ -825,6 +896,13 @@ def test_rejected_calls_launch_nothing():
         "vtq_k_skinny_linear: unknown num": lambda: skinny(num=99),
         "vtq_k_cls_fold: H = 512": lambda: fold(H=512),
         "vtq_k_cls_fold: unknown num": lambda: fold(num=99),
+        "vtq_vl_cls_fold: NULL x": lambda: vfold(x=None),
+        "vtq_vl_cls_fold: NULL seq_len": lambda: vfold(seq_len=None),
+        "vtq_vl_cls_fold: nseq = 0": lambda: vfold(nseq=0),
+        "vtq_vl_cls_fold: a length of 0": lambda: vfold(nseq=2, seq_len=(C.c_int32 * 2)(2, 0)),
+        "vtq_vl_cls_fold: H = 512": lambda: vfold(H=512),
+        "vtq_vl_cls_fold: unknown num": lambda: vfold(num=99),
+        "vtq_vl_cls_fold: q_log2 on a 1-term num": lambda: vfold(num=17, q_log2=1),
         "vtq_k_diffnet_head: HB = 0": lambda: lib.vtq_k_diffnet_head(None, i0, 0, o0, s),
         "vtq_k_image_normalize: NI = 0": lambda: lib.vtq_k_image_normalize(i0, o0, 0, 8, 8, None, f3, f3, s),
         "vtq_k_avgpool2: H = 1": lambda: lib.vtq_k_avgpool2(i0, o0, 3, 1, 8, s),

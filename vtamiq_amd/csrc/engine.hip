@@ -1785,6 +1785,47 @@ int vtq_k_cls_fold(const float* q, const void* wqkv, int64_t w_plane, const floa
     return 0;
 }
 
+int vtq_vl_cls_fold(const float* q, const void* wqkv, int64_t w_plane, const float* bqkv, const float* x, const float* ln_w, const float* ln_b,
+                    int32_t nseq, const int32_t* seq_len, int32_t H, int32_t num, int32_t q_log2, float* u, float* part, void* z, int64_t z_plane,
+                    float* ctx, void* stream) {
+    const Num nm = num_from_code(num);
+    if (!num_valid(nm) || nm.f16 > 1) return fail("vtq_vl_cls_fold: operand format code %d", num);
+    if (!q || !wqkv || !bqkv || !x || !ln_w || !ln_b || !seq_len || !u || !part || !z || !ctx) return fail("vtq_vl_cls_fold: null argument");
+    if (nseq < 1 || nseq > 65535 || (H != 768 && H != 1024)) return fail("vtq_vl_cls_fold: nseq=%d, H=%d", (int)nseq, (int)H);
+    if (q_log2 && nm.terms != 3) return fail("vtq_vl_cls_fold: q_log2 applies to the 3-term formats only");
+    // the call's tables: row offsets [nseq], then lengths [nseq]
+    std::vector<int> t((size_t)2 * nseq);
+    int64_t rows = 0;
+    int smax = 0;
+    for (int j = 0; j < nseq; ++j) {
+        if (seq_len[j] < 1) return fail("vtq_vl_cls_fold: sequence %d has length %d", j, (int)seq_len[j]);
+        t[j] = (int)rows; t[nseq + j] = seq_len[j];
+        rows += seq_len[j];
+        if (seq_len[j] > smax) smax = seq_len[j];
+        if (rows > INT32_MAX / 4) return fail("vtq_vl_cls_fold: more than %d rows", INT32_MAX / 4);
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const int nh = H / 64;
+    int* dev = nullptr;
+    HIP_TRY(hipMalloc((void**)&dev, t.size() * sizeof(int)));
+    hipError_t err = hipMemcpyAsync(dev, t.data(), t.size() * sizeof(int), hipMemcpyHostToDevice, s);
+    if (err == hipSuccess) {
+        const PlaneOut zo{z, z_plane, nh * H, nm.f16, nm.apl(), nullptr};
+        err = launch_cls_fold(q, (const char*)wqkv + (size_t)H * H * 2, w_plane, H, nm.f16, nm.wpl(), x, 0, ln_w, ln_b, u, part, nseq, smax, H, zo, s,
+                              q_log2 != 0, VarSeq{dev, dev + nseq});
+    }
+    if (err == hipSuccess) {
+        SkinnyArgs a{};
+        a.xa = z; a.xa_plane = z_plane; a.ldx = nh * H; a.xcol64 = H; a.W = (const char*)wqkv + (size_t)2 * H * H * 2; a.w_plane = w_plane;
+        a.R = nseq; a.N = H; a.K = H; a.bias = bqkv + 2 * H; a.epi = SK_PLAIN; a.y = ctx; a.ldy = H; a.ycols = H; a.ya_planes = nm.apl();
+        err = launch_skinny(a, nm, s);
+    }
+    const hipError_t err2 = hipStreamSynchronize(s);        // the tables are temporaries of this call
+    (void)hipFree(dev);
+    if (err != hipSuccess || err2 != hipSuccess) return fail("vtq_vl_cls_fold: %s", hipGetErrorString(err != hipSuccess ? err : err2));
+    return 0;
+}
+
 int vtq_k_diffnet_head(vtq_handle e, const float* d, int32_t HB, float* q_out, void* stream) {
     if (!e || !d || !q_out || HB < 1) return fail("vtq_k_diffnet_head: bad argument");
     if (all_loaded(e, "vtq_k_diffnet_head")) return 1;
