@@ -146,6 +146,14 @@ IMAGE_SIGNATURES = {
                                           C.POINTER(C.c_float), _P, _P, _P, _I, _I, _P]),
 }
 
+# include/vtamiq_hip_tensors.h: the same gather for float images resident on the device (vtamiq_amd.patches.extract_patches_planar);
+# the u8 entry's arguments with the pixel dtype behind image_bytes
+PIXEL_DTYPES = {"float32": 0, "float16": 1, "bfloat16": 2}
+TENSOR_SIGNATURES = {
+    "vtq_k_gather_patches_planar": (C.c_int, [_P, C.c_int64, _I, _P, _P, C.POINTER(C.c_int64), _IP, _IP, _IP, _I, _P, _P, _P,
+                                              C.POINTER(C.c_float), C.POINTER(C.c_float), _P, _P, _P, _I, _I, _P]),
+}
+
 # include/vtamiq_hip_sampler.h: patch coordinates sampled on the device (vtamiq_amd.sampling)
 SAMPLER_SIGNATURES = {
     "vtq_k_sample_grid": (C.c_int, [_P, _P, _IP, C.POINTER(C.c_uint64), _I, C.c_uint64, _I, _P, _P, _P]),
@@ -193,7 +201,7 @@ def load(path: str | None = None) -> C.CDLL:
     # build of an OLDER tree (different ABI: argument layouts may differ) loads only with VTQ_ALLOW_ABI_MISMATCH=1, with a warning.
     relaxed = os.environ.get("VTQ_ALLOW_ABI_MISMATCH") == "1"
     for name, (res, args) in (list(SIGNATURES.items()) + list(ROLLOUT_SIGNATURES.items()) + list(IMAGE_SIGNATURES.items())
-                              + list(SAMPLER_SIGNATURES.items()) + list(WEIGHTED_SAMPLER_SIGNATURES.items())):
+                              + list(TENSOR_SIGNATURES.items()) + list(SAMPLER_SIGNATURES.items()) + list(WEIGHTED_SAMPLER_SIGNATURES.items())):
         if relaxed and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)          # AttributeError if a declared symbol is not exported

@@ -17,9 +17,9 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libvtamiq_hip.so")
 LIB_FP8 = os.path.join(HERE, "libvtamiq_hip_fp8.so")
-SOURCES = ["gemm.hip", "gemm_st.hip", "gemm_rowln.hip", "attention.hip", "attention_varlen.hip", "attention_probs.hip", "attention_rollout.hip", "elementwise.hip", "head.hip", "skinny.hip", "cls_tail.hip", "patches.hip", "patches_ragged.hip", "patch_sampler.hip", "patch_sampler_weighted.hip", "metrics.hip", "mfma_stream.hip", "engine.hip"]
+SOURCES = ["gemm.hip", "gemm_st.hip", "gemm_rowln.hip", "attention.hip", "attention_varlen.hip", "attention_probs.hip", "attention_rollout.hip", "elementwise.hip", "head.hip", "skinny.hip", "cls_tail.hip", "patches.hip", "patches_ragged.hip", "patches_planar.hip", "patch_sampler.hip", "patch_sampler_weighted.hip", "metrics.hip", "mfma_stream.hip", "engine.hip"]
 DEPS = ["dev_common.h", "kernels.h", "launch_common.h", "attention_common.h", os.path.join("..", "..", "include", "vtamiq_hip.h"), os.path.join("..", "..", "include", "vtamiq_hip_fp8.h"),
-        os.path.join("..", "..", "include", "vtamiq_hip_rollout.h"), os.path.join("..", "..", "include", "vtamiq_hip_images.h"),
+        os.path.join("..", "..", "include", "vtamiq_hip_rollout.h"), os.path.join("..", "..", "include", "vtamiq_hip_images.h"), os.path.join("..", "..", "include", "vtamiq_hip_tensors.h"),
         os.path.join("..", "..", "include", "vtamiq_hip_sampler.h"), os.path.join("..", "..", "include", "vtamiq_hip_weighted_sampler.h")]
 # -amdgpu-mfma-vgpr-form: keep MFMA accumulators in VGPRs (no v_accvgpr_read/write shuffles around the softmax)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",

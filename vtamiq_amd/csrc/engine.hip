@@ -21,6 +21,7 @@
 #include "../../include/vtamiq_hip_fp8.h"
 #include "../../include/vtamiq_hip_rollout.h"
 #include "../../include/vtamiq_hip_images.h"
+#include "../../include/vtamiq_hip_tensors.h"
 #include "../../include/vtamiq_hip_sampler.h"
 #include "../../include/vtamiq_hip_weighted_sampler.h"
 #include "kernels.h"
@@ -1868,31 +1869,58 @@ int vtq_k_gather_patches(const float* const* levels, const int32_t* hs, const in
     return 0;
 }
 
-// include/vtamiq_hip_images.h: every check reads HOST arrays only, so a refusal touches no device memory and launches nothing
+// include/vtamiq_hip_images.h, include/vtamiq_hip_tensors.h: the checks the two gathers share, stated once.  Every check reads HOST arrays
+// only, so a refusal touches no device memory and launches nothing.  elem: bytes per pixel element (1 for the uint8 HWC images)
+static int gather_refused(const char* name, int64_t elem, const void* images, int64_t image_bytes, const int32_t* tab, const int32_t* patch_img,
+                          const int64_t* img_off, const int32_t* H, const int32_t* W, const int32_t* row0, int32_t NI, const int32_t* samples,
+                          const int32_t* scale_ids, const float* mean, const float* std_, const float* patches, const float* pos,
+                          int32_t patch_size, int32_t num_scales) {
+    if (!images || !tab || !patch_img || !img_off || !H || !W || !row0 || !samples || !mean || !std_ || !patches || !pos)
+        return fail("%s: null argument", name);
+    if ((uintptr_t)tab % 16) return fail("%s: tab is not 16-byte aligned", name);
+    if (NI < 1) return fail("%s: NI=%d (at least 1)", name, (int)NI);
+    if (patch_size != 16 && patch_size != 8) return fail("%s: patch_size %d (16 or 8)", name, (int)patch_size);
+    if (num_scales < 1 || num_scales > 4) return fail("%s: num_scales=%d (1 .. 4)", name, (int)num_scales);
+    if (!scale_ids && num_scales > 1) return fail("%s: scale_ids are required when num_scales > 1", name);
+    if (row0[0] != 0) return fail("%s: row0[0]=%d (0 required)", name, (int)row0[0]);
+    for (int32_t i = 0; i < NI; ++i) {
+        if (row0[i + 1] < row0[i]) return fail("%s: row0 decreases at image %d", name, (int)i);
+        if (H[i] < patch_size || W[i] < patch_size)
+            return fail("%s: image %d (%d x %d) is smaller than one %d x %d patch", name, (int)i, (int)H[i], (int)W[i], (int)patch_size,
+                        (int)patch_size);
+        if (img_off[i] % elem)
+            return fail("%s: image %d starts at byte %lld, not a multiple of the element size %d", name, (int)i, (long long)img_off[i], (int)elem);
+        if (img_off[i] < 0 || image_bytes < 0 || img_off[i] > image_bytes || (int64_t)3 * H[i] * W[i] > (image_bytes - img_off[i]) / elem)
+            return fail("%s: image %d (%d x %d at byte %lld) leaves the buffer of %lld bytes", name, (int)i, (int)H[i], (int)W[i],
+                        (long long)img_off[i], (long long)image_bytes);
+    }
+    if (row0[NI] < 1) return fail("%s: no patches (row0[NI]=%d)", name, (int)row0[NI]);
+    return 0;
+}
+
 int vtq_k_gather_patches_u8(const uint8_t* images, int64_t image_bytes, const int32_t* tab, const int32_t* patch_img, const int64_t* img_off,
                             const int32_t* H, const int32_t* W, const int32_t* row0, int32_t NI, const int32_t* samples,
                             const int32_t* scale_ids, const int32_t* flips, const float* mean, const float* std_, float* patches, float* pos,
                             float* scales, int32_t patch_size, int32_t num_scales, void* stream) {
-    if (!images || !tab || !patch_img || !img_off || !H || !W || !row0 || !samples || !mean || !std_ || !patches || !pos)
-        return fail("vtq_k_gather_patches_u8: null argument");
-    if ((uintptr_t)tab % 16) return fail("vtq_k_gather_patches_u8: tab is not 16-byte aligned");
-    if (NI < 1) return fail("vtq_k_gather_patches_u8: NI=%d (at least 1)", (int)NI);
-    if (patch_size != 16 && patch_size != 8) return fail("vtq_k_gather_patches_u8: patch_size %d (16 or 8)", (int)patch_size);
-    if (num_scales < 1 || num_scales > 4) return fail("vtq_k_gather_patches_u8: num_scales=%d (1 .. 4)", (int)num_scales);
-    if (!scale_ids && num_scales > 1) return fail("vtq_k_gather_patches_u8: scale_ids are required when num_scales > 1");
-    if (row0[0] != 0) return fail("vtq_k_gather_patches_u8: row0[0]=%d (0 required)", (int)row0[0]);
-    for (int32_t i = 0; i < NI; ++i) {
-        if (row0[i + 1] < row0[i]) return fail("vtq_k_gather_patches_u8: row0 decreases at image %d", (int)i);
-        if (H[i] < patch_size || W[i] < patch_size)
-            return fail("vtq_k_gather_patches_u8: image %d (%d x %d) is smaller than one %d x %d patch", (int)i, (int)H[i], (int)W[i],
-                        (int)patch_size, (int)patch_size);
-        if (img_off[i] < 0 || image_bytes < 0 || img_off[i] > image_bytes || (int64_t)3 * H[i] * W[i] > image_bytes - img_off[i])
-            return fail("vtq_k_gather_patches_u8: image %d (%d x %d at byte %lld) leaves the buffer of %lld bytes", (int)i, (int)H[i], (int)W[i],
-                        (long long)img_off[i], (long long)image_bytes);
-    }
-    if (row0[NI] < 1) return fail("vtq_k_gather_patches_u8: no patches (row0[NI]=%d)", (int)row0[NI]);
+    if (gather_refused("vtq_k_gather_patches_u8", 1, images, image_bytes, tab, patch_img, img_off, H, W, row0, NI, samples, scale_ids, mean, std_,
+                       patches, pos, patch_size, num_scales))
+        return 1;
     HIP_TRY(launch_gather_patches_u8(images, tab, patch_img, samples, scale_ids, flips, patches, pos, scales, row0[NI], mean, std_, patch_size,
                                      num_scales, (hipStream_t)stream));
+    return 0;
+}
+
+int vtq_k_gather_patches_planar(const void* images, int64_t image_bytes, int32_t dtype, const int32_t* tab, const int32_t* patch_img,
+                                const int64_t* img_off, const int32_t* H, const int32_t* W, const int32_t* row0, int32_t NI,
+                                const int32_t* samples, const int32_t* scale_ids, const int32_t* flips, const float* mean, const float* std_,
+                                float* patches, float* pos, float* scales, int32_t patch_size, int32_t num_scales, void* stream) {
+    if (dtype != VTQ_PIXEL_F32 && dtype != VTQ_PIXEL_F16 && dtype != VTQ_PIXEL_BF16)
+        return fail("vtq_k_gather_patches_planar: dtype %d (0 fp32, 1 fp16, 2 bf16)", (int)dtype);
+    if (gather_refused("vtq_k_gather_patches_planar", dtype == VTQ_PIXEL_F32 ? 4 : 2, images, image_bytes, tab, patch_img, img_off, H, W, row0, NI,
+                       samples, scale_ids, mean, std_, patches, pos, patch_size, num_scales))
+        return 1;
+    HIP_TRY(launch_gather_patches_planar(images, dtype, tab, patch_img, samples, scale_ids, flips, patches, pos, scales, row0[NI], mean, std_,
+                                         patch_size, num_scales, (hipStream_t)stream));
     return 0;
 }
 

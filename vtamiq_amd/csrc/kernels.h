@@ -251,6 +251,11 @@ hipError_t launch_gather_patches(const float* const* levels, const int* hs, cons
 hipError_t launch_gather_patches_u8(const uint8_t* images, const int* tab, const int* patch_img, const int* samples, const int* scale_ids,
                                     const int* flips, float* patches, float* pos, float* scales, int64_t total, const float* mean,
                                     const float* sd, int P, int num_scales, hipStream_t s);
+// patches_planar.hip: the same gather for float images, three contiguous CHW planes each (include/vtamiq_hip_tensors.h); dtype 0 fp32,
+// 1 fp16, 2 bf16; the offsets of tab are bytes, multiples of the element size
+hipError_t launch_gather_patches_planar(const void* images, int dtype, const int* tab, const int* patch_img, const int* samples,
+                                        const int* scale_ids, const int* flips, float* patches, float* pos, float* scales, int64_t total,
+                                        const float* mean, const float* sd, int P, int num_scales, hipStream_t s);
 
 // patch_sampler.hip: the samples / scale_ids lists of launch_gather_patches_u8, sampled on the device (include/vtamiq_hip_sampler.h);
 // seg int32 [NS][8], keys uint64 [NS], both on the device; max_cells = the largest Hg * Wg of the table (it sizes the workgroups only)

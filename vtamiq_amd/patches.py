@@ -114,7 +114,7 @@ class ImageTables(NamedTuple):
     row0: np.ndarray          # int32 [NI + 1]  patch-row prefix: image i owns rows [row0[i], row0[i + 1])
     tab: np.ndarray           # int32 [NI, 4]   (img_off low word, high word, H, W): what the kernel reads
     patch_img: np.ndarray     # int32 [total]   the image of every patch row
-    image_bytes: int          # sum of 3 H W
+    image_bytes: int          # sum of 3 H W times the element size (1 for uint8 images)
     total: int                # row0[NI]
 
 
@@ -125,8 +125,9 @@ def _sizes(sizes) -> np.ndarray:
     return sz
 
 
-def image_tables(sizes, lengths) -> ImageTables:
-    """The offset, prefix and image-index tables of NI images [(H_i, W_i) ...] with lengths[i] >= 0 patches each, on the host (numpy only)."""
+def image_tables(sizes, lengths, elem: int = 1) -> ImageTables:
+    """The offset, prefix and image-index tables of NI images [(H_i, W_i) ...] with lengths[i] >= 0 patches each, on the host (numpy only).
+    elem: bytes per pixel element -- 1 for uint8 images, 4 or 2 for the float planes of extract_patches_planar; the offsets are bytes."""
     sz = _sizes(sizes)
     ln = np.asarray(lengths)
     if ln.shape != (sz.shape[0],) or ln.dtype.kind not in "iu":
@@ -134,7 +135,7 @@ def image_tables(sizes, lengths) -> ImageTables:
     ln = ln.astype(np.int64)
     if (ln < 0).any():
         raise ValueError("lengths: >= 0")
-    nbytes = 3 * sz[:, 0] * sz[:, 1]
+    nbytes = 3 * sz[:, 0] * sz[:, 1] * int(elem)
     off = np.concatenate([[0], np.cumsum(nbytes)[:-1]]).astype(np.int64)
     row0 = np.concatenate([[0], np.cumsum(ln)])
     if row0[-1] > 0x7fffffff or (sz > 0x7fffffff).any():
@@ -144,6 +145,15 @@ def image_tables(sizes, lengths) -> ImageTables:
     tab[:, 2:] = sz
     return ImageTables(off, sz[:, 0].astype(np.int32), sz[:, 1].astype(np.int32), row0.astype(np.int32), tab,
                        np.repeat(np.arange(sz.shape[0], dtype=np.int32), ln), int(nbytes.sum()), int(row0[-1]))
+
+
+def table_rows(t: ImageTables, rows, lengths) -> ImageTables:
+    """Tables whose row k is image rows[k] of `t` with lengths[k] patches: an image listed more than once (validation repeats) keeps ONE
+    copy of its pixels, every listing its own patch rows."""
+    rows, lengths = np.asarray(rows, dtype=np.int64), np.asarray(lengths, dtype=np.int64)
+    row0 = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int32)
+    return ImageTables(t.img_off[rows], t.H[rows], t.W[rows], row0, np.ascontiguousarray(t.tab[rows]),
+                       np.repeat(np.arange(len(rows), dtype=np.int32), lengths), t.image_bytes, int(row0[-1]))
 
 
 def check_samples_host_varlen(samples, scale_ids, sizes, lengths, num_scales: int = 1, patch_size: int = 16) -> None:
@@ -163,10 +173,10 @@ def check_samples_host_varlen(samples, scale_ids, sizes, lengths, num_scales: in
     _in_range(smp, lvl, np.repeat(sz, ln, axis=0), num_scales, int(patch_size))           # dims (total, 2): the image of every row
 
 
-def gather_patches_u8(flat: torch.Tensor, tables: ImageTables, dev_tab: torch.Tensor, dev_patch_img: torch.Tensor, samples: torch.Tensor,
-                      scale_ids: Optional[torch.Tensor], flips: Optional[torch.Tensor], num_scales: int, mean, std, patch_size: int):
-    """The launch itself (vtq_k_gather_patches_u8) on the current stream: every tensor is on the device already, `tables` are the host
-    arrays dev_tab / dev_patch_img were copied from.  Nothing here copies or synchronises."""
+def _gather(flat: torch.Tensor, tables: ImageTables, dev_tab, dev_patch_img, samples, scale_ids, flips, num_scales: int, mean, std,
+            patch_size: int):
+    """The launch of either gather on the current stream, chosen by the dtype of `flat`: vtq_k_gather_patches_u8 for uint8 HWC bytes,
+    vtq_k_gather_patches_planar for float CHW planes.  The two entries take the same arguments but for the pixel dtype."""
     lib = _lib.load()
     dev = flat.device
     P, T = int(patch_size), tables.total
@@ -175,13 +185,65 @@ def gather_patches_u8(flat: torch.Tensor, tables: ImageTables, dev_tab: torch.Te
         pos = torch.empty(T, 2, device=dev, dtype=torch.float32)
         scales = torch.empty(T, device=dev, dtype=torch.float32) if num_scales > 1 else None
         as_p = lambda a, t: a.ctypes.data_as(C.POINTER(t))
-        _lib.check(lib.vtq_k_gather_patches_u8(
-            flat.data_ptr(), flat.numel(), dev_tab.data_ptr(), dev_patch_img.data_ptr(), as_p(tables.img_off, C.c_int64),
-            as_p(tables.H, C.c_int32), as_p(tables.W, C.c_int32), as_p(tables.row0, C.c_int32), len(tables.H), samples.data_ptr(),
-            scale_ids.data_ptr() if scale_ids is not None else None, flips.data_ptr() if flips is not None else None,
-            (C.c_float * 3)(*mean), (C.c_float * 3)(*std), patches.data_ptr(), pos.data_ptr(),
-            scales.data_ptr() if scales is not None else None, P, num_scales, torch.cuda.current_stream(dev).cuda_stream))
+        image = (flat.data_ptr(), flat.numel() * flat.element_size())
+        rest = (dev_tab.data_ptr(), dev_patch_img.data_ptr(), as_p(tables.img_off, C.c_int64),
+                as_p(tables.H, C.c_int32), as_p(tables.W, C.c_int32), as_p(tables.row0, C.c_int32), len(tables.H), samples.data_ptr(),
+                scale_ids.data_ptr() if scale_ids is not None else None, flips.data_ptr() if flips is not None else None,
+                (C.c_float * 3)(*mean), (C.c_float * 3)(*std), patches.data_ptr(), pos.data_ptr(),
+                scales.data_ptr() if scales is not None else None, P, num_scales, torch.cuda.current_stream(dev).cuda_stream)
+        if flat.dtype == torch.uint8:
+            _lib.check(lib.vtq_k_gather_patches_u8(*image, *rest))
+        else:
+            _lib.check(lib.vtq_k_gather_patches_planar(*image, _lib.PIXEL_DTYPES[str(flat.dtype).split(".")[-1]], *rest))
     return patches, pos, scales
+
+
+def gather_patches_u8(flat: torch.Tensor, tables: ImageTables, dev_tab: torch.Tensor, dev_patch_img: torch.Tensor, samples: torch.Tensor,
+                      scale_ids: Optional[torch.Tensor], flips: Optional[torch.Tensor], num_scales: int, mean, std, patch_size: int):
+    """The launch itself (vtq_k_gather_patches_u8) on the current stream: every tensor is on the device already, `tables` are the host
+    arrays dev_tab / dev_patch_img were copied from.  Nothing here copies or synchronises."""
+    if flat.dtype != torch.uint8:
+        raise ValueError("gather_patches_u8 takes uint8 bytes")
+    return _gather(flat, tables, dev_tab, dev_patch_img, samples, scale_ids, flips, num_scales, mean, std, patch_size)
+
+
+PLANAR_DTYPES = (torch.float32, torch.float16, torch.bfloat16)
+
+
+def gather_patches_planar(flat: torch.Tensor, tables: ImageTables, dev_tab: torch.Tensor, dev_patch_img: torch.Tensor, samples: torch.Tensor,
+                          scale_ids: Optional[torch.Tensor], flips: Optional[torch.Tensor], num_scales: int, mean, std, patch_size: int):
+    """gather_patches_u8 for float CHW planes (vtq_k_gather_patches_planar): flat is 1-D float32 / float16 / bfloat16 and `tables` were made
+    with elem=flat.element_size().  Nothing here copies or synchronises."""
+    if flat.dtype not in PLANAR_DTYPES:
+        raise ValueError("gather_patches_planar takes float32, float16 or bfloat16 planes")
+    return _gather(flat, tables, dev_tab, dev_patch_img, samples, scale_ids, flips, num_scales, mean, std, patch_size)
+
+
+def _extract_flat(flat: torch.Tensor, sizes, samples, lengths, scale_ids, num_scales, flips, mean, std, patch_size, validate):
+    """The part extract_patches_varlen and extract_patches_planar share: `flat` holds the images back to back (uint8 HWC or float CHW),
+    sizes their (H_i, W_i).  Table building, shape and range checks, the upload of host arguments and the launch."""
+    dev = flat.device
+    P = _patch_size(patch_size)
+    _check_levels(num_scales, scale_ids)
+    lengths = [int(n) for n in (lengths.tolist() if isinstance(lengths, (torch.Tensor, np.ndarray)) else lengths)]
+    tables = image_tables(sizes, lengths, flat.element_size())
+    if tables.total < 1:
+        raise ValueError("no patches: sum(lengths) must be at least 1")
+    if flat.numel() * flat.element_size() != tables.image_bytes:
+        raise ValueError(f"the flat image tensor has {flat.numel() * flat.element_size()} bytes, the sizes need {tables.image_bytes}")
+    to_np = lambda a: a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+    if tuple(samples.shape) != (tables.total, 2):
+        raise ValueError("samples must be int32 (sum(lengths), 2)")
+    if scale_ids is not None and tuple(scale_ids.shape) != (tables.total,):
+        raise ValueError("scale_ids must be int32 (sum(lengths),)")
+    if flips is not None and tuple(flips.shape) != (len(lengths), 2):
+        raise ValueError("flips must be int32 (NI, 2)")
+    if validate:
+        check_samples_host_varlen(to_np(samples), to_np(scale_ids) if scale_ids is not None else None, sizes, lengths, num_scales, P)
+    on_dev = lambda a: torch.as_tensor(a).to(device=dev, dtype=torch.int32).contiguous()
+    return _gather(flat, tables, on_dev(tables.tab), on_dev(tables.patch_img), on_dev(samples),
+                   on_dev(scale_ids) if scale_ids is not None else None, on_dev(flips) if flips is not None else None,
+                   num_scales, mean, std, P)
 
 
 def extract_patches_varlen(images, samples, lengths, scale_ids=None, num_scales: int = 1, flips=None,
@@ -217,24 +279,82 @@ def extract_patches_varlen(images, samples, lengths, scale_ids=None, num_scales:
         flat = torch.cat([i.contiguous().reshape(-1) for i in images])
     if flat.dtype != torch.uint8 or flat.dim() != 1:
         raise ValueError("the flat image tensor must be uint8 and one-dimensional")
-    P = _patch_size(patch_size)
-    _check_levels(num_scales, scale_ids)
-    lengths = [int(n) for n in (lengths.tolist() if isinstance(lengths, (torch.Tensor, np.ndarray)) else lengths)]
-    tables = image_tables(sizes, lengths)
-    if tables.total < 1:
-        raise ValueError("no patches: sum(lengths) must be at least 1")
-    if flat.numel() != tables.image_bytes:
-        raise ValueError(f"the flat image tensor has {flat.numel()} bytes, the sizes need {tables.image_bytes}")
-    to_np = lambda a: a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
-    if tuple(samples.shape) != (tables.total, 2):
-        raise ValueError("samples must be int32 (sum(lengths), 2)")
-    if scale_ids is not None and tuple(scale_ids.shape) != (tables.total,):
-        raise ValueError("scale_ids must be int32 (sum(lengths),)")
-    if flips is not None and tuple(flips.shape) != (len(lengths), 2):
-        raise ValueError("flips must be int32 (NI, 2)")
-    if validate:
-        check_samples_host_varlen(to_np(samples), to_np(scale_ids) if scale_ids is not None else None, sizes, lengths, num_scales, P)
-    on_dev = lambda a: torch.as_tensor(a).to(device=dev, dtype=torch.int32).contiguous()
-    return gather_patches_u8(flat, tables, on_dev(tables.tab), on_dev(tables.patch_img), on_dev(samples),
-                             on_dev(scale_ids) if scale_ids is not None else None, on_dev(flips) if flips is not None else None,
-                             num_scales, mean, std, P)
+    return _extract_flat(flat, sizes, samples, lengths, scale_ids, num_scales, flips, mean, std, patch_size, validate)
+
+
+# ---- float images resident on the device (include/vtamiq_hip_tensors.h, csrc/patches_planar.hip) ------------------------------------------
+class ResidentImages(NamedTuple):
+    """Images that are on the device, inspected on the host without enqueuing anything (resident_images)."""
+    sizes: list               # NI (H, W)
+    dtype: torch.dtype        # uint8: HWC bytes (the u8 gather); float32 / float16 / bfloat16: CHW planes (the planar gather)
+    device: torch.device
+    parts: list               # the tensors as given: one batch or flat tensor, or the list's images
+
+    def flat(self) -> torch.Tensor:
+        """The images back to back in ONE 1-D tensor: a view of a batch or flat tensor (no copy), the concatenation of a list (one copy of
+        the images, on the device and the current stream)."""
+        if len(self.parts) == 1 and self.parts[0].is_contiguous():
+            return self.parts[0].view(-1)
+        return torch.cat([i.contiguous().reshape(-1) for i in self.parts])
+
+
+def resident_images(images, sizes=None, what: str = "images", u8: bool = False) -> ResidentImages:
+    """The input forms of extract_patches_planar (and, with u8=True, their uint8 HWC counterparts), checked on the host:
+      one contiguous batch tensor (NI, 3, H, W) of float pixels -- or (NI, H, W, 3) of uint8 --, used in place;
+      a list of (3, H_i, W_i) float tensors -- or (H_i, W_i, 3) uint8 ones -- of one dtype on one device, concatenated by flat();
+      one flat 1-D tensor with sizes=[(H_i, W_i) ...], used in place.
+    Refused: CPU tensors (RuntimeError); float64 and integer pixels other than uint8 (TypeError); a batch tensor that is not contiguous in
+    its own order -- strided or channels_last -- naming .contiguous(): nothing here copies a strided batch silently (ValueError, like every
+    other malformed argument)."""
+    if isinstance(images, torch.Tensor):
+        ts = [images]
+    else:
+        ts = list(images)
+        if not ts or any(not isinstance(i, torch.Tensor) for i in ts):
+            raise ValueError(f"{what}: a tensor or a non-empty list of tensors")
+    dev, dtype = ts[0].device, ts[0].dtype
+    if dev.type != "cuda":
+        raise RuntimeError(f"{what}: a {dev.type} tensor; images that are resident on the GPU are taken (no CPU fallback on the product path)")
+    if dtype not in PLANAR_DTYPES and not (u8 and dtype == torch.uint8):
+        raise TypeError(f"{what}: float32, float16 or bfloat16 pixels{' or uint8 bytes' if u8 else ''}, not {dtype}")
+    if any(i.device != dev or i.dtype != dtype for i in ts):
+        raise ValueError(f"{what}: tensors of one dtype on one device")
+    hwc = dtype == torch.uint8
+    form = "(H, W, 3)" if hwc else "(3, H, W)"
+    hw = (lambda t: tuple(int(d) for d in t.shape[-3:-1])) if hwc else (lambda t: tuple(int(d) for d in t.shape[-2:]))
+    chan = (lambda t: t.shape[-1]) if hwc else (lambda t: t.shape[-3])
+    if not isinstance(images, torch.Tensor):
+        if sizes is not None:
+            raise ValueError("sizes= goes with a flat image tensor; a list of images carries its own")
+        if any(i.dim() != 3 or chan(i) != 3 for i in ts):
+            raise ValueError(f"{what}: a list of {form} tensors")
+        return ResidentImages([hw(i) for i in ts], dtype, dev, ts)
+    if images.dim() == 1:
+        if sizes is None:
+            raise ValueError("a flat image tensor needs sizes=[(H, W) ...]")
+        if not images.is_contiguous():
+            raise ValueError(f"{what}: the flat tensor is strided: pass images.contiguous()")
+        return ResidentImages([(int(h), int(w)) for h, w in sizes], dtype, dev, ts)
+    if sizes is not None:
+        raise ValueError("sizes= goes with a flat image tensor; a batch tensor carries its own")
+    if images.dim() != 4 or chan(images) != 3 or images.shape[0] < 1:
+        raise ValueError(f"{what}: a batch tensor must be (NI, {form[1:-1]}), NI >= 1")
+    if not images.is_contiguous():
+        raise ValueError(f"{what}: the batch tensor is not contiguous in (NI, {form[1:-1]}) order (strided or channels_last): "
+                         "pass images.contiguous()")
+    return ResidentImages([hw(images)] * images.shape[0], dtype, dev, ts)
+
+
+def extract_patches_planar(images, samples, lengths, scale_ids=None, num_scales: int = 1, flips=None,
+                           mean: Sequence[float] = (0.5, 0.5, 0.5), std: Sequence[float] = (0.5, 0.5, 0.5), patch_size: int = 16,
+                           validate: bool = True, sizes=None) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
+    """extract_patches_varlen for FLOAT images that are already on the device, e.g. the output of another model: float32 / float16 /
+    bfloat16 pixels in CHW order, gathered as they are -- no quantisation to 8 bits, no permute, no host copy.
+      images     ONE contiguous cuda tensor (NI, 3, H, W), used in place with no copy;  or a list of (3, H_i, W_i) cuda tensors of one dtype,
+                 which are CONCATENATED here on the device (one copy of the images: keep them in one flat tensor to avoid it);  or ONE flat
+                 1-D tensor holding the images' planes back to back, with sizes=[(H_i, W_i) ...], used in place
+      the other arguments, the returns and the checks are those of extract_patches_varlen
+    Level 0 is ((float)x - mean[c]) / std[c], the pooled levels the nested 2 x 2 means of it: the bits oracle.patch_oracle gives for the
+    normalised image.  A pixel scale of [0, 1] is the caller's (the reference's to_tensor leaves float arrays unscaled too)."""
+    res = resident_images(images, sizes)
+    return _extract_flat(res.flat(), res.sizes, samples, lengths, scale_ids, num_scales, flips, mean, std, patch_size, validate)

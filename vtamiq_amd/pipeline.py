@@ -33,7 +33,7 @@ from typing import NamedTuple, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from .patches import ImageTables, check_samples_host, check_samples_host_varlen, extract_patches, gather_patches_u8, image_tables
+from .patches import ImageTables, check_samples_host, check_samples_host_varlen, extract_patches, gather_patches_u8, image_tables, table_rows
 from .sampling import (DEFAULT_NUM_SAMPLES_RATIO, MAX_CELLS, PatchSampler, WeightedPatchSampler, as_keys, launch_diff_cells, launch_sample_grid,
                        launch_sample_weighted, patch_counts, plan_samples, plan_samples_weighted, repeat_key, segments_for)
 
@@ -101,10 +101,39 @@ def _host_images(refs, dists, pairs: bool = False):
     return refs, dists
 
 
-def _aligned_sizes(refs, dists) -> None:
-    for b, (r, d) in enumerate(zip(refs, dists)):
-        if r.shape != d.shape:
-            raise ValueError(f"aligned sampling: pair {b}'s images differ in size ({r.shape[:2]}, {d.shape[:2]}); pass 2B sample arrays / aligned=False")
+def _aligned_sizes(sizes_ref, sizes_dist) -> None:
+    """Aligned sampling gives a pair's two images the same coordinates: their (H, W) must be equal."""
+    for b, (r, d) in enumerate(zip(sizes_ref, sizes_dist)):
+        if tuple(r) != tuple(d):
+            raise ValueError(f"aligned sampling: pair {b}'s images differ in size ({tuple(r)}, {tuple(d)}); pass 2B sample arrays / aligned=False")
+
+
+def default_keys(count: int, n: int) -> list:
+    """keys=None: image / pair b of a caller's i-th submission (count = i) gets (i << 32) | b."""
+    return [(count << 32) | b for b in range(n)]
+
+
+def pair_keys(keys, count: int, B: int, aligned: bool):
+    """(reference keys, distorted keys) of B pairs as uint64: B keys, one per pair (aligned: both images get the pair's key), or 2B,
+    references first; None: from the submission counter, the distorted image's with the top bit flipped when unaligned."""
+    if aligned:
+        k = as_keys(default_keys(count, B) if keys is None else keys, B)
+        return k, k
+    k2 = as_keys(keys, 2 * B) if keys is not None else as_keys([k ^ (s << 63) for s in (0, 1) for k in default_keys(count, B)], 2 * B)
+    return k2[:B], k2[B:]
+
+
+def repeat_keys(keys: np.ndarray, repeats: int) -> np.ndarray:
+    """The keys of `repeats` validation repeats, repeat-major: sampling.repeat_key(key, r) for r = 0 .. repeats - 1."""
+    return np.array([repeat_key(k, r) for r in range(repeats) for k in keys.tolist()], dtype=np.uint64)
+
+
+def mean_over_repeats(q: torch.Tensor, repeats: int) -> torch.Tensor:
+    """Repeat-major scores (repeats * n,) -> their mean over the repeats on the device (fp64 (n,)); q itself for one repeat."""
+    if repeats == 1:
+        return q
+    from .validate import average_over_repeats
+    return average_over_repeats(q, repeats)
 
 
 def _ref_indices(ref_index, G: int, M: int) -> list:
@@ -274,7 +303,7 @@ def pair_arguments(refs, dists, samples, lengths=None, scale_ids=None, num_scale
     B = len(refs)
     first, second = _two_sides(list(samples), B, "samples")
     if first is second:
-        _aligned_sizes(refs, dists)
+        _aligned_sizes([r.shape[:2] for r in refs], [d.shape[:2] for d in dists])
     ids = None
     if scale_ids is not None and num_scales > 1:
         ids_first, ids_second = _two_sides(list(scale_ids), B, "scale_ids")
@@ -319,15 +348,12 @@ def plan_sampled_batch(sizes_first, sizes_second, counts_first, counts_second, k
         raise ValueError(f"{side} patches on one side ({R} repeats), the pipeline was built for max_patches={max_patches}")
     kf, ks = as_keys(keys_first, nf), as_keys(keys_second, ns_)
     rows = np.concatenate([np.tile(np.arange(nf), R), np.tile(np.arange(nf, nf + ns_), R)])          # the base image of every table row
-    keys = np.array([repeat_key(k, r) for r in range(R) for k in kf.tolist()] + [repeat_key(k, r) for r in range(R) for k in ks.tolist()],
-                    dtype=np.uint64)
+    keys = np.concatenate([repeat_keys(kf, R), repeat_keys(ks, R)])
     sizes = [base.sizes[i] for i in rows]
     lengths = base.lengths[rows]
     plan = plan_samples(sizes, lengths.tolist(), num_scales, scale_num_samples_ratio, patch_size)
     t = base.tables
-    row0 = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int32)
-    tables = ImageTables(t.img_off[rows], t.H[rows], t.W[rows], row0, np.ascontiguousarray(t.tab[rows]),
-                         np.repeat(np.arange(len(rows), dtype=np.int32), lengths), t.image_bytes, int(row0[-1]))
+    tables = table_rows(t, rows, lengths)
     layout = block_layout(len(rows), tables.total, len(plan.seg), num_scales > 1)
     batch = VarlenBatch(sizes, lengths, R * nf, tables, layout.words)
     return SampledBatch(batch, np.ascontiguousarray(plan.seg), np.ascontiguousarray(keys[plan.seg_image]), nf + ns_, R, layout.uploaded,
@@ -500,10 +526,6 @@ class ImagePairVarlenPipeline(_SlotRing):
         return plan_sampled_batch(sizes_first, sizes_second, counts_first, counts_second, keys_first, keys_second, repeats=repeats,
                                   scale_num_samples_ratio=scale_num_samples_ratio, **self._caps)
 
-    def _default_keys(self, n: int) -> list:
-        """keys=None: image / pair b of this pipeline's i-th submission gets (i << 32) | b."""
-        return [(self.count << 32) | b for b in range(n)]
-
     def _sample_and_gather(self, sb: SampledBatch, images, seed: int, sampler: Optional[PatchSampler]):
         """Stage the batch's images and tables and, as the upload's step on the copy stream, launch the sampler into the slot's device
         block: behind the tables it reads and under the forward of the batch before, not in front of this batch's gather on the current
@@ -564,12 +586,6 @@ class ImagePairVarlenPipeline(_SlotRing):
 
         return self._upload_and_gather(sb, behind)
 
-    def _mean_over_repeats(self, q: torch.Tensor, repeats: int) -> torch.Tensor:
-        if repeats == 1:
-            return q
-        from .validate import average_over_repeats
-        return average_over_repeats(q, repeats)
-
     def submit_images(self, refs, dists, patch_count, keys=None, seed: int = 0, aligned: bool = True, num_repeats: int = 1,
                       sampler: Optional[PatchSampler] = None, scale_num_samples_ratio: float = DEFAULT_NUM_SAMPLES_RATIO) -> torch.Tensor:
         """submit() without coordinates: B pairs of host images uint8 [H, W, 3] and patch_count patches per image (one int, or B), sampled
@@ -584,11 +600,8 @@ class ImagePairVarlenPipeline(_SlotRing):
         refs, dists = _host_images(refs, dists, pairs=True)
         B = len(refs)
         if aligned:
-            _aligned_sizes(refs, dists)
-            kr = kd = as_keys(self._default_keys(B) if keys is None else keys, B)
-        else:
-            k2 = as_keys(keys, 2 * B) if keys is not None else as_keys([k ^ (s << 63) for s in (0, 1) for k in self._default_keys(B)], 2 * B)
-            kr, kd = k2[:B], k2[B:]
+            _aligned_sizes([r.shape[:2] for r in refs], [d.shape[:2] for d in dists])
+        kr, kd = pair_keys(keys, self.count, B, aligned)
         counts = patch_counts(patch_count, B)
         weighted = isinstance(sampler, WeightedPatchSampler)
         if weighted and any(r.shape != d.shape for r, d in zip(refs, dists)):
@@ -599,7 +612,7 @@ class ImagePairVarlenPipeline(_SlotRing):
             out = self._sample_weighted_and_gather(sb, refs + dists, seed, sampler, scale_num_samples_ratio)
         else:
             out = self._sample_and_gather(sb, refs + dists, seed, sampler)
-        return self._mean_over_repeats(self._as_pairs(sb.batch, out), sb.repeats)
+        return mean_over_repeats(self._as_pairs(sb.batch, out), sb.repeats)
 
     def submit_group_images(self, refs, dists, ref_index, patch_count, keys=None, seed: int = 0, num_repeats: int = 1,
                             sampler: Optional[PatchSampler] = None, scale_num_samples_ratio: float = DEFAULT_NUM_SAMPLES_RATIO,
@@ -617,8 +630,8 @@ class ImagePairVarlenPipeline(_SlotRing):
             if np.ndim(patch_count) != 0:
                 raise ValueError("patch_count per reference needs patch_count_dist for the distorted images")
             patch_count_dist = patch_count
-        k = as_keys(self._default_keys(G + M) if keys is None else keys, G + M)
+        k = as_keys(default_keys(self.count, G + M) if keys is None else keys, G + M)
         sb = self.plan_sampled([r.shape[:2] for r in refs], [d.shape[:2] for d in dists], patch_counts(patch_count, G),
                                patch_counts(patch_count_dist, M), k[:G], k[G:], num_repeats, scale_num_samples_ratio)
         out = self._sample_and_gather(sb, refs + dists, seed, sampler)
-        return self._mean_over_repeats(self._as_group(sb.batch, out, [i + r * G for r in range(sb.repeats) for i in idx]), sb.repeats)
+        return mean_over_repeats(self._as_group(sb.batch, out, [i + r * G for r in range(sb.repeats) for i in idx]), sb.repeats)
