@@ -522,12 +522,20 @@ def test_skinny_linear_epilogues(fmt):
     assert (pv - torch.relu(full[:, H:])).abs().max().item() < tolp * full.abs().max().item()
 
 
+def _head_catalogue_params():
+    """The head's row counts on either side of every switch of launch_skinny's rows-per-workgroup rule (tests/tail_rows.py), one model each."""
+    from tests import tail_rows as R
+    return [pytest.param(dict(), tuple(R.head_catalogue(**R.VIT_B)), id="vitb-catalogue"),
+            pytest.param(dict(vit_config=dict(variant="ViT-L16", num_keep_layers=1)), tuple(R.head_catalogue(**R.VIT_L)), id="vitl-catalogue")]
+
+
 @pytest.mark.parametrize("kw,HB", [(dict(), 32), (dict(ca_reduction=16, num_rgs=2, num_rcabs=3), 5), (dict(calibrate=False), 7),
-                                   (dict(vit_config=dict(variant="ViT-L16", num_keep_layers=1)), 130)])
+                                   (dict(vit_config=dict(variant="ViT-L16", num_keep_layers=1)), 130)] + _head_catalogue_params())
 @pytest.mark.parametrize("precision", ["fp16x3", "bf16"])
 def test_diffnet_head_against_oracle(kw, HB, precision):
     """vtq_k_diffnet_head (quality_decoder -> q_predictor as skinny MFMA stages, fp16 hi/lo whatever the encoder's precision)
-    against oracle.quality_decoder / q_predictor on the same CLS differences."""
+    against oracle.quality_decoder / q_predictor in fp64 on the same CLS differences, row by row.  HB a tuple: those row counts in turn
+    on one engine, ascending then descending (a smaller batch behind a larger one reads planes the larger one wrote)."""
     import ctypes as C
     import json
     from oracle import vtamiq_oracle as O
@@ -540,17 +548,20 @@ def test_diffnet_head_against_oracle(kw, HB, precision):
     m.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})
     m = m.to(DEV).eval()
     H = m.spec.hidden_size
+    counts = list(HB) + list(HB)[::-1] if isinstance(HB, tuple) else [HB]
     p = torch.zeros(1, 4, 3, 16, 16, device=DEV)
-    with torch.no_grad():
+    with torch.no_grad():                                   # creates the engine; vtq_k_diffnet_head grows the workspace to its own row count
         m((p, p), (torch.zeros(1, 4, 2, device=DEV),) * 2, ((torch.zeros(1, 4, device=DEV),) * 2 if m.spec.use_scale_embedding else (None, None)))
-    d = _randn(HB, H, seed=62, scale=0.5)
-    q = torch.zeros(HB, device=DEV)
-    _lib.check(_lib.load().vtq_k_diffnet_head(m._engine, d.data_ptr(), HB, q.data_ptr(), stream()))
-    torch.cuda.synchronize()
-    t = O.to_torch(sd)
-    ref = O.q_predictor(t, O.quality_decoder(t, m.spec, d.cpu())).numpy()
-    err = (q.cpu().numpy() - ref)
-    assert abs(err).max() < HEAD_TOL * max(1.0, abs(ref).max()), (abs(err).max(), abs(ref).max())
+    t = {k: v.to(DEV) for k, v in O.to_torch(sd, torch.float64).items()}
+    d_all = _randn(max(counts), H, seed=62, scale=0.5)
+    for n in counts:
+        d = d_all[:n].contiguous()
+        q = torch.zeros(n, device=DEV)
+        _lib.check(_lib.load().vtq_k_diffnet_head(m._engine, d.data_ptr(), n, q.data_ptr(), stream()))
+        torch.cuda.synchronize()
+        ref = O.q_predictor(t, O.quality_decoder(t, m.spec, d.double())).cpu().numpy()
+        err = abs(q.cpu().numpy() - ref)                    # per row
+        assert err.max() < HEAD_TOL * max(1.0, abs(ref).max()), (n, int(err.argmax()), err.max(), abs(ref).max())
 
 
 @pytest.mark.parametrize("P", [16, 8])

@@ -15,8 +15,13 @@ Each case exists for the kernel path the library's rules pick for it:
   vitl_b4_n1024        ViT-L/16 over 3 scales: H = 1024, 16 heads, K = 1024 / 4096
   vitb8_b3_n77         ViT-B/8 (patch K = 192, padded), registers, one adapter pair: nseq * S = 480, not a multiple of 256
 
-The CLS-only last layer (cls_tail.hip: rows_ln_kernel, cls_attention_kernel, the skinny out-proj / fc1 / fc2), final_diff_kernel and
-the skinny head are checked the same way: the engine's scores against fp64 from the engine's own stream entering the last layer.
+  vitb_b81_n8          (the tail check only) 81 pairs of 8 patches: 162 sequences, more rows than any other engine-level case gives the tail
+
+The CLS-only last layer (cls_tail.hip: rows_ln_kernel, cls_fold, the skinny query / value / out-proj / fc1 / fc2), final_diff_kernel and
+the skinny head have no stage stops.  Here their SCORES are compared with fp64 from the engine's own stream entering the last layer, at
+production size (test_cls_tail_teacher_forced); the tail's ROWS -- what encode_reference() exports -- are measured per sequence and
+channel against the same fp64 reference in tests/test_gpu_tail_rows.py, at every row count at which launch_skinny changes kernel form, and
+the difference and the head from caller-held rows there too.
 """
 import json
 import math
@@ -87,8 +92,13 @@ CASES = {
     "vitl_b4_n1024": (lambda: _own_case(dict(vit_config=dict(variant="ViT-L16", num_scales=3)), 4, 1024, 53, 63), ["fp16x3", "bf16x3", "fp16"], 0),
     "vitb8_b3_n77": (lambda: _own_case(dict(vit_config=dict(variant="ViT-B8", num_keep_layers=3, num_scales=2, num_extra_tokens=2, num_adapters=1,
                                                         use_layer_scale=True)), 3, 77, 8, 18), ["fp16x3", "bf16x3", "bf16"], 0),
+    # the tail check only: 162 sequences, past the switches of launch_skinny's rows-per-workgroup rule at 80 | 81 and 160 | 161 rows
+    # (tests/tail_rows.py), through the pair entry and final_diff
+    # (stress5h_b32_n500's weights: the head at its operating point -- a random head's scores of 8-patch images are cancellation remainders)
+    "vitb_b81_n8": (lambda: _own_case(dict(vit_config=dict(variant="ViT-B16")), 81, 8, 32, 19, dict(qk=5.0, head=True)), ALL_MODES, 0),
 }
-TAIL_CASES = ["stress5h_b32_n500", "refdefault_b16_n512", "vitl_b4_n1024"]
+STAGE_CASES = ["c2_b32_n500", "stress5h_b32_n500", "c2shape_b2_n500", "refdefault_b16_n512", "vitl_b4_n1024", "vitb8_b3_n77"]
+TAIL_CASES = ["stress5h_b32_n500", "refdefault_b16_n512", "vitl_b4_n1024", "vitb_b81_n8"]
 
 _cache = {}
 
@@ -209,7 +219,7 @@ def _case_params(names, with_options=False):
     return out
 
 
-@pytest.mark.parametrize("name,mode", _case_params(CASES))
+@pytest.mark.parametrize("name,mode", _case_params(STAGE_CASES))
 def test_stages_teacher_forced(name, mode):
     c = get_case(name)
     spec, B, N = c["spec"], c["B"], c["N"]
@@ -223,9 +233,10 @@ def test_stages_teacher_forced(name, mode):
 
 # ---- the CLS-only last layer and the head ------------------------------------------------------------------------------
 
-def tail_ref(sdr, spec, x, B, t):
-    """Scores from the stream x [2B, S, H] entering the last layer: that layer's token-t rows (K / V from every row), encoder_norm, the
-    ref - dist difference and the head, in fp64."""
+def tail_rows_ref(sdr, spec, x, t, hidden=False):
+    """The residual rows xr [nseq, H] of token t behind the last layer, before encoder_norm, from the stream x [nseq, S, H] entering that
+    layer: LayerNorm 1, the token's query against keys and values of every row, out-proj, LayerNorm 2 and the MLP, in fp64.  These are the
+    rows encode_reference() exports (tests/test_gpu_tail_rows.py).  hidden=True: (xr, the fc1 + GELU rows [nseq, mlp_dim] fc2 consumes)."""
     L, nh = spec.num_layers, spec.num_heads
     pre = f"transformer.encoder.layers.{L - 1}."
     nseq, S, H = x.shape
@@ -235,10 +246,24 @@ def tail_ref(sdr, spec, x, B, t):
     k = _lin(ln, sdr, pre + "attn.key").view(nseq, S, nh, dh).transpose(1, 2)
     v = _lin(ln, sdr, pre + "attn.value").view(nseq, S, nh, dh).transpose(1, 2)
     ctx = (torch.softmax(q @ k.transpose(-1, -2) / math.sqrt(dh), -1) @ v).reshape(nseq, H)
-    xr = x[:, t] + branch(sdr, spec, pre, _lin(ctx, sdr, pre + "attn.out"), 1)
-    xr = xr + branch(sdr, spec, pre, O.mlp(sdr, pre, O._layer_norm(xr, sdr[pre + "ffn_norm.weight"], sdr[pre + "ffn_norm.bias"])), 2)
+    xa = x[:, t] + branch(sdr, spec, pre, _lin(ctx, sdr, pre + "attn.out"), 1)
+    h = Fn.gelu(_lin(O._layer_norm(xa, sdr[pre + "ffn_norm.weight"], sdr[pre + "ffn_norm.bias"]), sdr, pre + "ffn.fc1"))      # O.mlp, in its two halves
+    xr = xa + branch(sdr, spec, pre, _lin(h, sdr, pre + "ffn.fc2"), 2)
+    return (xr, h) if hidden else xr
+
+
+def tail_scores(sdr, spec, xr, B):
+    """Scores of B pairs from their 2B rows xr behind the last layer (references first): encoder_norm, ref - dist, the head, in fp64."""
     y = O._layer_norm(xr, sdr["transformer.encoder.encoder_norm.weight"], sdr["transformer.encoder.encoder_norm.bias"])
     return O.head(sdr, spec, y[:B, None], y[B:, None], 0)
+
+
+def tail_ref(sdr, spec, x, B, t, rows=False):
+    """Scores from the stream x [2B, S, H] entering the last layer: that layer's token-t rows (K / V from every row), encoder_norm, the
+    ref - dist difference and the head, in fp64.  rows=True: (scores, the rows xr before encoder_norm)."""
+    xr = tail_rows_ref(sdr, spec, x, t)
+    q = tail_scores(sdr, spec, xr, B)
+    return (q, xr) if rows else q
 
 
 @pytest.mark.parametrize("name,mode,options", _case_params(TAIL_CASES, with_options=True))
